@@ -19,9 +19,12 @@ HBM, rank r processes crops r, r+N, ... (K objects per GPU: "scaling": "weak") a
 rank 0 inside the timed region (r3g/dist.py; the reference uses a process pool and the filesystem,
 src/2d_to_3d_models/run.py:176-193): value = N*K / max-over-ranks time.  A second, shorter measurement with a FIXED
 total of 8 crops (configs[1]'s scene split over the N GPUs, objects claimed dynamically from the shared queue) is
-reported as "strong".
+reported as "strong" (--full only).
 
-Rank 0 prints one JSON line.  Besides the contract fields it carries
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the --steps objects and prints the headline figure; with
+--dump-outputs DIR it first writes the last timed object's mesh (the arrays a caller of the path receives) as
+DIR/mesh_vertices.npy (float32, V x 3) and DIR/mesh_faces.npy (float64 vertex indices, F x 3) -- above 60 MB in all, the
+same seeded sample of rows (np.random.default_rng(0)) of each.  With --full the line also carries
   roofline     : the dominant kernel family (bf16 MFMA GEMM), timed live with HIP events on the launch stream
                  over one further object: achieved = sum of algorithmic FLOPs / sum of launch durations
   roofline_mc  : the HBM-bound kernel of the path (marching cubes): algorithmic bytes 4 (R+1)^3 + 12 V + 12 F over its
@@ -30,6 +33,7 @@ Rank 0 prints one JSON line.  Besides the contract fields it carries
                  this box's host cores on a bounded sample of the same workload and extrapolated (rank 0, N=1 only)
   mc_parity    : the last timed object's mesh (faces AND float32 vertices) against the C oracle's mesh of the same grid,
                  computed for the CPU baseline anyway: "exact" or the run fails
+  strong       : the strong-scaling block (N > 1 or a launcher-started run)
 """
 import argparse
 import ctypes
@@ -181,6 +185,28 @@ def cpu_baseline(cfg, steps, R, grid_np):
                      "how": "the same modules and sample under torch.autocast('cpu', dtype=torch.bfloat16); marching cubes as in fp32"}}
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6       # (below 64 MB with the .npy headers, in either unit)
+
+
+def dump_outputs(path, mesh):
+    """the last timed object's mesh as <path>/mesh_vertices.npy (float32) and <path>/mesh_faces.npy (float64 indices, exact);
+    above DUMP_LIMIT_BYTES in all, the same fraction of rows of each, chosen by a fixed seed (rows kept in order)"""
+    if mesh is None:                     # (no surface: the path returns None for the object)
+        arrays = {"mesh_vertices": np.zeros((0, 3), np.float32), "mesh_faces": np.zeros((0, 3), np.float64)}
+    else:
+        arrays = {"mesh_vertices": mesh[0].cpu().numpy().astype(np.float32),
+                  "mesh_faces": mesh[1].cpu().numpy().astype(np.float64)}
+    total = sum(x.nbytes for x in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES / total
+        for k, x in arrays.items():
+            rows = np.sort(np.random.default_rng(0).choice(len(x), int(len(x) * keep), replace=False))
+            arrays[k] = x[rows]
+    os.makedirs(path, exist_ok=True)
+    for k, x in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -198,7 +224,14 @@ def main():
     ap.add_argument("--fp8-geo", action="store_true",
                     help="BASELINE.json configs[3] direction: the geo decoder's c_q / MLP GEMMs on fp8 (e4m3) operands; NOT the "
                          "headline configuration (the line says so in dtype / config)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check beside the headline figure: roofline (one further event-timed launch group), "
+                         "CPU baseline + marching-cubes parity, and the strong-scaling block of a multi-rank run")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed object's mesh as DIR/mesh_vertices.npy and DIR/mesh_faces.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -325,8 +358,11 @@ def main():
         per_rank_weak = rdist.exchange_json({"rank": rank, "objects": len(meshes), "compute_s": round(t_compute, 4), "queue_wait_s": 0.0,
                                              "gather_s": round(t_gather, 4), "end_wait_s": round(t_wait, 4)}, name="bench_weak_ranks", dst=0)
 
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, last)
+
     strong = None
-    if dist is not None:
+    if dist is not None and a.full:
         # strong scaling: a FIXED total of 8 crops per GPU of the node (configs[2]: 8 scenes x 8 objects on 8 GPUs), claimed
         # dynamically B at a time (r3g.dist.WorkQueue), meshes gathered -- enough objects per rank for the queue to balance
         total_s = 8 * world
@@ -396,7 +432,7 @@ def main():
         out["dit_f16_fallbacks"] = ffi.counter("dit_f16_fallbacks")
         out["dit_groups"] = ffi.counter("dit_groups")
 
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         L = ffi.lib()
         # one further object with every launch bracketed by HIP events on its stream.  The optional second-stream
         # overlap (a GEMM beside the attention kernel; off by default) stays off for this object so that a launch
@@ -483,7 +519,7 @@ def main():
     bad = False
     if hasattr(pipe, "close_prefetch"):
         pipe.close_prefetch()       # the host-preparation thread ends here
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         oracle_mesh, out["cpu_baseline"] = cpu_baseline(cfg, S, R, last_grid.cpu().numpy())
         # the C oracle's mesh of the last TIMED object's grid against the mesh the timed region produced
         if oracle_mesh is None or last is None:

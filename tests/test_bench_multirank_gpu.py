@@ -30,7 +30,7 @@ def test_bench_with_eight_ranks_on_one_device(world):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--model", "mini", "--inference-steps", "2", "--octree-resolution", "64",
-           "--steps", "4", "--warmup", "1", "--objects-per-launch", "2", "--no-roofline"]
+           "--steps", "4", "--warmup", "1", "--objects-per-launch", "2", "--full", "--no-roofline"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -204,6 +204,32 @@ def test_bench_workload_definition():
         assert (rgb[al == 0] == 255).all()                     # white where transparent
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed mesh as float32 vertices and exact float64 faces; above the size limit the same
+    seeded rows of each array, in order, the same from run to run"""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    rng = np.random.default_rng(5)
+    v = torch.from_numpy(rng.standard_normal((1000, 3)).astype(np.float32))
+    f = torch.from_numpy(rng.integers(0, 1000, (2000, 3)).astype(np.int32))
+    bench.dump_outputs(str(tmp_path / "all"), (v, f))
+    gv, gf = np.load(tmp_path / "all" / "mesh_vertices.npy"), np.load(tmp_path / "all" / "mesh_faces.npy")
+    assert gv.dtype == np.float32 and np.array_equal(gv, v.numpy())
+    assert gf.dtype == np.float64 and np.array_equal(gf, f.numpy().astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", (gv.nbytes + gf.nbytes) // 4)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), (v, f))
+    for name, full in (("mesh_vertices", gv), ("mesh_faces", gf)):
+        a, b = np.load(tmp_path / "s1" / (name + ".npy")), np.load(tmp_path / "s2" / (name + ".npy"))
+        assert np.array_equal(a, b) and len(a) == len(full) // 4
+        assert all(any(np.array_equal(r, q) for q in full) for r in a[:20])      # rows of the output, not new values
+    assert sum(os.path.getsize(tmp_path / "s1" / n) for n in os.listdir(tmp_path / "s1")) <= bench.DUMP_LIMIT_BYTES + 512
+    bench.dump_outputs(str(tmp_path / "none"), None)                # no surface: empty arrays, same names
+    assert np.load(tmp_path / "none" / "mesh_vertices.npy").shape == (0, 3)
+
+
 def test_committed_bench_line_has_the_contract_fields():
     """the last bench line measured on the MI355X box (profiles/r*_bench.json) against the driver's contract: one JSON object,
     the named keys with the right types, a roofline and a cpu_baseline object; frac = achieved / peak"""

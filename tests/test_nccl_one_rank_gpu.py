@@ -69,8 +69,8 @@ def test_bench_under_the_drivers_launch_line_at_one_rank_uses_rccl():
     launcher's environment and goes through its multi-rank path on an RCCL group of one (broadcast of the crops into HBM, meshes
     gathered as device tensors, the strong block's queue) -- small model settings, a functional test"""
     p = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "mini", "--inference-steps", "2",
-                   "--octree-resolution", "64", "--steps", "2", "--warmup", "1", "--objects-per-launch", "2", "--no-roofline",
-                   "--no-cpu-baseline"], 1500)
+                   "--octree-resolution", "64", "--steps", "2", "--warmup", "1", "--objects-per-launch", "2", "--full",
+                   "--no-roofline", "--no-cpu-baseline"], 1500)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -9,7 +9,7 @@
 #   texprof    kernel trace of the texture step
 #   mc / tex / attn   marching-cubes timeline, texture step time, attention generations
 #   suite      the whole -m gpu suite
-#   bench      the driver's invocation of bench.py
+#   bench      the driver's invocation of bench.py, with --full (roofline, CPU baseline, mc_parity)
 #   evidence <commit> [objects per launch]  kernel trace + PMC passes (tools/profile_evidence.sh), tables -> gpurun_out/r05_*.md
 set -x
 cd "$(dirname "$0")/.."
@@ -61,7 +61,7 @@ ab)
         for side in a b; do
             if [ $side = a ]; then OPT="$A"; else OPT="$B"; fi
             [ "$OPT" = "-" ] && OPT=""
-            R3G_OPTIONS="$OPT" timeout 300 python bench.py --gpus 1 --steps $K --warmup $W --no-cpu-baseline > $O/r05_ab_${side}${i}.json 2> $O/r05_ab_${side}${i}.err
+            R3G_OPTIONS="$OPT" timeout 300 python bench.py --full --gpus 1 --steps $K --warmup $W --no-cpu-baseline > $O/r05_ab_${side}${i}.json 2> $O/r05_ab_${side}${i}.err
             python - <<PY
 import json
 d=json.loads(open("$O/r05_ab_${side}${i}.json").read().strip().splitlines()[-1])
@@ -96,7 +96,7 @@ suite)
     tail -15 $O/r05_gpu_tests.txt
     ;;
 bench)
-    timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_bench.json 2> $O/r05_bench.err
+    timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r05_bench.json 2> $O/r05_bench.err
     cut -c1-600 $O/r05_bench.json; tail -2 $O/r05_bench.err
     ;;
 evidence)

@@ -10,7 +10,7 @@
 #   texprof             kernel trace of the texture step (tests/tex_stage_time.py) by kernel and by (kernel, grid)
 #   mc                  marching-cubes timeline on the blob and noise fields
 #   suite               the whole -m gpu suite
-#   bench               the driver's invocation of bench.py
+#   bench               the driver's invocation of bench.py, with --full (roofline, CPU baseline, mc_parity)
 #   cfg4                configs[3]-shaped bench line (513^3, fp8 geo decoder) + the texture step's time
 #   evidence <commit> [objects per launch]   kernel trace + PMC passes (tools/profile_evidence.sh), tables -> gpurun_out/r06_*
 #   attnpmc             SQ_INSTS_VALU / SQ_INSTS_MFMA of the attention kernels, variant 0 and 1
@@ -47,7 +47,7 @@ abn)
         for OPT in "$@"; do
             n=$((n + 1))
             [ "$OPT" = "-" ] && OPT=""
-            R3G_OPTIONS="$OPT" timeout 300 python bench.py --gpus 1 --steps $K --warmup $W --no-cpu-baseline > $O/r06_ab_${n}_${i}.json 2> $O/r06_ab_${n}_${i}.err
+            R3G_OPTIONS="$OPT" timeout 300 python bench.py --full --gpus 1 --steps $K --warmup $W --no-cpu-baseline > $O/r06_ab_${n}_${i}.json 2> $O/r06_ab_${n}_${i}.err
             python - <<PY
 import json
 try:
@@ -67,7 +67,7 @@ ablib)
     for i in 1 2; do
         for side in a b; do
             if [ $side = a ]; then export R3G_LIBRARY="$(pwd)/$OTHER"; else unset R3G_LIBRARY; fi
-            timeout 300 python bench.py --gpus 1 --steps $K --warmup $W --no-cpu-baseline > $O/r06_ablib_${side}${i}.json 2> $O/r06_ablib_${side}${i}.err
+            timeout 300 python bench.py --full --gpus 1 --steps $K --warmup $W --no-cpu-baseline > $O/r06_ablib_${side}${i}.json 2> $O/r06_ablib_${side}${i}.err
             python - <<PY
 import json
 try:
@@ -98,11 +98,11 @@ suite)
     tail -15 $O/r06_gpu_tests.txt
     ;;
 bench)
-    timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench.json 2> $O/r06_bench.err
+    timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r06_bench.json 2> $O/r06_bench.err
     cut -c1-800 $O/r06_bench.json; tail -2 $O/r06_bench.err
     ;;
 cfg4)
-    timeout 900 python bench.py --gpus 1 --octree-resolution 512 --fp8-geo --steps 4 --warmup 4 --no-cpu-baseline > $O/r06_bench_cfg4.json 2> $O/r06_bench_cfg4.err
+    timeout 900 python bench.py --full --gpus 1 --octree-resolution 512 --fp8-geo --steps 4 --warmup 4 --no-cpu-baseline > $O/r06_bench_cfg4.json 2> $O/r06_bench_cfg4.err
     cut -c1-1200 $O/r06_bench_cfg4.json; tail -3 $O/r06_bench_cfg4.err
     ;;
 texprof)
