@@ -468,6 +468,44 @@ __global__ void fourier_grid_kernel(uint16_t* out, int64_t start, int count, int
     for (int c = dim; c < 64; ++c) o[c] = 0;
 }
 
+// The same embedding for LISTED points of the lattice (hierarchical volume decoder): row i is point list[i], rows in
+// [count, rows) are padding (the origin, as fourier_grid_kernel's rows behind the grid).  Every channel is the expression
+// fourier_grid_kernel evaluates for it, so a listed point's row equals the dense kernel's row bit for bit; a lane owns 8
+// channels of a point and writes them with one 16-byte store.
+__global__ __launch_bounds__(256) void fourier_points_kernel(uint16_t* out, const int32_t* __restrict__ list, int count, int rows,
+                                                             int R, double bound, int nf, int pi) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = (int)(t >> 3), part = (int)(t & 7);
+    if (i >= rows) return;
+    const int n = R + 1;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (i < count) {
+        const int64_t idx = list[i];
+        const int kk = (int)(idx % n), jj = (int)((idx / n) % n), ii = (int)(idx / ((int64_t)n * n));
+        if (ii < n) { x = lin_coord(ii, R, bound); y = lin_coord(jj, R, bound); z = lin_coord(kk, R, bound); }
+    }
+    const int dim = 3 + 6 * nf;
+    uint32_t o[4];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int ch = part * 8 + e;
+        uint16_t v = 0;
+        if (ch < 3) {
+            v = f2bf(ch == 0 ? x : ch == 1 ? y : z);
+        } else if (ch < dim) {
+            const int r = ch - 3, is_cos = r >= 3 * nf, rr = is_cos ? r - 3 * nf : r;
+            const int c = rr / nf, f = rr % nf;
+            float fr = (float)(1 << f);
+            if (pi) fr *= 3.14159265358979323846f;
+            const float a = (c == 0 ? x : c == 1 ? y : z) * fr;
+            v = f2bf(is_cos ? cosf(a) : sinf(a));
+        }
+        if (e & 1) o[e >> 1] |= (uint32_t)v << 16;
+        else o[e >> 1] = v;
+    }
+    *reinterpret_cast<uint4*>(out + (int64_t)i * 64 + part * 8) = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 template <bool XBF16, int NV, int RPW>
 __global__ __launch_bounds__(256) void ln_dot_kernel(const float* x, int64_t ldx, int rows, int C, int do_ln,
                                                      const float* lnw, const float* lnb, float eps, const float* w,
@@ -728,6 +766,15 @@ hipError_t fourier_grid_launch(uint16_t* out, int64_t start, int count, int R, d
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(fourier_grid_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, s, out, start, count, R, bound,
                        num_freqs, include_pi);
+    return hipGetLastError();
+}
+
+hipError_t fourier_points_launch(uint16_t* out, const int32_t* list, int count, int rows, int R, double bound, int num_freqs,
+                                 int include_pi, hipStream_t s) {
+    if (3 + 6 * num_freqs > 64 || count > rows) return hipErrorInvalidValue;
+    ProfScope prof_scope_(PC_ELEMWISE, (double)rows * 128 + (double)count * 4, s);
+    hipLaunchKernelGGL(fourier_points_kernel, dim3(blocks_for((int64_t)rows * 8, 256)), dim3(256), 0, s, out, list, count, rows, R,
+                       bound, num_freqs, include_pi);
     return hipGetLastError();
 }
 

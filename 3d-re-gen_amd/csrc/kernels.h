@@ -239,6 +239,10 @@ hipError_t swiglu_launch(const uint16_t* in, int64_t ldi, uint16_t* out, int64_t
 // Fourier features of dense grid points [start, start+count): bf16 [count][64] = (xyz, sin(x 2^k).., cos.., 0 pad)
 hipError_t fourier_grid_launch(uint16_t* out, int64_t start, int count, int R, double bound, int num_freqs,
                                int include_pi, hipStream_t s);
+// the same rows for listed points: row i < count is grid point list[i] (bit-identical to fourier_grid_launch's row for that
+// index), rows [count, rows) are padding
+hipError_t fourier_points_launch(uint16_t* out, const int32_t* list, int count, int rows, int R, double bound, int num_freqs,
+                                 int include_pi, hipStream_t s);
 // logits[r] = LN(x[r]) . w + b  (ln_post + output_proj fused);  x f32 [rows][C]
 // EPI_RESID_BF16_LND's two small kernels (elem.hip): gw[n] = lnw[n] * w[n], consts = {sum gw, sum lnb[n] w[n] + b}; and the merge of the
 // per-chunk statistics into out[row] = rstd * (dot - mean * consts[0]) + consts[1]

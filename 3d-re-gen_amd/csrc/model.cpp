@@ -63,6 +63,7 @@ static bool g_geo_q_cache = true;   // keep the object-independent query side of
 static bool g_dit_f16_guard = true;    // option "dit_f16_guard": check the latents of an fp16-stream group, fall back to fp32 on overflow
 static bool g_geo_ln3_fold = true;    // option "geo_ln3_fold" (round 6): the geo decoder's ln_3 folded into c_proj's epilogue (statistics) and c_fc (W' = W gamma, rstd (acc - mean c1) + c2)
 static bool g_geo_lnd_fused = true;   // option "geo_lnd_fused" (round 6): ln_post + output_proj folded into the geo decoder's last residual GEMM
+static int64_t g_geo_q_cache_builds = 0;   // allocations of Model::GeoCache so far (r3g_get_counter "geo_q_cache_builds")
 static int64_t g_dit_groups = 0;         // launch groups r3g_flow_sample_batch has run (r3g_get_counter)
 static int g_dit_f16_fallbacks = 0;    // how often that happened (r3g_set_option("dit_f16_fallbacks_reset", ...) / stderr line)
 static bool g_dit_resid_f16 = true;   // the DiT's residual stream of the de-duplicated CFG path in fp16 (the reference's activation type) instead of fp32
@@ -137,6 +138,10 @@ struct Model {
         unsigned epoch = 0;                     // option epoch the built passes belong to (kernel generations change what Q holds)
         bool refused = false;                   // allocation failed for this (R, bound): do not try again
     } gq;
+    // hierarchical volume decoder (r3g_grid_query_hier): the grids of the levels below the finest, the active list of the level
+    // being built and its logits; grown on demand, released with the model
+    char *hier_grids = nullptr, *hier_idx = nullptr, *hier_val = nullptr;
+    size_t hier_grids_bytes = 0, hier_idx_bytes = 0, hier_val_bytes = 0;
     std::string err;
 
     const Tensor* find(const std::string& name) const {
@@ -794,12 +799,19 @@ static int layernorm_fp8(const float* x, int64_t ldx, uint8_t* y8, int64_t ldy8,
     return R3G_OK;
 }
 
-static int grid_query(Model& m, double bound, int R, float* grid, int64_t start, int64_t count, hipStream_t s) {
+// A pass takes its points either from the contiguous range [start, start + count) of the (R+1)^3 grid and writes their logits
+// to grid[start ...] (list == nullptr: the dense decoder), or from list[0 .. count) and writes them to grid[0 .. count) (the
+// hierarchical decoder's listed points; start is 0).  Everything between the Fourier features and the logits is the same
+// sequence of launches.  `cache` = false keeps the call away from the query-side cache: it neither reads nor builds it and does
+// not touch its (R, bound) key (listed points and the coarse levels of a hierarchical decode).
+static int grid_query(Model& m, double bound, int R, float* grid, int64_t start, int64_t count, hipStream_t s,
+                      const int32_t* list = nullptr, bool cache = true) {
     const r3g_model_config& c = m.c;
     if (!m.have_z) return fail(R3G_ERR_STATE, "r3g_grid_query: r3g_vae_decode has not run");
     const int W = m.W, Nl = c.vae_num_latents, heads = m.Wh;
     const int64_t total = (int64_t)(R + 1) * (R + 1) * (R + 1);
     if (start < 0 || count < 0 || start + count > total) return fail(R3G_ERR_INVALID, "grid_query: range outside the grid");
+    if (list && start != 0) return fail(R3G_ERR_INVALID, "grid_query: listed points start at 0");
     const std::string g = "vae.geo_decoder";
     Lin lq, lcq, lproj, lfc, lfp;
     R3G_RC(get_lin(m, g + ".query_proj", true, &lq));
@@ -833,7 +845,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
     // the query-side cache (Model::GeoCache): bf16 stream, bf16 c_q, and room for 2 x passes x qc x W bf16 in HBM
     Model::GeoCache& gq = m.gq;
     const int64_t passes_all = (total + m.qc - 1) / m.qc;
-    bool use_cache = g_geo_q_cache && xb && !f8q;
+    bool use_cache = g_geo_q_cache && xb && !f8q && cache && !list;
     if (use_cache && (gq.R != R || gq.bound != bound)) {
         if (gq.x0) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(gq.x0); gq.x0 = nullptr; gq.Q = nullptr; }
         gq.R = R; gq.bound = bound; gq.passes = 0; gq.built.clear(); gq.refused = false;
@@ -858,6 +870,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
             gq.refused = true;            // every pass is recomputed, as before
         } else {
             gq.Q = gq.x0 + n_cached * (int64_t)m.qc * W;
+            ++g_geo_q_cache_builds;
             gq.passes = n_cached;
             gq.built.assign((size_t)n_cached, 0);
         }
@@ -909,7 +922,8 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
             R3G_RC(fill_f32(m.fp8_sconst, m.qc, kGeoHiddenScale, s));
         }
         if (!hit) {
-            R3G_TRY(fourier_grid_launch(m.inb, p0, npad, R, bound, c.vae_num_freqs, c.vae_include_pi, s));
+            if (list) R3G_TRY(fourier_points_launch(m.inb, list + off, n, npad, R, bound, c.vae_num_freqs, c.vae_include_pi, s));
+            else R3G_TRY(fourier_grid_launch(m.inb, p0, npad, R, bound, c.vae_num_freqs, c.vae_include_pi, s));
             R3G_RC(gemm(m.inb, 64, 0, lq, 0, W, xb ? (void*)x0 : (void*)m.f32a, W, 0, n, 64, epi_x0, nullptr, 0, 1, s));
             const float* xin = xb ? reinterpret_cast<const float*>(x0) : m.f32a;
             if (f8q) R3G_RC(layernorm_fp8(xin, W, xn8, W, m.fp8_sa, n, W, l1w, l1b, 1e-6f, s, xb));
@@ -1040,6 +1054,9 @@ static void model_free(Model* m) {
     if (m->fp8_sconst) (void)hipFree(m->fp8_sconst);
     if (m->db.base) (void)hipFree(m->db.base);
     if (m->gq.x0) (void)hipFree(m->gq.x0);
+    if (m->hier_grids) (void)hipFree(m->hier_grids);
+    if (m->hier_idx) (void)hipFree(m->hier_idx);
+    if (m->hier_val) (void)hipFree(m->hier_val);
     delete m;
 }
 
@@ -1243,6 +1260,7 @@ int r3g_get_counter(const char* name, int64_t* value) {
     if (!name || !value) return fail(R3G_ERR_INVALID, "r3g_get_counter: null argument");
     if (!strcmp(name, "dit_f16_fallbacks")) *value = g_dit_f16_fallbacks;
     else if (!strcmp(name, "dit_groups")) *value = g_dit_groups;
+    else if (!strcmp(name, "geo_q_cache_builds")) *value = g_geo_q_cache_builds;
     else return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
     return R3G_OK;
 }
@@ -1291,6 +1309,88 @@ int r3g_grid_query(r3g_ctx* ctx, double bound, int octree_resolution, float* d_g
     NEED_MODEL("r3g_grid_query");
     if (!d_grid || octree_resolution < 1) return fail(R3G_ERR_INVALID, "r3g_grid_query: bad argument");
     return grid_query(*m, bound, octree_resolution, d_grid, start, count, (hipStream_t)stream);
+}
+
+int r3g_grid_query_points(r3g_ctx* ctx, double bound, int octree_resolution, const int32_t* d_idx, int64_t count, float* d_values,
+                          void* stream) {
+    NEED_MODEL("r3g_grid_query_points");
+    if (octree_resolution < 1 || octree_resolution > 1289 || count < 0 || (count && (!d_idx || !d_values)))
+        return fail(R3G_ERR_INVALID, "r3g_grid_query_points: bad argument");
+    if (g_geo_fp8) return fail(R3G_ERR_INVALID, "r3g_grid_query_points: not available with option geo_fp8");
+    if (count == 0) return R3G_OK;
+    return grid_query(*m, bound, octree_resolution, d_values, 0, count, (hipStream_t)stream, d_idx, false);
+}
+
+// levels(R, min_resolution): halve while even and the half is >= min_resolution; coarsest first
+static std::vector<int> hier_levels(int R, int min_resolution) {
+    std::vector<int> l{R};
+    while (l.back() % 2 == 0 && l.back() / 2 >= min_resolution) l.push_back(l.back() / 2);
+    std::reverse(l.begin(), l.end());
+    return l;
+}
+
+int r3g_grid_query_hier(r3g_ctx* ctx, double bound, int octree_resolution, double mc_level, double band, int min_resolution,
+                        float* d_grid, int64_t* stats, int n_stats, void* stream) {
+    NEED_MODEL("r3g_grid_query_hier");
+    const int R = octree_resolution;
+    if (!d_grid || R < 1 || R > 1289 || min_resolution < 1 || !(band >= 0.0) || (stats && n_stats < 0))
+        return fail(R3G_ERR_INVALID, "r3g_grid_query_hier: bad argument");
+    if ((uintptr_t)d_grid % 16) return fail(R3G_ERR_INVALID, "r3g_grid_query_hier: d_grid must be 16-byte aligned");
+    if (g_geo_fp8) return fail(R3G_ERR_INVALID, "r3g_grid_query_hier: not available with option geo_fp8");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    const std::vector<int> lv = hier_levels(R, min_resolution);
+    const int L = (int)lv.size();
+    if (stats && n_stats < 4 + 2 * L) return fail(R3G_ERR_INVALID, "r3g_grid_query_hier: stats needs %d slots", 4 + 2 * L);
+    auto pts = [](int r) { return (int64_t)(r + 1) * (r + 1) * (r + 1); };
+    std::vector<int64_t> evaluated((size_t)L, 0);
+    int64_t unsafe = 0;
+    if (L == 1) {
+        // nothing to refine from: the dense decoder (and its query-side cache), exactly as r3g_grid_query
+        R3G_RC(grid_query(*m, bound, R, d_grid, 0, pts(R), s));
+        evaluated[0] = pts(R);
+    } else {
+        std::vector<size_t> off((size_t)L, 0);
+        size_t need = 0;
+        for (int l = 0; l + 1 < L; ++l) {
+            off[(size_t)l] = need;
+            need += ((size_t)pts(lv[(size_t)l]) * 4 + 255) & ~(size_t)255;
+        }
+        R3G_RC(c->reserve(&m->hier_grids, &m->hier_grids_bytes, need, "hipMalloc(hier level grids)"));
+        float* G = reinterpret_cast<float*>(m->hier_grids + off[0]);
+        R3G_RC(grid_query(*m, bound, lv[0], G, 0, pts(lv[0]), s, nullptr, false));
+        evaluated[0] = pts(lv[0]);
+        for (int l = 1; l < L; ++l) {
+            const bool finest = l == L - 1;
+            int64_t count = 0;
+            R3G_RC(hier_select(c, G, lv[(size_t)l - 1] + 1, mc_level, band, finest ? 1 : 0, &count, s));
+            if (count) {
+                R3G_RC(c->reserve(&m->hier_idx, &m->hier_idx_bytes, (size_t)count * 4, "hipMalloc(hier index list)"));
+                R3G_RC(c->reserve(&m->hier_val, &m->hier_val_bytes, (size_t)count * 4, "hipMalloc(hier values)"));
+                R3G_RC(hier_indices(c, reinterpret_cast<int32_t*>(m->hier_idx), s));
+                R3G_RC(grid_query(*m, bound, lv[(size_t)l], reinterpret_cast<float*>(m->hier_val), 0, count, s,
+                                  reinterpret_cast<const int32_t*>(m->hier_idx), false));
+            }
+            float* F = finest ? d_grid : reinterpret_cast<float*>(m->hier_grids + off[(size_t)l]);
+            R3G_RC(hier_merge(c, G, reinterpret_cast<const float*>(m->hier_val), F, s));
+            evaluated[(size_t)l] = count;
+            G = F;
+        }
+        if (stats) R3G_RC(hier_unsafe_cells(c, d_grid, mc_level, &unsafe, s));
+    }
+    if (stats) {
+        int64_t total = 0;
+        for (int l = 0; l < L; ++l) {
+            stats[4 + 2 * l] = lv[(size_t)l];
+            stats[5 + 2 * l] = evaluated[(size_t)l];
+            total += evaluated[(size_t)l];
+        }
+        stats[0] = L;
+        stats[1] = total;
+        stats[2] = pts(R);
+        stats[3] = unsafe;
+    }
+    return R3G_OK;
 }
 
 // ---- single-op entry points (parity tests call the kernels through the C ABI) ---------------------------

@@ -39,6 +39,56 @@ int Ctx::reserve(char** buf, size_t* have, size_t need, const char* what) {
     *have = need;
     return R3G_OK;
 }
+
+// ---- hierarchical volume decoder: planner (model-free) -------------------------------------------------------------
+int hier_select(Ctx* c, const float* d_coarse, int n_coarse, double level, double band, int is_finest, int64_t* count, hipStream_t s) {
+    c->hier_selected = false;
+    if (n_coarse < 2 || n_coarse > 645) return fail(R3G_ERR_INVALID, "r3g_hier_select: n_coarse outside [2, 645] (int32 indices of the fine lattice)");
+    if (!(band >= 0.0)) return fail(R3G_ERR_INVALID, "r3g_hier_select: band must be >= 0");
+    HierLayout lay;
+    const size_t need = hier_workspace_bytes(n_coarse, &lay);
+    int rc = c->reserve(&c->hier_ws, &c->hier_ws_bytes, need, "hipMalloc(hier workspace)");
+    if (rc) return rc;
+    hipError_t e = hier_select_launch(d_coarse, level, band, is_finest, c->hier_ws, lay, s);
+    if (e != hipSuccess) return hip_fail(e, "hier_select_launch");
+    e = hipMemcpyAsync(c->h_small, c->hier_ws + lay.off_small, 8, hipMemcpyDeviceToHost, s);    // the level's one read-back
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(hier count)");
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(hier select)");
+    c->hier_lay = lay;
+    c->hier_count = (int64_t) * (const unsigned long long*)c->h_small;
+    c->hier_selected = true;
+    *count = c->hier_count;
+    return R3G_OK;
+}
+
+int hier_indices(Ctx* c, int32_t* d_idx_out, hipStream_t s) {
+    if (!c->hier_selected) return fail(R3G_ERR_STATE, "r3g_hier_indices: no successful r3g_hier_select precedes this call");
+    if (c->hier_count == 0) return R3G_OK;
+    if (!d_idx_out) return fail(R3G_ERR_INVALID, "r3g_hier_indices: null argument");
+    hipError_t e = hier_indices_launch(c->hier_ws, c->hier_lay, d_idx_out, s);
+    return e == hipSuccess ? R3G_OK : hip_fail(e, "hier_indices_launch");
+}
+
+int hier_merge(Ctx* c, const float* d_coarse, const float* d_values, float* d_fine_out, hipStream_t s) {
+    if (!c->hier_selected) return fail(R3G_ERR_STATE, "r3g_hier_merge: no successful r3g_hier_select precedes this call");
+    if (!d_coarse || !d_fine_out || (c->hier_count && !d_values)) return fail(R3G_ERR_INVALID, "r3g_hier_merge: null argument");
+    if ((uintptr_t)d_fine_out % 16) return fail(R3G_ERR_INVALID, "r3g_hier_merge: d_fine_out must be 16-byte aligned");
+    hipError_t e = hier_merge_launch(c->hier_ws, c->hier_lay, d_coarse, d_values, d_fine_out, s);
+    return e == hipSuccess ? R3G_OK : hip_fail(e, "hier_merge_launch");
+}
+
+int hier_unsafe_cells(Ctx* c, const float* d_fine, double level, int64_t* count, hipStream_t s) {
+    if (!c->hier_selected) return fail(R3G_ERR_STATE, "hier_unsafe_cells: no successful select precedes this call");
+    hipError_t e = hier_unsafe_launch(c->hier_ws, c->hier_lay, d_fine, level, s);
+    if (e != hipSuccess) return hip_fail(e, "hier_unsafe_launch");
+    e = hipMemcpyAsync(c->h_small, c->hier_ws + c->hier_lay.off_small + 8, 8, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(hier unsafe cells)");
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(hier unsafe cells)");
+    *count = (int64_t) * (const unsigned long long*)c->h_small;
+    return R3G_OK;
+}
 }  // namespace r3g
 
 using namespace r3g;
@@ -86,6 +136,7 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->mc_ws) (void)hipFree(c->mc_ws);
     if (c->mesh_ws) (void)hipFree(c->mesh_ws);
     if (c->tex_ws) (void)hipFree(c->tex_ws);
+    if (c->hier_ws) (void)hipFree(c->hier_ws);
     if (c->h_small) (void)hipHostFree(c->h_small);
     c->release_model();
     c->release_unet();
@@ -138,6 +189,23 @@ int r3g_mc_emit(r3g_ctx* ctx, float* d_verts, int32_t* d_faces, const double* xf
                                   d_verts, d_faces, xform, reverse_faces, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "mc_emit_launch");
     return R3G_OK;
+}
+
+// ---- hierarchical volume decoder: the planner steps on their own ----------------------------------------------
+int r3g_hier_select(r3g_ctx* ctx, const float* d_coarse, int n_coarse, double level, double band, int is_finest, int64_t* count,
+                    void* stream) {
+    if (!ctx || !d_coarse || !count) return fail(R3G_ERR_INVALID, "r3g_hier_select: null argument");
+    return hier_select(reinterpret_cast<Ctx*>(ctx), d_coarse, n_coarse, level, band, is_finest, count, (hipStream_t)stream);
+}
+
+int r3g_hier_indices(r3g_ctx* ctx, int32_t* d_idx_out, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_hier_indices: null argument");
+    return hier_indices(reinterpret_cast<Ctx*>(ctx), d_idx_out, (hipStream_t)stream);
+}
+
+int r3g_hier_merge(r3g_ctx* ctx, const float* d_coarse, const float* d_values, float* d_fine_out, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_hier_merge: null argument");
+    return hier_merge(reinterpret_cast<Ctx*>(ctx), d_coarse, d_values, d_fine_out, (hipStream_t)stream);
 }
 
 // ---- mesh cleaners -------------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "hier_kernels.h"
 #include "kernels.h"
 #include "mc_kernels.h"
 
@@ -32,12 +33,25 @@ struct Ctx {
     char* tex_ws = nullptr;
     size_t tex_ws_bytes = 0;
 
+    // hierarchical volume decoder: mask / prefix of the last r3g_hier_select
+    char* hier_ws = nullptr;
+    size_t hier_ws_bytes = 0;
+    HierLayout hier_lay{};
+    int64_t hier_count = 0;
+    bool hier_selected = false;
+
     int reserve(char** buf, size_t* have, size_t need, const char* what);
     void* model = nullptr;  // r3g::Model (model.cpp)
     void release_model();
     void* unet = nullptr;   // r3g::Unet (unet.cpp)
     void release_unet();
 };
+
+// the planner steps behind r3g_hier_select / _indices / _merge (r3g_api.cpp); r3g_grid_query_hier drives them too
+int hier_select(Ctx* c, const float* d_coarse, int n_coarse, double level, double band, int is_finest, int64_t* count, hipStream_t s);
+int hier_indices(Ctx* c, int32_t* d_idx_out, hipStream_t s);
+int hier_merge(Ctx* c, const float* d_coarse, const float* d_values, float* d_fine_out, hipStream_t s);
+int hier_unsafe_cells(Ctx* c, const float* d_fine, double level, int64_t* count, hipStream_t s);
 
 }  // namespace r3g
 #endif

@@ -59,6 +59,11 @@ SYMBOLS = {
     "r3g_flow_sample_batch": (_I, [_P, _P, _P, _I, _I, ctypes.c_float, ctypes.c_float, _I, _P]),
     "r3g_vae_decode": (_I, [_P, _P, _P, _P]),
     "r3g_grid_query": (_I, [_P, _D, _I, _P, ctypes.c_int64, ctypes.c_int64, _P]),
+    "r3g_hier_select": (_I, [_P, _P, _I, _D, _D, _I, _I64P, _P]),
+    "r3g_hier_indices": (_I, [_P, _P, _P]),
+    "r3g_hier_merge": (_I, [_P, _P, _P, _P, _P]),
+    "r3g_grid_query_points": (_I, [_P, _D, _I, _P, ctypes.c_int64, _P, _P]),
+    "r3g_grid_query_hier": (_I, [_P, _D, _I, _D, _D, _I, _P, _I64P, _I, _P]),
     "r3g_unet_create": (_I, [_P, _P]),
     "r3g_unet_set_tensor": (_I, [_P, ctypes.c_char_p, _P, _I, ctypes.c_int64, ctypes.c_int64]),
     "r3g_unet_resnet": (_I, [_P, ctypes.c_char_p, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -147,7 +152,7 @@ def check(rc):
 
 
 def counter(name):
-    """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups")"""
+    """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "geo_q_cache_builds")"""
     v = ctypes.c_int64(0)
     check(lib().r3g_get_counter(name.encode(), ctypes.byref(v)))
     return int(v.value)

@@ -214,3 +214,32 @@ class ShapeModel:
             _l.check(self.L.r3g_grid_query(self.ctx, float(bound), int(octree_resolution), out.data_ptr(), int(start),
                                            int(count), self._s()))
         return out
+
+    def grid_query_points(self, bound, octree_resolution, idx, out=None):
+        """the geo decoder at listed points of the (R+1)^3 lattice (int32 linear indices, any order) -> f32 [len(idx)];
+        a point's logit equals grid_query's for the same index bit for bit"""
+        idx = idx.to(self.device, torch.int32).contiguous()
+        if out is None:
+            out = torch.empty((idx.numel(),), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _l.check(self.L.r3g_grid_query_points(self.ctx, float(bound), int(octree_resolution), idx.data_ptr() if idx.numel() else None,
+                                                  int(idx.numel()), out.data_ptr() if idx.numel() else None, self._s()))
+        return out
+
+    def grid_query_hier(self, bound, octree_resolution, mc_level=0.0, band=0.95, min_resolution=63, out=None, stats=True):
+        """hierarchical volume decoding (r3g_grid_query_hier): a full (R+1)^3 grid whose points near the surface hold the dense
+        decoder's values, and {"levels", "evaluated_per_level", "evaluated", "dense_points", "unsafe_cells"} (None without stats)"""
+        n = octree_resolution + 1
+        if out is None:
+            out = torch.empty((n, n, n), dtype=torch.float32, device=self.device)
+        st = (ctypes.c_int64 * 36)()
+        with torch.cuda.device(self.device):
+            _l.check(self.L.r3g_grid_query_hier(self.ctx, float(bound), int(octree_resolution), float(mc_level), float(band),
+                                                int(min_resolution), out.data_ptr(), st if stats else None, 36 if stats else 0,
+                                                self._s()))
+        if not stats:
+            return out, None
+        nl = int(st[0])
+        return out, {"levels": [int(st[4 + 2 * i]) for i in range(nl)],
+                     "evaluated_per_level": [int(st[5 + 2 * i]) for i in range(nl)],
+                     "evaluated": int(st[1]), "dense_points": int(st[2]), "unsafe_cells": int(st[3])}

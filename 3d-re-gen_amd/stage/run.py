@@ -146,6 +146,23 @@ def objects_per_launch(config):
     return max(1, int(config.get("r3g_objects_per_launch", 4)))
 
 
+def volume_decoder(config):
+    """private key `r3g_volume_decoder`: vanilla (default: the dense grid query) | hierarchical (upstream's
+    pipeline.enable_flashvdm(): a coarse grid densely, then only the points near the surface).  None when the
+    key is absent: the pipeline keeps what it was constructed with (R3G_VOLUME_DECODER, default vanilla)."""
+    v = config.get("r3g_volume_decoder")
+    if v is not None and v not in ("vanilla", "hierarchical"):
+        raise ValueError("r3g_volume_decoder: %r is not one of vanilla, hierarchical" % (v,))
+    return v
+
+
+def apply_volume_decoder(config, shapegen):
+    v = volume_decoder(config)
+    if v is not None:
+        shapegen.enable_flashvdm(enabled=(v == "hierarchical"))
+    return shapegen
+
+
 def shape_meshes(images, shapegen, config):
     """reference :77-84 for a group of images: the raw marching-cubes meshes, in order (None where extraction failed).
     Every object gets a generator seeded with cfg.seed, exactly as the reference seeds each of its calls (:82)."""
@@ -265,6 +282,7 @@ def run_rank(config, image_paths, output_folder, rank, world, factory, swallow_e
     from PIL import Image
     device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")) if torch.cuda.is_available() else "cpu"
     shapegen, texgen, cleaners = factory(config, device)
+    apply_volume_decoder(config, shapegen)
     results = []
     todo = partition(len(image_paths), rank, world)
     B = objects_per_launch(config)
@@ -364,6 +382,7 @@ def run_distributed(config, input_folder, output_folder, rank, world, factory):
         if wd is not None:
             wd.beat("loading the models")
         shapegen, texgen, cleaners = factory(config, device)
+        apply_volume_decoder(config, shapegen)
         if wd is not None:
             wd.beat("models loaded")
 

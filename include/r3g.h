@@ -231,6 +231,48 @@ int r3g_vae_decode(r3g_ctx* ctx, const float* d_latents, float* d_z_out, void* s
 int r3g_grid_query(r3g_ctx* ctx, double bound, int octree_resolution, float* d_grid, int64_t start, int64_t count,
                    void* stream);
 
+/* ---- hierarchical volume decoding (upstream: pipeline.enable_flashvdm(); opt-in, the default stays r3g_grid_query) ------------
+ * The dense decoder evaluates all (R+1)^3 points although marching cubes only reads the cells the surface passes through.  The
+ * hierarchical decoder evaluates a coarse lattice densely and, level by level, only the points near the surface of the level
+ * below.  It is DEFINED here and in DESIGN.md ("Hierarchical volume decoding"); it is modelled on upstream's hierarchical
+ * decoder but not pinned to it (parity-unpinned, like the rest of the VAE).
+ *   levels(R, min_resolution): start from R; while the value is even and its half is >= min_resolution, append the half;
+ *   coarsest first (256 -> 64, 128, 256; an odd R -> R alone: the dense decoder).  Level l has R_l + 1 points per axis; fine
+ *   index 2p is coarse point p.
+ *   From the complete grid G of the level below, the iso level and a band:  s(p) = G(p) > level (as a double, NaN: false -- the
+ *   marching-cubes inside test);  near(p) = some 6-neighbour q inside the grid has s(q) != s(p);  cand(p) = near(p) or
+ *   |G(p) - level| < band (double arithmetic, NaN: false);  e = 0 when the level being built is the finest, else 1;  C = cand
+ *   dilated e times by the 3x3x3 box;  F = the seed F0(2p) = C(p) dilated 2 - e times on the fine lattice (clipped to the grid).
+ *   The active points are F in ascending linear index; the decoder is evaluated at each of them with that level's own
+ *   coordinates; every other fine point q takes G(q >> 1 per axis).
+ * r3g_hier_select: steps above for one level on ANY coarse fp32 grid [n_coarse]^3 (2 <= n_coarse <= 645; no model needed):
+ *   keeps the mask and its rank table in the context (like r3g_mc_count) and returns the number of active points of the
+ *   (2 n_coarse - 1)^3 fine lattice in *count.  Synchronous: one 8-byte read-back.
+ * r3g_hier_indices: the ascending int32 linear indices of the preceding select -> d_idx_out[count].
+ * r3g_hier_merge: d_fine_out[(2 n_coarse - 1)^3] (16-byte aligned) = d_values[rank] at the active points (d_values in the order
+ *   of r3g_hier_indices), the floor parent of d_coarse everywhere else.
+ * r3g_grid_query_points: the geo decoder at `count` listed points (linear indices into the (R+1)^3 lattice, any order, int32)
+ *   -> d_values[count].  Same launches as r3g_grid_query per pass: a point's logit equals the dense grid's bit for bit.  Never
+ *   reads, builds or re-keys the query-side cache of r3g_grid_query.  Needs a preceding r3g_vae_decode.
+ * r3g_grid_query_hier: the whole decode into d_grid [(R+1)^3] (16-byte aligned): level 0 densely, then select / indices / listed
+ *   points / merge per level.  Points evaluated at the finest level hold exactly the dense decoder's values; the others hold a
+ *   coarser level's value of their floor parent.  One read-back per level.  The levels below the finest and the listed points
+ *   stay away from the query-side cache (a hierarchical object between two dense ones leaves it as it was); a single-level
+ *   decode (odd R, or R / 2 < min_resolution) IS r3g_grid_query.  stats (optional, n_stats >= 4 + 2 * levels; one more
+ *   read-back): [0] levels, [1] points evaluated in total, [2] (R+1)^3, [3] unsafe cells -- cells of the result whose corners
+ *   are not all on one side of mc_level and not all active (their triangles rest on a filled value) --, then per level
+ *   [4 + 2l] R_l and [5 + 2l] points evaluated.
+ * Both grid entry points refuse the fp8 mode (option "geo_fp8" != 0) with R3G_ERR_INVALID: it is not covered by the bit-equality
+ * tests of the listed-points path. */
+int r3g_hier_select(r3g_ctx* ctx, const float* d_coarse, int n_coarse, double level, double band, int is_finest, int64_t* count,
+                    void* stream);
+int r3g_hier_indices(r3g_ctx* ctx, int32_t* d_idx_out, void* stream);
+int r3g_hier_merge(r3g_ctx* ctx, const float* d_coarse, const float* d_values, float* d_fine_out, void* stream);
+int r3g_grid_query_points(r3g_ctx* ctx, double bound, int octree_resolution, const int32_t* d_idx, int64_t count, float* d_values,
+                          void* stream);
+int r3g_grid_query_hier(r3g_ctx* ctx, double bound, int octree_resolution, double mc_level, double band, int min_resolution,
+                        float* d_grid, int64_t* stats, int n_stats, void* stream);
+
 /* ---- texture stage: UNet blocks (first slice) -------------------------------------------
  * The two diffusion models behind upstream's Hunyuan3DPaintPipeline.__call__ (reference call site
  * src/2d_to_3d_models/run.py:97; built at :126-128, :207-209) are diffusers UNet2DConditionModels on the Stable-Diffusion-2.1
@@ -448,6 +490,8 @@ int r3g_set_option(const char* name, int value);
 /* Process-wide event counters (round 6).  "dit_f16_fallbacks": launch groups of r3g_flow_sample_batch whose fp16 residual stream
  * produced non-finite latents and that therefore ran a second time on the fp32 stream ("dit_f16_guard"; such a group costs twice its
  * time -- bench.py and the stage report carry the count so that a slow run says why).  "dit_groups": launch groups run so far.
+ * "geo_q_cache_builds": allocations of the geo decoder's query-side cache so far (a change of (R, bound) frees and allocates it
+ * again; r3g_grid_query_points and the coarse levels of r3g_grid_query_hier never do).
  * r3g_flow_sample_batch is SYNCHRONOUS while the guard is on (one 4-byte read-back per group) and must not be captured into a
  * hipGraph then; with "dit_f16_guard" 0 or "dit_resid_f16" 0 it only enqueues work.  Unknown name: R3G_ERR_INVALID. */
 int r3g_get_counter(const char* name, int64_t* value);
