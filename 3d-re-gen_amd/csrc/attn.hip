@@ -30,6 +30,7 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(8))) float f32x8;
 
 constexpr int KV_TILE = 64;
 constexpr int TILE_B = KV_TILE * 64 * 2;  // 8 KiB: K tile [64 keys][64 d] or V^T tile [64 d][64 keys]
@@ -573,6 +574,24 @@ __device__ __forceinline__ float half_sum(float x) {
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
+// One LDS-DMA piece (16 bytes per lane, 1 KiB per wave) issued from inline asm, so that the compiler's wait-count pass does not know
+// of it.  Issued through __builtin_amdgcn_global_load_lds the pass has to assume that the transfer writes the LDS bytes the next
+// ds_read reads, and puts s_waitcnt vmcnt(0) in front of the first fragment read of every key tile: the prefetch of tile t + 1,
+// issued a few instructions earlier, was waited for BEFORE tile t's work instead of behind it (profiles/attention_interleave.md).
+// The kernels' own s_waitcnt vmcnt(0) + barrier at the end of a tile is what orders the transfer against its readers; a wait
+// the compiler computes for a load of its own can only wait for more than it counted (vmcnt retires in order), never less.
+// (address = the wave-uniform tile base in scalar registers + the lane's 32-bit byte offset: no 64-bit vector pointers to keep.)
+__device__ __forceinline__ void lds_dma16_unseen(const char* tile_base, uint32_t lane_off, uint32_t lds_addr) {
+    const uint32_t a = __builtin_amdgcn_readfirstlane(lds_addr);
+    uint32_t m0_saved;   // (m0 belongs to the compiler: handed back as found; the transfer takes its LDS base from m0 when it issues)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(m0_saved) : "v"(lane_off), "s"(tile_base), "s"(a) : "memory");
+}
+// LDS byte address of a __shared__ object
+__device__ __forceinline__ uint32_t lds_address(const void* q) {
+    return (uint32_t)(size_t)(const __attribute__((address_space(3))) void*)q;
+}
+
 constexpr float PSUM_LIMIT = 1024.f;   // (pipelined body) a block whose 16 p of one lane sum to more is re-stabilised
 // Round 6 variants of the generation-2 / generation-6 bodies (template VAR, option "attn_variant"; profiles/r06_attention.md):
 //  bit 0  after the first key block (whose exact maximum starts the stabiliser) the FAST pass takes no maximum at all: the 8 v_max3,
@@ -690,12 +709,18 @@ __global__ __launch_bounds__(NW * 64, (PIPE || NW == 8) ? 2 : 3) void attn2_kern
         koff[i] = (uint32_t)(row * 64 + kc * 8) * 2u;
         voff[i] = ((uint32_t)row * (uint32_t)p.Lk_pad + (uint32_t)(kc * 8)) * 2u;
     }
+    const uint32_t smem_lds = lds_address(smem);
     auto stage = [&](int t, char* dst) {
         if constexpr (GLDS) {
             const char* kt = reinterpret_cast<const char*>(Kg + (int64_t)t * (KV_TILE * 64));
             const char* vt = reinterpret_cast<const char*>(Vtg + (int64_t)t * KV_TILE);
 #pragma unroll
             for (int i = 0; i < PPW; ++i) {
+                if constexpr ((VAR & 4) != 0) {     // option "attn_async_stage": comment at lds_dma16_unseen
+                    lds_dma16_unseen(kt, koff[i], smem_lds + (uint32_t)(dst - smem) + (wid * PPW + i) * 1024);
+                    lds_dma16_unseen(vt, voff[i], smem_lds + (uint32_t)(dst - smem) + TILE_B + (wid * PPW + i) * 1024);
+                    continue;
+                }
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kt + (size_t)koff[i]),
                                                  (__attribute__((address_space(3))) void*)(dst + (wid * PPW + i) * 1024), 16, 0, 0);
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vt + (size_t)voff[i]),
@@ -849,6 +874,7 @@ __global__ __launch_bounds__(NW * 64, (PIPE || NW == 8) ? 2 : 3) void attn2_kern
 
     auto tile = [&](auto masked, auto first, const int t) {
         const char* cur = smem + (t & 1) * STAGE_B;
+        if constexpr ((VAR & 4) != 0) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), known to the compiler: comment in attn3_kernel
         if (!(ABL & 16) && t + 1 < ntiles) stage(t + 1, smem + ((t + 1) & 1) * STAGE_B);
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
@@ -996,6 +1022,36 @@ __global__ __launch_bounds__(NW * 64, (PIPE || NW == 8) ? 2 : 3) void attn2_kern
     }
 }
 
+// One eighth of the fast pass's softmax of a 32 x 32 score block (attn3_kernel's interleaved tiles): exponentials 2J and 2J + 1, and
+// for the PREVIOUS pair (whose exponentials are a gap old: no transcendental wait state) the bf16 packing and the step of
+// sum16's even / odd partial sums -- on two plain adds, which are the two halves of sum16's packed add bit for bit and cost an
+// MFMA gap less than it (profiles/attention_interleave.md).  The two empty asm statements are volatile, like the scheduling
+// barriers between the MFMA gaps: the step's inputs are not available before the first one and its results are complete at
+// the second, so the step stays in the gap it is written in (left alone the compiler gathers the exponentials of a block
+// behind its last score MFMA again).  st: {even sum, odd sum, the pair in flight}.
+struct SoftmaxRun { float ps0, ps1, ea, eb; };
+template <int J>
+__device__ __forceinline__ void softmax_step(f32x8& half, uint32_t (&pk)[8], SoftmaxRun& st) {
+    asm volatile("" : "+v"(half));   // (the half block: a pin on the two scores alone copies one of them out of the tuple)
+    const float a = __builtin_amdgcn_exp2f(half[2 * (J & 3)]);
+    const float b = __builtin_amdgcn_exp2f(half[2 * (J & 3) + 1]);
+    if (J == 1) { st.ps0 = st.ea; st.ps1 = st.eb; }
+    if (J > 1) { st.ps0 += st.ea; st.ps1 += st.eb; }
+    if (J > 0) {
+        pk[J - 1] = pack_bf16(st.ea, st.eb);
+        asm volatile("" : "+v"(pk[J - 1]));
+    }
+    st.ea = a;
+    st.eb = b;
+    if (J == 7) {
+        pk[7] = pack_bf16(a, b);
+        st.ps0 += a;
+        st.ps1 += b;
+        asm volatile("" : "+v"(pk[7]));
+    }
+    asm volatile("" : "+v"(st.ps0), "+v"(st.ps1), "+v"(st.ea), "+v"(st.eb));
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Third generation: 64 queries per wave.  The second-generation body with TWO 32-query blocks per wave that share every
 // K and V^T fragment read from LDS: a 32-key block costs a wave 8 ds_read_b128 for 16 MFMAs instead of 8 (at the matrix
@@ -1003,6 +1059,17 @@ __global__ __launch_bounds__(NW * 64, (PIPE || NW == 8) ? 2 : 3) void attn2_kern
 // L2 -> LDS stream per query, and the two blocks give every MFMA chain an independent neighbour.  Two workgroups of four
 // waves per CU (256 registers per lane).  Per 32-query block the arithmetic, the order of the key blocks and the
 // re-stabilise decisions (taken per aligned group of 32 queries) are those of attn2_kernel: the outputs are bit-identical.
+// VAR bit 1 (option "attn_interleave", profiles/attention_interleave.md): the unmasked tiles of the fast pass behind the first one
+// run with the softmax of one (query block, key block) pair INSIDE the gaps between the MFMAs of another pair -- an in-order
+// wave overlaps its two pipes only where the two kinds alternate in its own stream.  Per tile, MFMA groups of four || fillers:
+//     QK(0,0) || -          QK(1,0) || S(0,0) a     QK(0,1) || S(0,0) b     PV(0,0) || S(1,0) a
+//     QK(1,1) || S(1,0) b   PV(1,0) || S(0,1) a     [S(0,1) b]   PV(0,1) || S(1,1) a   [S(1,1) b]   PV(1,1)
+// ((query block, key block); a / b: the first / second eight exponentials with their packing and row-sum steps).  Every value
+// keeps its producer and every accumulator its order of additions: bit-identical to the clustered body.  The fragments of a
+// group are read from LDS during the group before it (K of key block 1 and V^T of key block 0 twice: 24 ds_read_b128 per tile
+// instead of 16, which keeps 32 registers free).
+// VAR bit 2 (option "attn_async_stage"; the same bit of attn2_kernel's VAR): the K / V^T tiles' LDS-DMA is issued unseen by the compiler,
+// comment at lds_dma16_unseen.
 template <int NW, int VAR = 0>
 __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_B];
@@ -1079,11 +1146,17 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
         koff[i] = (uint32_t)(row * 64 + kc * 8) * 2u;
         voff[i] = ((uint32_t)row * (uint32_t)p.Lk_pad + (uint32_t)(kc * 8)) * 2u;
     }
+    const uint32_t smem_lds = lds_address(smem);
     auto stage = [&](int t, char* dst) {
         const char* kt = reinterpret_cast<const char*>(Kg + (int64_t)t * (KV_TILE * 64));
         const char* vt = reinterpret_cast<const char*>(Vtg + (int64_t)t * KV_TILE);
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
+            if constexpr ((VAR & 4) != 0) {     // option "attn_async_stage": comment at lds_dma16_unseen
+                lds_dma16_unseen(kt, koff[i], smem_lds + (uint32_t)(dst - smem) + (wid * PPW + i) * 1024);
+                lds_dma16_unseen(vt, voff[i], smem_lds + (uint32_t)(dst - smem) + TILE_B + (wid * PPW + i) * 1024);
+                continue;
+            }
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kt + (size_t)koff[i]),
                                              (__attribute__((address_space(3))) void*)(dst + (wid * PPW + i) * 1024), 16, 0, 0);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vt + (size_t)voff[i]),
@@ -1107,7 +1180,81 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
 
     auto tile = [&](auto masked, auto first, const int t) {
         const char* cur = smem + (t & 1) * STAGE_B;
+        // (a wait the compiler KNOWS, where nothing of the loop is in flight: whatever it loaded ahead of the loop -- a spilled Q fragment --
+        // is then complete for it, and it puts no wait of its own behind the transfers it cannot see)
+        if constexpr ((VAR & 4) != 0) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
         if (t + 1 < ntiles) stage(t + 1, smem + ((t + 1) & 1) * STAGE_B);
+        if constexpr ((VAR & 2) != 0 && kFast && !decltype(masked)::value && !decltype(first)::value) {
+            auto ldk = [&](int kb, int ks) { return *reinterpret_cast<const bf16x8*>(cur + (off[kb] ^ (ks << 5))); };
+            auto ldv = [&](int kb, int i) {   // i: the group's MFMA, (ks2, db) = (i >> 1, i & 1)
+                return *reinterpret_cast<const bf16x8*>(cur + TILE_B + (off[i & 1] ^ ((2 * kb + (i >> 1)) << 5)));
+            };
+            auto pfrag = [&](const uint32_t (&pk)[8], int ks2) {
+                union { uint32_t u[4]; bf16x8 v; } pf;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pf.u[e] = pk[4 * ks2 + e];
+                return pf.v;
+            };
+            auto finish = [&](int qb, const SoftmaxRun& ps) {
+                const float psum = ps.ps0 + ps.ps1;
+                l_run[qb] += psum;
+                sticky |= __ballot(!(psum <= PSUM_LIMIT2)) & valid_lanes[qb];
+            };
+#define R3G_GAP() __builtin_amdgcn_sched_barrier(0)
+            f32x16 s00, s10, s01, s11;
+            uint32_t pk00[8], pk10[8], pk01[8], pk11[8];
+            SoftmaxRun ps;
+            f32x8 h;     // the half score block the softmax steps are working through
+            // fragments: fa K of key block 0 | fb, fd K of key block 1 | fc, fe V^T of key block 0 | ff V^T of key block 1; pieces 0, 1 of
+            // a group are read in gaps 2, 3 of the group before it and pieces 2, 3 in its own gaps 0, 1 (two MFMAs ahead of their use)
+            bf16x8 fa[4], fb[4], fc[4], fd[4], fe[4], ff[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) fa[i] = ldk(0, i);
+            // ---- QK(0,0)
+            s00 = mfma_32x32x16_fresh(fa[0], qf[0][0], negm[0]); R3G_GAP();
+            s00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], qf[0][1], s00, 0, 0, 0); R3G_GAP();
+            s00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], qf[0][2], s00, 0, 0, 0); R3G_GAP();
+            s00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[3], qf[0][3], s00, 0, 0, 0); R3G_GAP();
+            // ---- QK(1,0) || S(0,0) a
+            s10 = mfma_32x32x16_fresh(fa[0], qf[1][0], negm[1]); h = s00.lo; softmax_step<0>(h, pk00, ps); R3G_GAP();
+            s10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], qf[1][1], s10, 0, 0, 0); softmax_step<1>(h, pk00, ps); R3G_GAP();
+            s10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], qf[1][2], s10, 0, 0, 0); softmax_step<2>(h, pk00, ps); fb[0] = ldk(1, 0); R3G_GAP();
+            s10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[3], qf[1][3], s10, 0, 0, 0); softmax_step<3>(h, pk00, ps); fb[1] = ldk(1, 1); R3G_GAP();
+            // ---- QK(0,1) || S(0,0) b
+            s01 = mfma_32x32x16_fresh(fb[0], qf[0][0], negm[0]); h = s00.hi; softmax_step<4>(h, pk00, ps); fb[2] = ldk(1, 2); R3G_GAP();
+            s01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[1], qf[0][1], s01, 0, 0, 0); softmax_step<5>(h, pk00, ps); fb[3] = ldk(1, 3); R3G_GAP();
+            s01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[2], qf[0][2], s01, 0, 0, 0); softmax_step<6>(h, pk00, ps); fc[0] = ldv(0, 0); R3G_GAP();
+            s01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[3], qf[0][3], s01, 0, 0, 0); softmax_step<7>(h, pk00, ps); fc[1] = ldv(0, 1); finish(0, ps); R3G_GAP();
+            // ---- PV(0,0) || S(1,0) a
+            o[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc[0], pfrag(pk00, 0), o[0][0], 0, 0, 0); h = s10.lo; softmax_step<0>(h, pk10, ps); fc[2] = ldv(0, 2); R3G_GAP();
+            o[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc[1], pfrag(pk00, 0), o[0][1], 0, 0, 0); softmax_step<1>(h, pk10, ps); fc[3] = ldv(0, 3); R3G_GAP();
+            o[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc[2], pfrag(pk00, 1), o[0][0], 0, 0, 0); softmax_step<2>(h, pk10, ps); fd[0] = ldk(1, 0); R3G_GAP();
+            o[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc[3], pfrag(pk00, 1), o[0][1], 0, 0, 0); softmax_step<3>(h, pk10, ps); fd[1] = ldk(1, 1); R3G_GAP();
+            // ---- QK(1,1) || S(1,0) b
+            s11 = mfma_32x32x16_fresh(fd[0], qf[1][0], negm[1]); h = s10.hi; softmax_step<4>(h, pk10, ps); fd[2] = ldk(1, 2); R3G_GAP();
+            s11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fd[1], qf[1][1], s11, 0, 0, 0); softmax_step<5>(h, pk10, ps); fd[3] = ldk(1, 3); R3G_GAP();
+            s11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fd[2], qf[1][2], s11, 0, 0, 0); softmax_step<6>(h, pk10, ps); fe[0] = ldv(0, 0); R3G_GAP();
+            s11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fd[3], qf[1][3], s11, 0, 0, 0); softmax_step<7>(h, pk10, ps); fe[1] = ldv(0, 1); finish(1, ps); R3G_GAP();
+            // ---- PV(1,0) || S(0,1) a
+            o[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fe[0], pfrag(pk10, 0), o[1][0], 0, 0, 0); h = s01.lo; softmax_step<0>(h, pk01, ps); fe[2] = ldv(0, 2); R3G_GAP();
+            o[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fe[1], pfrag(pk10, 0), o[1][1], 0, 0, 0); softmax_step<1>(h, pk01, ps); fe[3] = ldv(0, 3); R3G_GAP();
+            o[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fe[2], pfrag(pk10, 1), o[1][0], 0, 0, 0); softmax_step<2>(h, pk01, ps); ff[0] = ldv(1, 0); R3G_GAP();
+            o[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fe[3], pfrag(pk10, 1), o[1][1], 0, 0, 0); softmax_step<3>(h, pk01, ps); ff[1] = ldv(1, 1); R3G_GAP();
+            // ---- S(0,1) b, then PV(0,1) || S(1,1) a
+            ff[2] = ldv(1, 2); ff[3] = ldv(1, 3);
+            h = s01.hi; softmax_step<4>(h, pk01, ps); softmax_step<5>(h, pk01, ps); softmax_step<6>(h, pk01, ps); softmax_step<7>(h, pk01, ps); finish(0, ps); R3G_GAP();
+            o[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[0], pfrag(pk01, 0), o[0][0], 0, 0, 0); h = s11.lo; softmax_step<0>(h, pk11, ps); R3G_GAP();
+            o[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[1], pfrag(pk01, 0), o[0][1], 0, 0, 0); softmax_step<1>(h, pk11, ps); R3G_GAP();
+            o[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[2], pfrag(pk01, 1), o[0][0], 0, 0, 0); softmax_step<2>(h, pk11, ps); R3G_GAP();
+            o[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[3], pfrag(pk01, 1), o[0][1], 0, 0, 0); softmax_step<3>(h, pk11, ps); R3G_GAP();
+            // ---- S(1,1) b, then PV(1,1)
+            h = s11.hi; softmax_step<4>(h, pk11, ps); softmax_step<5>(h, pk11, ps); softmax_step<6>(h, pk11, ps); softmax_step<7>(h, pk11, ps); finish(1, ps); R3G_GAP();
+            o[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[0], pfrag(pk11, 0), o[1][0], 0, 0, 0);
+            o[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[1], pfrag(pk11, 0), o[1][1], 0, 0, 0);
+            o[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[2], pfrag(pk11, 1), o[1][0], 0, 0, 0);
+            o[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[3], pfrag(pk11, 1), o[1][1], 0, 0, 0);
+#undef R3G_GAP
+        } else {
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             constexpr bool kFirst = decltype(first)::value;
@@ -1193,6 +1340,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
                 }
             }
         }
+        }   // clustered body
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     };
@@ -1520,6 +1668,10 @@ void attn_set_pipelined(bool on) { g_attn_pipelined = on; }
 static int g_attn_gen = 7;
 static int g_attn_variant = 1;     // option "attn_variant" (round 6): 1 = fast pass without a maximum + sticky sum test (default) | 0 = rounds 2-5 (generations 2 / 6 / 7)
 void attn_set_variant(int v) { if (v >= 0 && v <= 1) g_attn_variant = v; }
+static int g_attn_interleave = 0;  // option "attn_interleave" (opt-in: measured 2-3 % slower, profiles/attention_interleave.md): the 64-query kernel's fast pass with the softmax inside its MFMA gaps (attn3_kernel VAR bit 1); 0 = clustered
+void attn_set_interleave(int v) { g_attn_interleave = v != 0; }
+static int g_attn_async_stage = 1; // option "attn_async_stage": the variant-1 kernels issue their LDS-DMA unseen by the compiler's wait counts (VAR bit 2); 0 = through the builtin
+void attn_set_async_stage(int v) { g_attn_async_stage = v != 0; }
 // generation 7 takes the 64-query-per-wave kernel where its 256-query workgroups make at least four full rounds of the
 // 512 slots (the geo decoder's 131072-query passes: +6 %); on the DiT's 4442-query attention the coarser grid costs more
 // than the kernel gains (576 workgroups on 512 slots), profiles/r02_attention.md
@@ -1615,10 +1767,18 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
         else if (gen == 4) hipLaunchKernelGGL((attn2_kernel<true, true, 8>), dim3(items), dim3(512), 0, s, p);
         else if (gen == 5) hipLaunchKernelGGL((attn2_kernel<true, false, 8>), dim3(items), dim3(512), 0, s, p);
         else if (gen == 6) {
-            if (g_attn_variant == 1) hipLaunchKernelGGL((attn3_kernel<4, 1>), dim3(items), dim3(256), 0, s, p);
+            if (g_attn_variant == 1) {
+                switch ((g_attn_interleave ? 2 : 0) | (g_attn_async_stage ? 4 : 0)) {
+                    case 6: hipLaunchKernelGGL((attn3_kernel<4, 7>), dim3(items), dim3(256), 0, s, p); break;
+                    case 4: hipLaunchKernelGGL((attn3_kernel<4, 5>), dim3(items), dim3(256), 0, s, p); break;
+                    case 2: hipLaunchKernelGGL((attn3_kernel<4, 3>), dim3(items), dim3(256), 0, s, p); break;
+                    default: hipLaunchKernelGGL((attn3_kernel<4, 1>), dim3(items), dim3(256), 0, s, p); break;
+                }
+            }
             else hipLaunchKernelGGL((attn3_kernel<4, 0>), dim3(items), dim3(256), 0, s, p);
         } else {
-            if (g_attn_variant == 1) hipLaunchKernelGGL((attn2_kernel<true, false, 4, 0, 1>), dim3(items), dim3(256), 0, s, p);
+            if (g_attn_variant == 1 && g_attn_async_stage) hipLaunchKernelGGL((attn2_kernel<true, false, 4, 0, 5>), dim3(items), dim3(256), 0, s, p);
+            else if (g_attn_variant == 1) hipLaunchKernelGGL((attn2_kernel<true, false, 4, 0, 1>), dim3(items), dim3(256), 0, s, p);
             else hipLaunchKernelGGL((attn2_kernel<true, false, 4>), dim3(items), dim3(256), 0, s, p);
         }
         return hipGetLastError();

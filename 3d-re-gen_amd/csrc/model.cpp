@@ -1505,6 +1505,8 @@ int r3g_set_option(const char* name, int value) {
     else if (!strcmp(name, "geo_lnd_fused")) g_geo_lnd_fused = value != 0;
     else if (!strcmp(name, "geo_ln3_fold")) g_geo_ln3_fold = value != 0;
     else if (!strcmp(name, "attn_variant")) attn_set_variant(value);
+    else if (!strcmp(name, "attn_interleave")) attn_set_interleave(value);
+    else if (!strcmp(name, "attn_async_stage")) attn_set_async_stage(value);
     else if (!strcmp(name, "gemm_epi_slices")) gemm_set_epi_slices(value != 0);
     else if (!strcmp(name, "gemm_mixed")) gemm_set_mixed(value != 0);
     else if (!strcmp(name, "gemm_persistent_qkv")) gemm_set_persistent_qkv(value != 0);

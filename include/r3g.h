@@ -469,6 +469,12 @@ int r3g_prof_read_bytes(double* bytes, int n);
  * the sum of a lane's 16 exponentials against 2^16 into a sticky flag; a workgroup whose valid queries set it runs its query tile
  * again with variant 0's body | 0 = rounds 2-5.  Bit-identical to variant 0 unless variant 0 would have moved its stabiliser where
  * the fast pass does not: then equal within the bf16 rounding of P),
+ * "attn_interleave" (0 default | 1, opt-in: where "attn_variant" 1 runs the 64-query-per-wave kernel, the unmasked key tiles of its fast
+ * pass issue the softmax of one score block between the MFMAs of another instead of behind them; bit-identical either way and
+ * measured 2-3 % slower in this form, profiles/attention_interleave.md),
+ * "attn_async_stage" (1 default | 0: the "attn_variant" 1 kernels issue the LDS-DMA of the next K / V^T tile through the compiler's
+ * builtin, which makes it wait for the transfer in front of the current tile's first fragment read instead of at the tile's end;
+ * bit-identical either way, profiles/attention_interleave.md),
  * "geo_ln3_fold" (1 default, round 6 | 0: the geo decoder's ln_3 as its own launch writing a normalised bf16 copy of the stream, rounds
  * 1-5; folded, c_proj's epilogue also writes the rows' chunk statistics, and c_fc runs on the raw stream with W' = bf16(W gamma) and
  * rstd (acc - mean c1) + c2 in front of its GELU -- the same function without the bf16 rounding of the normalised operand: logits move

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "3d-re-gen_amd"))
 import torch  # noqa: E402
 from r3g import ffi  # noqa: E402
 
+EXTRA_DEFAULTS = {b"attn_interleave": 0, b"attn_async_stage": 1}
 SHAPES = [(2, 16, 4442, 4442, 0), (1, 16, 131072, 3072, 1), (1, 16, 3072, 3072, 0), (1, 24, 1370, 1370, 0)]
 
 
@@ -32,7 +33,16 @@ def main():
     ap.add_argument("--zero", action="store_true", help="zero-filled operands (clock / power sensitivity)")
     a = ap.parse_args()
     # --gens entries: "G" or "GvV" = attn_generation G with attn_variant V (round 6), e.g. 2v0,2v1,2v3,6v0,6v1
+    # ... and "G[vV]:name=value[:name=value]" sets further options for that entry (restored to the library's defaults of
+    # EXTRA_DEFAULTS before every other entry), e.g. 6v1:attn_interleave=0:attn_async_stage=0,6v1
+    extra = {}
+
     def parse(m):
+        if ":" in m:
+            m, *opts = m.split(":")
+            code = parse(m)
+            extra[code + 100000 * (len(extra) + 1)] = [(o.split("=")[0].encode(), int(o.split("=")[1])) for o in opts]
+            return code + 100000 * len(extra)
         if "v" in m:
             g_, v_ = m.split("v")
             return int(g_) * 10 + int(v_) + 1000
@@ -55,6 +65,11 @@ def main():
             ffi.check(L.r3g_set_option(b"attn_generation", a.gen))
 
         def run(mask):
+            for name, val in EXTRA_DEFAULTS.items():
+                ffi.check(L.r3g_set_option(name, val))
+            for name, val in extra.get(mask, []):
+                ffi.check(L.r3g_set_option(name, val))
+            mask %= 100000
             if a.gens:
                 if mask >= 1000:
                     ffi.check(L.r3g_set_option(b"attn_generation", (mask - 1000) // 10))
@@ -96,6 +111,8 @@ def main():
     ffi.check(L.r3g_set_option(b"attn_ablate", 0))
     ffi.check(L.r3g_set_option(b"attn_generation", 7))
     ffi.check(L.r3g_set_option(b"attn_variant", 1))
+    for name, val in EXTRA_DEFAULTS.items():
+        ffi.check(L.r3g_set_option(name, val))
 
 
 if __name__ == "__main__":
