@@ -414,6 +414,31 @@ __global__ void cfg_euler_kernel(float* lat, const float* v2, int64_t n, float g
     lat[i] = lat[i] + ds * (vu + g * (vc - vu));
 }
 
+// the Euler update of a guidance-distilled model (no CFG combine), over all objects of a launch group: lat += ds * v
+__global__ __launch_bounds__(256) void euler_step_kernel(float* __restrict__ lat, const float* __restrict__ v, int64_t n, float ds) {
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i + 4 <= n) {
+        float4 x = *reinterpret_cast<const float4*>(lat + i);
+        const float4 w = *reinterpret_cast<const float4*>(v + i);
+        x.x = x.x + ds * w.x; x.y = x.y + ds * w.y; x.z = x.z + ds * w.z; x.w = x.w + ds * w.w;
+        *reinterpret_cast<float4*>(lat + i) = x;
+    } else {
+        for (int64_t j = i; j < n; ++j) lat[j] = lat[j] + ds * v[j];
+    }
+}
+
+// the same update one element per lane, for arrays that are not 16-byte aligned
+__global__ __launch_bounds__(256) void euler_step_scalar_kernel(float* __restrict__ lat, const float* __restrict__ v, int64_t n, float ds) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) lat[i] = lat[i] + ds * v[i];
+}
+
+// y[i] += x[i] (vec = time_in(emb(t)) + guidance_in(emb(g)) of a guidance-distilled DiT)
+__global__ __launch_bounds__(256) void vec_add_kernel(float* __restrict__ y, const float* __restrict__ x, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = y[i] + x[i];
+}
+
 // *flag |= 1 when x holds a NaN or an infinity (one atomic per wave that saw one)
 __global__ void nonfinite_flag_kernel(const float* __restrict__ x, int64_t n, int* flag) {
     bool bad = false;
@@ -742,6 +767,25 @@ hipError_t fill_rows_launch(float* dst, int64_t ld, int rows, int C, const float
 hipError_t cfg_euler_launch(float* latents, const float* v2, int64_t n, float guidance, float dsigma, hipStream_t s) {
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(cfg_euler_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, latents, v2, n, guidance, dsigma);
+    return hipGetLastError();
+}
+
+hipError_t euler_step_launch(float* latents, const float* v, int64_t n, float dsigma, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
+    // float4 accesses where both arrays are 16-byte aligned (whole objects' latents from an allocator are); otherwise per element --
+    // the same fp32 operation per element either way
+    if (((uintptr_t)latents | (uintptr_t)v) & 15)
+        hipLaunchKernelGGL(euler_step_scalar_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, latents, v, n, dsigma);
+    else
+        hipLaunchKernelGGL(euler_step_kernel, dim3(blocks_for((n + 3) / 4, 256)), dim3(256), 0, s, latents, v, n, dsigma);
+    return hipGetLastError();
+}
+
+hipError_t vec_add_launch(float* y, const float* x, int n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
+    hipLaunchKernelGGL(vec_add_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, y, x, n);
     return hipGetLastError();
 }
 

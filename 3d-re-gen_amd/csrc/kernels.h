@@ -235,6 +235,9 @@ hipError_t cast_pad_launch(const float* in, int64_t ldi, uint16_t* out, int64_t 
 hipError_t fill_rows_launch(float* dst, int64_t ld, int rows, int C, const float* row_values, hipStream_t s);
 // latents += dsigma * (v_u + g (v_c - v_u));  v = [2][n] (cond first)
 hipError_t cfg_euler_launch(float* latents, const float* v2, int64_t n, float guidance, float dsigma, hipStream_t s);
+// guidance-distilled sampling (no CFG batch): latents += dsigma * v over all n elements of a launch group (float4 accesses when both are 16-byte aligned)
+hipError_t euler_step_launch(float* latents, const float* v, int64_t n, float dsigma, hipStream_t s);
+hipError_t vec_add_launch(float* y, const float* x, int n, hipStream_t s);   // y[i] += x[i]
 hipError_t nonfinite_flag_launch(const float* x, int64_t n, int* flag, hipStream_t s);   // *flag |= 1 when x holds a NaN / infinity
 // swiglu: out(bf16)[r][c] = silu(in[r][c]) * in[r][F + c]
 hipError_t swiglu_launch(const uint16_t* in, int64_t ldi, uint16_t* out, int64_t ldo, int rows, int F, hipStream_t s);

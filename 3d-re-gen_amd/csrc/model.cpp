@@ -65,6 +65,7 @@ static bool g_geo_ln3_fold = true;    // option "geo_ln3_fold" (round 6): the ge
 static bool g_geo_lnd_fused = true;   // option "geo_lnd_fused" (round 6): ln_post + output_proj folded into the geo decoder's last residual GEMM
 static int64_t g_geo_q_cache_builds = 0;   // allocations of Model::GeoCache so far (r3g_get_counter "geo_q_cache_builds")
 static int64_t g_dit_groups = 0;         // launch groups r3g_flow_sample_batch has run (r3g_get_counter)
+static int64_t g_dit_evals = 0;          // DiT evaluations issued, one per launch group and step (r3g_get_counter "dit_evals")
 static int g_dit_f16_fallbacks = 0;    // how often that happened (r3g_set_option("dit_f16_fallbacks_reset", ...) / stderr line)
 static bool g_dit_resid_f16 = true;   // the DiT's residual stream of the de-duplicated CFG path in fp16 (the reference's activation type) instead of fp32
 static bool g_skip_zero_step = true;   // skip the DiT evaluation of a step whose d_sigma is 0 (upstream's last step)
@@ -92,6 +93,8 @@ struct Model {
     uint16_t* inb = nullptr;    // bf16 copy of small inputs (latents, Fourier features, patches)
     float* small = nullptr;     // temb[B][256] | th[B][H] | vec[B][H] | mods[B][12H] | v2[2][N][Cin] ...
     float *temb = nullptr, *th = nullptr, *vec = nullptr, *mods = nullptr, *v2 = nullptr;
+    // guidance-distilled checkpoints: timestep_embedding(g) [256] | guidance_in's hidden [H] | guidance_in(emb(g)) [H], per call
+    float *gemb = nullptr, *gth = nullptr, *gvec = nullptr;
     // persistent results
     float* z = nullptr;         // VAE-decoded latents f32 [Nlat][W]
     uint16_t *geoK = nullptr, *geoVt = nullptr;
@@ -101,7 +104,7 @@ struct Model {
     int n_mod_jobs = 0;
     float* mod_all = nullptr;           // [job][B][N]
     std::vector<int64_t> mod_off;       // per job offset into mod_all
-    // second stream: the MLP half of a single block's linear1 runs beside the attention kernel (see dit_forward_cfg_dedup)
+    // second stream: the MLP half of a single block's linear1 runs beside the attention kernel (see dit_forward_grouped)
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // fp8 mode of the geo decoder (option geo_fp8): e4m3 copies of its weights with one scale per output row, made on
@@ -112,10 +115,11 @@ struct Model {
     uint16_t* lnf_w = nullptr;                       // ln_3 fold: bf16(c_fc.weight * ln_3.weight) [N][W]
     float *lnf_c = nullptr, *lnf_stats = nullptr;    //   c1 | c2 [2 N], (mean, rstd) per row of a pass [qc][2]
     float *lnd_gw = nullptr, *lnd_part = nullptr;   // EPI_RESID_BF16_LND: gamma * w [W] + 2 constants, chunk statistics [qc][W / 64][4]
-    // activation arena of the CFG-de-duplicated DiT for `cap` objects per launch (allocated on first use), and the segment
-    // tables of its fused QKV epilogues for `nb` objects
+    // activation arena of the grouped DiT engine for `cap_obj` objects and `cap_lat` latent blocks (= attention entries) per
+    // launch (allocated on first use), and the segment tables of its fused QKV epilogues for `nb` objects of `epo` entries each
+    // (2: classifier-free guidance with the de-duplicated unconditional entry | 1: a guidance-distilled model, no CFG batch)
     struct DitBatch {
-        int cap = 0, nb = 0;
+        int cap_obj = 0, cap_lat = 0, nb = 0, epo = 0;
         char* base = nullptr;
         float *f32a = nullptr, *v2 = nullptr, *lat0 = nullptr;   // lat0: the group's initial latents (fp16-stream overflow guard)
         int* bad = nullptr;                                        // device flag of that guard
@@ -432,7 +436,8 @@ static int dit_forward(Model& m, const float* x_in, const float* t_dev, float t_
     return R3G_OK;
 }
 
-// ---- DiT under classifier-free guidance with a de-duplicated unconditional context, for NB objects at once -------------
+// ---- the grouped DiT engine: NB objects at once, under classifier-free guidance with a de-duplicated unconditional context
+// ---- (2 entries per object, described first) or, for a guidance-distilled model, without the CFG batch (1 entry per object) ----
 // The unconditional context is `zeros_like(cond)` (upstream conditioner.unconditional_embedding): after cond_in its
 // Lc tokens are identical, and every layer keeps them identical (same input, same per-token ops, same attention
 // row).  They are therefore carried as ONE token whose key counts Lc times in the softmax (score + log2(Lc) in the
@@ -441,30 +446,56 @@ static int dit_forward(Model& m, const float* x_in, const float* t_dev, float t_
 // launch (upstream: the pipeline's batch dimension when `image` is a list; the reference's object-level parallelism is the
 // pool at src/2d_to_3d_models/run.py:176-193).  A GEMM row does not know which object it belongs to: per-object results are
 // bit-identical to NB = 1.  Global row layout of all row-indexed buffers (CFG entry e = 2*object + {0 cond, 1 uncond}):
-//   [e*Nl, (e+1)*Nl)  latent rows of entry e          (2*NB blocks; the img stream of the double blocks)
+//   [e*Nl, (e+1)*Nl)  latent rows of entry e          (2*NB blocks, E*NB in general; the img stream of the double blocks)
 //   TX0 = 2*NB*Nl;  [TX0 + o*Ltp, +Lc) cond tokens of object o | row TX0 + o*Ltp + Lc: its unconditional token | pad to Ltp
 // (Ltp = dit_txt_rows(): Lc + 1 rounded up to whole 16-token groups of V^T, at least 128).  The txt-stream GEMMs see NB*Ltp contiguous rows, the
 // single blocks all Rall = TX0 + NB*Ltp rows.
 static constexpr int kMaxObjects = kAttnMaxEntries / 2;
+// Guidance-distilled checkpoints (model.guidance_in.*: the guidance scale is an embedded input, upstream's "fast" / "turbo"
+// subfolders) run WITHOUT the CFG batch: one entry per object, no unconditional token.  The same engine carries them with
+// E = 1 entries per object instead of 2 -- E*NB latent blocks, TX0 = E*NB*Nl, per object Lc cond tokens padded to Ltp, E*NB
+// ragged attention entries of lq = lk = T without a weighted key -- and a launch group then takes kAttnMaxEntries objects.
+static constexpr int kMaxObjectsDistilled = kAttnMaxEntries;
 // rows per object in the txt block: Lc cond tokens + 1 unconditional token, padded so that 16-token groups of V^T stay whole
 // and (>= 128) no 128-row window of a GEMM meets more than three row segments (QkvEpi::seg_tab)
 static int dit_txt_rows(const Model& m) { return (int)std::max<int64_t>(128, rup(m.Lc + 1, 16)); }
 
-static int ensure_dit_batch(Model& m, int NB) {
+static const char* const kGuidanceKeys[4] = {"model.guidance_in.in_layer.weight", "model.guidance_in.in_layer.bias",
+                                             "model.guidance_in.out_layer.weight", "model.guidance_in.out_layer.bias"};
+// A model is guidance-distilled if and only if the four model.guidance_in.* tensors are registered; a partial set is an error
+// that names the first missing key.
+static int model_distilled(const Model& m, bool* distilled) {
+    int have = 0;
+    const char* missing = nullptr;
+    for (const char* k : kGuidanceKeys) {
+        if (m.find(k)) ++have;
+        else if (!missing) missing = k;
+    }
+    *distilled = have == 4;
+    if (have != 0 && have != 4)
+        return fail(R3G_ERR_STATE, "guidance-distilled checkpoint is incomplete: missing '%s' (all four model.guidance_in.* tensors or none)",
+                    missing);
+    return R3G_OK;
+}
+
+// E = entries per object: 2 (CFG: conditional + de-duplicated unconditional) or 1 (guidance-distilled)
+static int ensure_dit_batch(Model& m, int NB, int E) {
     Model::DitBatch& d = m.db;
     const r3g_model_config& c = m.c;
     const int H = m.H, Nl = c.vae_num_latents, Lc = m.Lc;
     const int Ltp = dit_txt_rows(m);
-    if (d.cap < NB) {
-        if (d.base) { R3G_TRY(hipDeviceSynchronize()); (void)hipFree(d.base); d.base = nullptr; d.cap = 0; }
-        const int64_t rows = rup(2LL * NB * Nl + (int64_t)NB * Ltp, 256);
-        const int64_t n_attn = 2LL * NB * m.Hd * m.Tpad * 64;
+    if (d.cap_obj < NB || d.cap_lat < E * NB) {
+        if (d.base) { R3G_TRY(hipDeviceSynchronize()); (void)hipFree(d.base); d.base = nullptr; }
+        const int co = std::max(d.cap_obj, NB), cl = std::max(d.cap_lat, E * NB);
+        d.cap_obj = d.cap_lat = 0;
+        const int64_t rows = rup((int64_t)cl * Nl + (int64_t)co * Ltp, 256);
+        const int64_t n_attn = (int64_t)cl * m.Hd * m.Tpad * 64;
         size_t off = 0;
         auto carve = [&](int64_t bytes) { size_t o = off; off += (size_t)rup(bytes, 256); return o; };
         const size_t o_f = carve(rows * H * 4), o_xn = carve(rows * H * 2), o_q = carve(n_attn * 2), o_k = carve(n_attn * 2),
-                     o_v = carve(n_attn * 2), o_cat = carve(rows * 5 * H * 2), o_inb = carve((int64_t)NB * Nl * m.cin_pad * 2),
-                     o_ctx = carve((int64_t)NB * Ltp * c.dit_context_dim * 2), o_v2 = carve(2LL * NB * Nl * c.dit_in_channels * 4),
-                     o_seg = carve(2 * 64 * 16), o_lat0 = carve((int64_t)NB * Nl * c.dit_in_channels * 4), o_bad = carve(256);
+                     o_v = carve(n_attn * 2), o_cat = carve(rows * 5 * H * 2), o_inb = carve((int64_t)co * Nl * m.cin_pad * 2),
+                     o_ctx = carve((int64_t)co * Ltp * c.dit_context_dim * 2), o_v2 = carve((int64_t)cl * Nl * c.dit_in_channels * 4),
+                     o_seg = carve(2 * 64 * 16), o_lat0 = carve((int64_t)co * Nl * c.dit_in_channels * 4), o_bad = carve(256);
         R3G_TRY(hipMalloc((void**)&d.base, off));
         R3G_TRY(hipMemset(d.base, 0, off));   // padded rows / columns must start finite
         char* a = d.base;
@@ -472,38 +503,47 @@ static int ensure_dit_batch(Model& m, int NB) {
         d.Vt = (uint16_t*)(a + o_v); d.cat = (uint16_t*)(a + o_cat); d.inb = (uint16_t*)(a + o_inb);
         d.ctx = (uint16_t*)(a + o_ctx); d.v2 = (float*)(a + o_v2); d.seg_txt = (int*)(a + o_seg); d.seg_all = d.seg_txt + 64 * 4;
         d.lat0 = (float*)(a + o_lat0); d.bad = (int*)(a + o_bad);
-        d.cap = NB;
-        d.nb = 0;
+        d.cap_obj = co; d.cap_lat = cl;
+        d.nb = 0; d.epo = 0;
     }
-    if (d.nb != NB) {
+    if (d.nb != NB || d.epo != E) {
         // segment tables of the EPI_QKV epilogue: {first row, end row, attention batch slot, destination row}
-        const int TX0 = 2 * NB * Nl;
+        const int TX0 = E * NB * Nl;
         d.h_seg_txt.clear(); d.h_seg_all.clear();
-        for (int e = 0; e < 2 * NB; ++e) { const int v[4] = {e * Nl, (e + 1) * Nl, e, 0}; d.h_seg_all.insert(d.h_seg_all.end(), v, v + 4); }
+        for (int e = 0; e < E * NB; ++e) { const int v[4] = {e * Nl, (e + 1) * Nl, e, 0}; d.h_seg_all.insert(d.h_seg_all.end(), v, v + 4); }
         for (int o = 0; o < NB; ++o) {
-            const int c0[4] = {o * Ltp, o * Ltp + Lc, 2 * o, Nl}, u0[4] = {o * Ltp + Lc, o * Ltp + Lc + 1, 2 * o + 1, Nl};
-            d.h_seg_txt.insert(d.h_seg_txt.end(), c0, c0 + 4); d.h_seg_txt.insert(d.h_seg_txt.end(), u0, u0 + 4);
-            const int c1[4] = {TX0 + c0[0], TX0 + c0[1], c0[2], c0[3]}, u1[4] = {TX0 + u0[0], TX0 + u0[1], u0[2], u0[3]};
-            d.h_seg_all.insert(d.h_seg_all.end(), c1, c1 + 4); d.h_seg_all.insert(d.h_seg_all.end(), u1, u1 + 4);
+            const int c0[4] = {o * Ltp, o * Ltp + Lc, E * o, Nl};
+            const int c1[4] = {TX0 + c0[0], TX0 + c0[1], c0[2], c0[3]};
+            d.h_seg_txt.insert(d.h_seg_txt.end(), c0, c0 + 4);
+            d.h_seg_all.insert(d.h_seg_all.end(), c1, c1 + 4);
+            if (E == 2) {   // CFG: the object's single unconditional token, attention slot 2o + 1
+                const int u0[4] = {o * Ltp + Lc, o * Ltp + Lc + 1, 2 * o + 1, Nl};
+                const int u1[4] = {TX0 + u0[0], TX0 + u0[1], u0[2], u0[3]};
+                d.h_seg_txt.insert(d.h_seg_txt.end(), u0, u0 + 4);
+                d.h_seg_all.insert(d.h_seg_all.end(), u1, u1 + 4);
+            }
         }
         R3G_TRY(hipDeviceSynchronize());   // a previous launch may still read the tables
         R3G_TRY(hipMemcpy(d.seg_txt, d.h_seg_txt.data(), d.h_seg_txt.size() * 4, hipMemcpyHostToDevice));
         R3G_TRY(hipMemcpy(d.seg_all, d.h_seg_all.data(), d.h_seg_all.size() * 4, hipMemcpyHostToDevice));
-        d.nb = NB;
+        d.nb = NB; d.epo = E;
     }
     return R3G_OK;
 }
 
-// x_lat f32 [NB][Nl][Cin]; the context rows (m.db.ctx) are filled by the caller; out2 f32 [2*NB][Nl][Cin] (entry order)
-static int dit_forward_cfg_dedup(Model& m, const float* x_lat, float t_scalar, float* out2, int NB, hipStream_t s,
-                                 bool allow_f16 = true) {
+// x_lat f32 [NB][Nl][Cin]; the context rows (m.db.ctx) are filled by the caller; out2 f32 [E*NB][Nl][Cin] (entry order).
+// E = m.db.epo entries per object.  gvec (E == 1 only): guidance_in(timestep_embedding(g)) [H], added to vec.
+static int dit_forward_grouped(Model& m, const float* x_lat, float t_scalar, float* out2, int NB, hipStream_t s,
+                                 bool allow_f16 = true, const float* gvec = nullptr) {
     const r3g_model_config& c = m.c;
     Model::DitBatch& d = m.db;
+    const int E = d.epo;
     const int H = m.H, Nl = c.vae_num_latents, Lc = m.Lc, T = m.T, Tpad = m.Tpad, heads = m.Hd;
-    const int Ltp = dit_txt_rows(m), TX0 = 2 * NB * Nl, Mtxt = NB * Ltp, Rall = TX0 + Mtxt;
+    const int Ltp = dit_txt_rows(m), TX0 = E * NB * Nl, Mtxt = NB * Ltp, Rall = TX0 + Mtxt;
     const int64_t catld = 5 * (int64_t)H;
     const int mh = c.dit_mlp_hidden;
-    if (d.nb != NB) return fail(R3G_ERR_STATE, "dit batch arena not prepared for %d objects", NB);
+    if (d.nb != NB || (E != 1 && E != 2)) return fail(R3G_ERR_STATE, "dit batch arena not prepared for %d objects", NB);
+    ++g_dit_evals;
     // The residual stream: fp32, or (option "dit_resid_f16") fp16 -- the reference's own activation type (its pipelines run in
     // fp16) -- in the same buffer: the read-modify-write epilogues of the N = 1024 projections and the LayerNorm reads move
     // half the bytes.  `xrow(r)` = the stream from row r on, in either format.
@@ -519,8 +559,8 @@ static int dit_forward_cfg_dedup(Model& m, const float* x_lat, float t_scalar, f
     // (fp16 stream: the stream starts as zeros and the two input projections ADD to it -- 0 + (acc + bias), rounded once)
     if (xh) R3G_TRY(hipMemsetAsync(d.f32a, 0, (size_t)Rall * H * 2, s));
     const int epi_in = xh ? EPI_RESID_F16 : EPI_F32;
-    for (int j = 0; j < 2; ++j)
-        R3G_RC(gemm(d.inb, m.cin_pad, (int64_t)Nl * m.cin_pad, l, 0, H, xrow((int64_t)j * Nl), H, 2LL * Nl * H, Nl, m.cin_pad,
+    for (int j = 0; j < E; ++j)
+        R3G_RC(gemm(d.inb, m.cin_pad, (int64_t)Nl * m.cin_pad, l, 0, H, xrow((int64_t)j * Nl), H, (int64_t)E * Nl * H, Nl, m.cin_pad,
                     epi_in, nullptr, 0, NB, s));
     R3G_RC(get_lin(m, "model.cond_in", true, &l));
     R3G_RC(gemm(d.ctx, c.dit_context_dim, 0, l, 0, H, xrow(TX0), H, 0, Mtxt, c.dit_context_dim, epi_in, nullptr, 0, 1, s));
@@ -529,18 +569,20 @@ static int dit_forward_cfg_dedup(Model& m, const float* x_lat, float t_scalar, f
     R3G_TRY(gemv_launch(m.temb, 1, 256, l.w, l.ldw, l.b, m.th, H, 0, 1, s));
     R3G_RC(get_lin(m, "model.time_in.out_layer", true, &l));
     R3G_TRY(gemv_launch(m.th, 1, H, l.w, l.ldw, l.b, m.vec, H, 0, 0, s));
+    if (gvec) R3G_TRY(vec_add_launch(m.vec, gvec, H, s));   // vec = time_in(emb(t)) + guidance_in(emb(g))
     R3G_RC(build_mod_jobs(m));
     R3G_TRY(gemv_multi_launch(m.vec, 1, H, m.mod_jobs, m.n_mod_jobs, m.mod_all, 1, s));
 
     AttnArgs at{};
     at.Q = d.Q; at.K = d.K; at.Vt = d.Vt; at.O = d.cat; at.ldo = catld; at.strideO = 0;
-    at.B = 2 * NB; at.H = heads; at.Lq = T; at.Lq_pad = Tpad; at.Lk = T; at.Lk_pad = Tpad; at.scale = 0.125f;
+    at.B = E * NB; at.H = heads; at.Lq = T; at.Lq_pad = Tpad; at.Lk = T; at.Lk_pad = Tpad; at.scale = 0.125f;
     at.q_prescaled = attn_q_scale(0.125f) != 1.0f;
     at.ragged = 1;
     for (int o = 0; o < NB; ++o) {   // work order: the long (conditional) entries first
         AttnEntry& ec = at.ent[o];
-        ec.lq = T; ec.lk = T; ec.buf = 2 * o; ec.o_row0 = (int64_t)(2 * o) * Nl; ec.o_split = Nl;
+        ec.lq = T; ec.lk = T; ec.buf = E * o; ec.o_row0 = (int64_t)(E * o) * Nl; ec.o_split = Nl;
         ec.o_row_split = (int64_t)TX0 + (int64_t)o * Ltp; ec.bias_key = -1; ec.bias_log2 = 0.f;
+        if (E == 1) continue;
         AttnEntry& eu = at.ent[NB + o];
         eu.lq = Nl + 1; eu.lk = Nl + 1; eu.buf = 2 * o + 1; eu.o_row0 = (int64_t)(2 * o + 1) * Nl; eu.o_split = Nl;
         eu.o_row_split = (int64_t)TX0 + (int64_t)o * Ltp + Lc; eu.bias_key = Nl; eu.bias_log2 = log2f((float)Lc);
@@ -601,15 +643,15 @@ static int dit_forward_cfg_dedup(Model& m, const float* x_lat, float t_scalar, f
         const float* mt = m.mod_all + m.mod_off[2 * i + 1];
         QkvSplitArgs qi, qt;
         Lin li, lt;
-        // img stream: the 2*NB latent blocks (one GEMM batch entry = one attention batch slot); txt stream: per object Lc
-        // cond tokens (slot 2o) + 1 unconditional token (slot 2o+1).  Each layer of the two streams is one grouped launch.
+        // img stream: the E*NB latent blocks (one GEMM batch entry = one attention batch slot); txt stream: per object Lc
+        // cond tokens (slot E*o) and, under CFG (E == 2), 1 unconditional token (slot 2o+1).  Each layer of the two streams is one grouped launch.
         R3G_RC(ln_streams(mi + H, mi, mt + H, mt));
         R3G_RC(get_lin(m, bi + "_attn.qkv", c.dit_qkv_bias != 0, &li));
         R3G_RC(get_lin(m, bt + "_attn.qkv", c.dit_qkv_bias != 0, &lt));
         R3G_RC(qkv_args(bi + "_attn.norm.query_norm.scale", bi + "_attn.norm.key_norm.scale", &qi));
         R3G_RC(qkv_args(bt + "_attn.norm.query_norm.scale", bt + "_attn.norm.key_norm.scale", &qt));
-        R3G_RC(gemm_pair(qkv_gemm_args(d.xn, (int64_t)Nl * H, li, Nl, qi, 0, nullptr, nullptr), 2 * NB,
-                         qkv_gemm_args(xnt, 0, lt, Mtxt, qt, 2 * NB, d.seg_txt, &d.h_seg_txt), 1, s));
+        R3G_RC(gemm_pair(qkv_gemm_args(d.xn, (int64_t)Nl * H, li, Nl, qi, 0, nullptr, nullptr), E * NB,
+                         qkv_gemm_args(xnt, 0, lt, Mtxt, qt, E * NB, d.seg_txt, &d.h_seg_txt), 1, s));
         hipError_t e = attention_launch(at, s);
         if (e != hipSuccess) return hip_fail(e, "attention_launch(dedup)");
         // attention projection
@@ -646,7 +688,7 @@ static int dit_forward_cfg_dedup(Model& m, const float* x_lat, float t_scalar, f
         R3G_RC(get_lin(m, blk + ".linear1", true, &l));
         QkvSplitArgs q;
         R3G_RC(qkv_args(blk + ".norm.query_norm.scale", blk + ".norm.key_norm.scale", &q));
-        const GemmArgs pq = qkv_gemm_args(d.xn, 0, l, Rall, q, 4 * NB, d.seg_all, &d.h_seg_all);
+        const GemmArgs pq = qkv_gemm_args(d.xn, 0, l, Rall, q, 2 * E * NB, d.seg_all, &d.h_seg_all);
         auto launch_qkv = [&]() -> int {
             hipError_t e = gemm_launch(pq, 1, s);
             if (e != hipSuccess) return hip_fail(e, "gemm_launch(qkv dedup)");
@@ -1093,7 +1135,7 @@ static int model_create(Ctx* ctx, const r3g_model_config* cfg) {
     const int64_t n_cat = mx({2LL * Tp * 5 * H, (int64_t)Nlp * W, (int64_t)Lp * Hc, (int64_t)qc * W});
     const int64_t n_hid = mx({(int64_t)Nlp * 4 * W, (int64_t)Lp * 3 * m->Fc, (int64_t)qc * c.vae_mlp_ratio * W});
     const int64_t n_inb = mx({2LL * Nl * m->cin_pad, (int64_t)(qc + 128) * 64, (int64_t)P * P * Kpatch});
-    const int64_t n_small = 2 * 256 + 2 * H + 2 * H + 2 * 12 * H + 4LL * Nl * c.dit_in_channels + 1024;
+    const int64_t n_small = 2 * 256 + 2 * H + 2 * H + 2 * 12 * H + 4LL * Nl * c.dit_in_channels + (256 + 2 * H) + 1024;
     const int64_t n_z = (int64_t)Nl * W;
     const int64_t n_geo = (int64_t)rup(Nl, 64) * W;
     size_t off = 0;
@@ -1114,6 +1156,7 @@ static int model_create(Ctx* ctx, const r3g_model_config* cfg) {
     m->small = (float*)(a + o_small); m->z = (float*)(a + o_z); m->geoK = (uint16_t*)(a + o_gk); m->geoVt = (uint16_t*)(a + o_gv);
     m->temb = m->small; m->th = m->temb + 2 * 256; m->vec = m->th + 2 * H; m->mods = m->vec + 2 * H;
     m->v2 = m->mods + 2 * 12 * H;
+    m->gemb = m->v2 + 4LL * Nl * c.dit_in_channels; m->gth = m->gemb + 256; m->gvec = m->gth + H;
     ctx->model = m;
     return R3G_OK;
 }
@@ -1180,22 +1223,20 @@ int r3g_dit_stream(r3g_ctx* ctx, float* d_out, int batch, void* stream) {
     return R3G_OK;
 }
 
-// The denoising loop for n_objects objects (latents f32 [n][Nl][Cin], cond2 bf16 [n][2][Lc][D]).  With a de-duplicated
-// unconditional context all objects go through every DiT layer together; otherwise one after the other.
-static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int n_objects, int steps, float guidance_scale,
-                       float shift, int uncond_uniform, hipStream_t s) {
+// The denoising loop for n_objects objects (latents f32 [n][Nl][Cin], cond2 bf16 [n][2][Lc][D]) over the sigma table
+// sig[0 .. steps].  With a de-duplicated unconditional context all objects go through every DiT layer together; otherwise one
+// after the other.  A guidance-distilled model (model.guidance_in.*) has no CFG batch: its objects always share the launches,
+// one entry each, the unconditional half of cond2 is never read and guidance_scale only feeds guidance_in.
+static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int n_objects, const std::vector<float>& sig,
+                       float guidance_scale, int uncond_uniform, hipStream_t s) {
     const r3g_model_config& c = m->c;
+    const int steps = (int)sig.size() - 1;
     const int64_t n = (int64_t)c.vae_num_latents * c.dit_in_channels;
     const int64_t cond_elems = (int64_t)m->Lc * c.dit_context_dim;
-    // sigmas = linspace(0,1,steps) (shifted), + a trailing 1: the last update has d_sigma = 0, as upstream
-    std::vector<float> sig(steps + 1);
-    for (int i = 0; i < steps; ++i) {
-        const double v = steps == 1 ? 0.0 : (double)i / (double)(steps - 1);
-        sig[i] = (float)(shift * v / (1.0 + (shift - 1.0) * v));
-    }
-    sig[steps] = 1.0f;
+    bool distilled = false;
+    R3G_RC(model_distilled(*m, &distilled));
     const bool dedup = g_cfg_dedup && uncond_uniform != 0;
-    if (!dedup) {
+    if (!dedup && !distilled) {
         float* x2 = m->v2 + 2 * n;  // [2][n] duplicated latents (CFG batch)
         for (int o = 0; o < n_objects; ++o) {
             float* lat = d_latents + o * n;
@@ -1205,22 +1246,38 @@ static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int 
                 if (ds == 0.f && g_skip_zero_step) continue;
                 R3G_TRY(hipMemcpyAsync(x2, lat, n * 4, hipMemcpyDeviceToDevice, s));
                 R3G_TRY(hipMemcpyAsync(x2 + n, lat, n * 4, hipMemcpyDeviceToDevice, s));
+                ++g_dit_evals;
                 R3G_RC(dit_forward(*m, x2, nullptr, sig[i], cond2, m->v2, 2, -1, -1, s));
                 R3G_TRY(cfg_euler_launch(lat, m->v2, n, guidance_scale, ds, s));
             }
         }
         return R3G_OK;
     }
-    for (int o0 = 0; o0 < n_objects; o0 += kMaxObjects) {
-        const int NB = std::min(kMaxObjects, n_objects - o0);
-        R3G_RC(ensure_dit_batch(*m, NB));
+    const int E = distilled ? 1 : 2, group = distilled ? kMaxObjectsDistilled : kMaxObjects;
+    if (distilled) {
+        // guidance_in(timestep_embedding(g)) depends on neither the step nor the object: once per call.  g goes through the same
+        // embedding as t (time_factor applied, cos first).
+        const int H = m->H;
+        Lin l;
+        R3G_TRY(timestep_embedding_launch(nullptr, guidance_scale, 1, c.dit_time_factor, m->gemb, s));
+        R3G_RC(get_lin(*m, "model.guidance_in.in_layer", true, &l));
+        if (l.N != H || l.K != 256) return fail(R3G_ERR_INVALID, "'model.guidance_in.in_layer.weight' is [%d][%d], expected [%d][256]", l.N, l.K, H);
+        R3G_TRY(gemv_launch(m->gemb, 1, 256, l.w, l.ldw, l.b, m->gth, H, 0, 1, s));
+        R3G_RC(get_lin(*m, "model.guidance_in.out_layer", true, &l));
+        if (l.N != H || l.K < H) return fail(R3G_ERR_INVALID, "'model.guidance_in.out_layer.weight' is [%d][%d], expected [%d][%d]", l.N, l.K, H, H);
+        R3G_TRY(gemv_launch(m->gth, 1, H, l.w, l.ldw, l.b, m->gvec, H, 0, 0, s));
+    }
+    for (int o0 = 0; o0 < n_objects; o0 += group) {
+        const int NB = std::min(group, n_objects - o0);
+        R3G_RC(ensure_dit_batch(*m, NB, E));
         Model::DitBatch& d = m->db;
         const int Ltp = dit_txt_rows(*m);
-        for (int o = 0; o < NB; ++o) {   // context rows of object o: its Lc cond tokens, then ONE unconditional token
+        for (int o = 0; o < NB; ++o) {   // context rows of object o: its Lc cond tokens, then (CFG) ONE unconditional token
             const uint16_t* cond2 = d_cond2 + 2 * (int64_t)(o0 + o) * cond_elems;
             uint16_t* dst = d.ctx + (int64_t)o * Ltp * c.dit_context_dim;
             R3G_TRY(hipMemcpyAsync(dst, cond2, (size_t)cond_elems * 2, hipMemcpyDeviceToDevice, s));
-            R3G_TRY(hipMemcpyAsync(dst + cond_elems, cond2 + cond_elems, (size_t)c.dit_context_dim * 2, hipMemcpyDeviceToDevice, s));
+            if (E == 2)
+                R3G_TRY(hipMemcpyAsync(dst + cond_elems, cond2 + cond_elems, (size_t)c.dit_context_dim * 2, hipMemcpyDeviceToDevice, s));
         }
         float* lat = d_latents + o0 * n;
         // The fp16 residual stream (option dit_resid_f16, default) tops out at 65504 where the fp32 stream of rounds 1-3 could not
@@ -1237,8 +1294,9 @@ static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int 
                 // (bit-identical; r3g_set_option("skip_zero_step", 0) evaluates it as upstream does)
                 const float ds = sig[i + 1] - sig[i];
                 if (ds == 0.f && g_skip_zero_step) continue;
-                R3G_RC(dit_forward_cfg_dedup(*m, lat, sig[i], d.v2, NB, s, allow_f16));
-                for (int o = 0; o < NB; ++o) R3G_TRY(cfg_euler_launch(lat + o * n, d.v2 + 2 * o * n, n, guidance_scale, ds, s));
+                R3G_RC(dit_forward_grouped(*m, lat, sig[i], d.v2, NB, s, allow_f16, distilled ? m->gvec : nullptr));
+                if (distilled) R3G_TRY(euler_step_launch(lat, d.v2, (int64_t)NB * n, ds, s));   // all objects of the group: lat += d_sigma v
+                else for (int o = 0; o < NB; ++o) R3G_TRY(cfg_euler_launch(lat + o * n, d.v2 + 2 * o * n, n, guidance_scale, ds, s));
             }
             if (!guard || attempt == 1) break;
             int bad = 0;
@@ -1256,10 +1314,22 @@ static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int 
     return R3G_OK;
 }
 
+// sigmas of FlowMatchEulerDiscreteScheduler: linspace(0,1,steps) (shifted), + a trailing 1: the last update has d_sigma = 0, as upstream
+static std::vector<float> linspace_sigmas(int steps, float shift) {
+    std::vector<float> sig(steps + 1);
+    for (int i = 0; i < steps; ++i) {
+        const double v = steps == 1 ? 0.0 : (double)i / (double)(steps - 1);
+        sig[i] = (float)(shift * v / (1.0 + (shift - 1.0) * v));
+    }
+    sig[steps] = 1.0f;
+    return sig;
+}
+
 int r3g_get_counter(const char* name, int64_t* value) {
     if (!name || !value) return fail(R3G_ERR_INVALID, "r3g_get_counter: null argument");
     if (!strcmp(name, "dit_f16_fallbacks")) *value = g_dit_f16_fallbacks;
     else if (!strcmp(name, "dit_groups")) *value = g_dit_groups;
+    else if (!strcmp(name, "dit_evals")) *value = g_dit_evals;
     else if (!strcmp(name, "geo_q_cache_builds")) *value = g_geo_q_cache_builds;
     else return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
     return R3G_OK;
@@ -1284,14 +1354,26 @@ int r3g_flow_sample(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond2, int
                     float shift, int uncond_uniform, void* stream) {
     NEED_MODEL("r3g_flow_sample");
     if (!d_latents || !d_cond2 || steps < 1) return fail(R3G_ERR_INVALID, "r3g_flow_sample: bad argument");
-    return flow_sample(m, d_latents, d_cond2, 1, steps, guidance_scale, shift, uncond_uniform, (hipStream_t)stream);
+    return flow_sample(m, d_latents, d_cond2, 1, linspace_sigmas(steps, shift), guidance_scale, uncond_uniform, (hipStream_t)stream);
 }
 
 int r3g_flow_sample_batch(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond2, int n_objects, int steps,
                           float guidance_scale, float shift, int uncond_uniform, void* stream) {
     NEED_MODEL("r3g_flow_sample_batch");
     if (!d_latents || !d_cond2 || steps < 1 || n_objects < 1) return fail(R3G_ERR_INVALID, "r3g_flow_sample_batch: bad argument");
-    return flow_sample(m, d_latents, d_cond2, n_objects, steps, guidance_scale, shift, uncond_uniform, (hipStream_t)stream);
+    return flow_sample(m, d_latents, d_cond2, n_objects, linspace_sigmas(steps, shift), guidance_scale, uncond_uniform,
+                       (hipStream_t)stream);
+}
+
+int r3g_flow_sample_sigmas(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond2, int n_objects, const float* sigmas, int n_sigmas,
+                           float guidance_scale, int uncond_uniform, void* stream) {
+    NEED_MODEL("r3g_flow_sample_sigmas");
+    if (!d_latents || !d_cond2 || !sigmas || n_sigmas < 2 || n_objects < 1)
+        return fail(R3G_ERR_INVALID, "r3g_flow_sample_sigmas: bad argument");
+    for (int i = 0; i < n_sigmas; ++i)
+        if (!std::isfinite(sigmas[i])) return fail(R3G_ERR_INVALID, "r3g_flow_sample_sigmas: sigmas[%d] is not finite", i);
+    return flow_sample(m, d_latents, d_cond2, n_objects, std::vector<float>(sigmas, sigmas + n_sigmas), guidance_scale, uncond_uniform,
+                       (hipStream_t)stream);
 }
 
 int r3g_vae_decode(r3g_ctx* ctx, const float* d_latents, float* d_z_out, void* stream) {

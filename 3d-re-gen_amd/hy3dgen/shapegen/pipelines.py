@@ -14,6 +14,7 @@ import numpy as np
 import torch
 import yaml
 
+from r3g import flow as _flow
 from r3g import mc as _mc
 from r3g import model as _model
 from r3g import weights as _weights
@@ -29,20 +30,29 @@ FULL = dict(
              geo_decoder_mlp_expand_ratio=4, geo_decoder_ln_post=True),
     cond=dict(image_size=518, patch_size=14, hidden_size=1536, num_hidden_layers=40, num_attention_heads=24,
               mlp_ratio=4, use_swiglu_ffn=True, layer_norm_eps=1e-6),
-    sched=dict(num_train_timesteps=1000, shift=1.0),
+    sched=dict(num_train_timesteps=1000, shift=1.0, kind="FlowMatchEulerDiscreteScheduler", pcm_timesteps=100),
     proc=dict(size=512, border_ratio=0.15),
     guidance_scale=5.0, box_v=1.01, mc_level=0.0)
 
+BUILTIN = ("full", "mini", "full-fast", "full-turbo", "mini-turbo")
+
 
 def builtin_config(name):
-    """'full' = hunyuan3d-dit-v2-0, 'mini' = hunyuan3d-dit-v2-mini (dims recalled)."""
+    """'full' = hunyuan3d-dit-v2-0, 'mini' = hunyuan3d-dit-v2-mini (dims recalled); the
+    guidance-distilled subfolders 'full-fast' = hunyuan3d-dit-v2-0-fast, 'full-turbo' = hunyuan3d-dit-v2-0-turbo, 'mini-turbo' =
+    hunyuan3d-dit-v2-mini-turbo: the same dims with guidance_embed, the turbo ones on the consistency scheduler."""
     import copy
+    if name not in BUILTIN:
+        raise KeyError(name)
     c = copy.deepcopy(FULL)
-    if name == "mini":
+    base, _, variant = name.partition("-")
+    if base == "mini":
         c["dit"].update(depth=8, depth_single_blocks=16)
         c["vae"].update(num_latents=512)
-    elif name != "full":
-        raise KeyError(name)
+    if variant:
+        c["dit"].update(guidance_embed=True)
+    if variant == "turbo":
+        c["sched"].update(kind="ConsistencyFlowMatchEulerDiscreteScheduler", pcm_timesteps=100)
     return c
 
 
@@ -64,8 +74,15 @@ def config_from_yaml(doc):
             c["cond"][k] = enc["config"][k]
     if "image_size" in enc:
         c["cond"]["image_size"] = enc["image_size"]
-    sp = doc.get("scheduler", {}).get("params", {})
-    c["sched"].update({k: sp[k] for k in ("num_train_timesteps", "shift") if k in sp})
+    sched = doc.get("scheduler", {})
+    sp = sched.get("params", {})
+    c["sched"].update({k: sp[k] for k in ("num_train_timesteps", "shift", "pcm_timesteps") if k in sp})
+    if "target" in sched:
+        # the scheduler's class by the last dotted component of its target (hy3dgen.shapegen.schedulers.<Class>)
+        kind = str(sched["target"]).rsplit(".", 1)[-1]
+        if kind not in _flow.SCHEDULERS:
+            raise ValueError("config.yaml names the scheduler %r; implemented: %s" % (kind, ", ".join(_flow.SCHEDULERS)))
+        c["sched"]["kind"] = kind
     ip = doc.get("image_processor", {}).get("params", {})
     c["proc"].update({k: ip[k] for k in ("size", "border_ratio") if k in ip})
     return c
@@ -118,7 +135,11 @@ class Hunyuan3DDiTPipeline:
                         subfolder="hunyuan3d-dit-v2-0", **kwargs):
         """model_path: a local directory holding <subfolder>/config.yaml + model[.variant].safetensors (or, with
         use_safetensors=False or when no safetensors file is there, model[.variant].ckpt) -- the HF snapshot layout --, or
-        'synthetic:<full|mini>[:seed]' for seeded synthetic weights."""
+        'synthetic:<full|mini|full-fast|full-turbo|mini-turbo>[:seed]' for seeded synthetic weights.  A snapshot whose
+        config.yaml says `guidance_embed: true` (upstream's subfolders hunyuan3d-dit-v2-0-fast, hunyuan3d-dit-v2-0-turbo,
+        hunyuan3d-dit-v2-mini-turbo) loads as a guidance-distilled model: no CFG batch, the turbo ones on the consistency
+        scheduler their config names.  NOT covered: upstream's turbo VAE swap (enable_flashvdm(replace_vae=True) keeps the
+        snapshot's own VAE), top-k KV selection, mc_algo='dmc', guidance-distilled texture models."""
         if isinstance(model_path, str) and model_path.startswith("synthetic:"):
             parts = model_path.split(":")
             cfg = builtin_config(parts[1])
@@ -260,13 +281,20 @@ class Hunyuan3DDiTPipeline:
             return torch.randn(shape, generator=generator, device=generator.device, dtype=dt).float().to(self.device)
         return torch.randn(shape, generator=generator, device="cpu", dtype=dt).float().to(self.device)
 
-    def generate_latents(self, images, num_inference_steps, guidance_scale, generator):
+    def generate_latents(self, images, num_inference_steps, guidance_scale, generator, sigmas=None):
         """preprocess + conditioner per image, then ALL objects through the denoising loop together
         (r3g_flow_sample_batch: every DiT layer is one launch over the objects' rows; per-object results do not depend on
         the company an object keeps) -> f32 [n, N, C]"""
         cond2 = torch.stack([self._encode_prepared(x) for x in self._prepared(images)], dim=0)
         latents = self._latents_for(generator, len(images))
         shift = self.cfg["sched"].get("shift", 1.0)
+        sched = self.cfg["sched"]
+        if sigmas is not None or getattr(self.model, "guidance_embed", False) or \
+                sched.get("kind", _flow.SCHEDULERS[0]) != _flow.SCHEDULERS[0]:
+            # an explicit table, the consistency scheduler, or a guidance-distilled model (no CFG batch: one entry per object,
+            # up to 8 objects per launch; guidance_scale only feeds guidance_in)
+            table = _flow.scheduler_sigmas(sched, num_inference_steps, sigmas)
+            return self.model.flow_sample_sigmas(latents, cond2, table, guidance_scale, uncond_uniform=True)
         if len(images) == 1:
             return self.model.flow_sample(latents[0], cond2[0], num_inference_steps, guidance_scale, shift,
                                           uncond_uniform=True)[None]          # zeros_like(cond)
@@ -296,10 +324,11 @@ class Hunyuan3DDiTPipeline:
             self.timings["grid_points_evaluated"] = n_dense
         return grid
 
-    def generate_grid(self, image, num_inference_steps, guidance_scale, generator, box_v, octree_resolution, mc_level=None):
+    def generate_grid(self, image, num_inference_steps, guidance_scale, generator, box_v, octree_resolution, mc_level=None,
+                      sigmas=None):
         import time
         t0 = time.perf_counter()
-        latents = self.generate_latents([image], num_inference_steps, guidance_scale, generator)[0]
+        latents = self.generate_latents([image], num_inference_steps, guidance_scale, generator, sigmas=sigmas)[0]
         self.model.vae_decode(latents)
         grid = self._query_grid(box_v, octree_resolution, self.cfg["mc_level"] if mc_level is None else mc_level)
         self.timings["grid_s"] = time.perf_counter() - t0
@@ -321,9 +350,13 @@ class Hunyuan3DDiTPipeline:
                  output_type="trimesh", enable_pbar=True, **kwargs):
         """image: one PIL image / path (the reference's call, src/2d_to_3d_models/run.py:77-84) or a list of them (upstream's
         batch dimension): the objects of a list share every launch of the denoising loop and are decoded one after the
-        other; the result has one entry per image."""
+        other; the result has one entry per image.  `sigmas`: an explicit strictly ascending table inside [0, 1] replaces the
+        scheduler's (it gets the trailing 1 as upstream's set_timesteps does; anything else is a ValueError).  A
+        guidance-distilled model runs without the CFG batch and groups up to 8 objects of a list per launch."""
         if image is None:
             raise ValueError("image is required")
+        if sigmas is not None:
+            _flow.scheduler_sigmas(self.cfg["sched"], num_inference_steps, sigmas)      # refuse a bad table before any GPU work
         if mc_algo not in (None, "mc"):
             raise NotImplementedError("only mc_algo='mc' (Lewiner marching cubes) is on the reference path")
         g = self.cfg["guidance_scale"] if guidance_scale is None else guidance_scale
@@ -333,7 +366,7 @@ class Hunyuan3DDiTPipeline:
             if isinstance(image, (list, tuple)):
                 import time
                 t0 = time.perf_counter()
-                latents = self.generate_latents(list(image), num_inference_steps, g, generator)
+                latents = self.generate_latents(list(image), num_inference_steps, g, generator, sigmas=sigmas)
                 out = []
                 for i in range(len(image)):
                     self.model.vae_decode(latents[i])
@@ -342,7 +375,8 @@ class Hunyuan3DDiTPipeline:
                     out.append(self._mesh_from_grid(grid, mc_level, box_v, octree_resolution, output_type))
                 self.timings["grid_s"] = time.perf_counter() - t0
                 return out
-            grid, latents = self.generate_grid(image, num_inference_steps, g, generator, box_v, octree_resolution, mc_level)
+            grid, latents = self.generate_grid(image, num_inference_steps, g, generator, box_v, octree_resolution, mc_level,
+                                               sigmas=sigmas)
             self.last_grid = grid
             return [self._mesh_from_grid(grid, mc_level, box_v, octree_resolution, output_type)]
 

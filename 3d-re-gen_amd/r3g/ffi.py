@@ -57,6 +57,7 @@ SYMBOLS = {
     "r3g_dit_stream": (_I, [_P, _P, _I, _P]),
     "r3g_flow_sample": (_I, [_P, _P, _P, _I, ctypes.c_float, ctypes.c_float, _I, _P]),
     "r3g_flow_sample_batch": (_I, [_P, _P, _P, _I, _I, ctypes.c_float, ctypes.c_float, _I, _P]),
+    "r3g_flow_sample_sigmas": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_float, _I, _P]),
     "r3g_vae_decode": (_I, [_P, _P, _P, _P]),
     "r3g_grid_query": (_I, [_P, _D, _I, _P, ctypes.c_int64, ctypes.c_int64, _P]),
     "r3g_hier_select": (_I, [_P, _P, _I, _D, _D, _I, _I64P, _P]),
@@ -152,7 +153,7 @@ def check(rc):
 
 
 def counter(name):
-    """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "geo_q_cache_builds")"""
+    """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "dit_evals", "geo_q_cache_builds")"""
     v = ctypes.c_int64(0)
     check(lib().r3g_get_counter(name.encode(), ctypes.byref(v)))
     return int(v.value)

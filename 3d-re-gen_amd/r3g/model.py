@@ -20,8 +20,6 @@ def make_config(cfg, grid_chunk=0):
     d, v, c = cfg["dit"], cfg["vae"], cfg["cond"]
     if not c.get("use_swiglu_ffn", True):
         raise ValueError("only the SwiGLU Dinov2 variant (dinov2-giant) is implemented")
-    if d.get("guidance_embed", False):
-        raise ValueError("guidance-distilled DiT variants are not on the reference's default path")
     m = _l.ModelConfig()
     m.dit_in_channels, m.dit_context_dim, m.dit_hidden = d["in_channels"], d["context_in_dim"], d["hidden_size"]
     m.dit_heads, m.dit_depth_double, m.dit_depth_single = d["num_heads"], d["depth"], d["depth_single_blocks"]
@@ -90,12 +88,28 @@ def prepare_weights(sd, device):
     return out, scalars
 
 
+def check_guidance_keys(cfg, state_dict):
+    """config and checkpoint must agree on guidance distillation: `guidance_embed: true` needs all four model.guidance_in.*
+    tensors (the first missing one is named), and a checkpoint that holds them needs the flag -- the library decides by the
+    tensors it is given (include/r3g.h r3g_flow_sample_sigmas), so a silent disagreement would change the sampler"""
+    from .weights import GUIDANCE_KEYS
+    have = [k for k in GUIDANCE_KEYS if k in state_dict]
+    if cfg["dit"].get("guidance_embed", False):
+        missing = [k for k in GUIDANCE_KEYS if k not in state_dict]
+        if missing:
+            raise KeyError("guidance-distilled model (guidance_embed: true): the checkpoint lacks '%s'" % missing[0])
+    elif have:
+        raise ValueError("the checkpoint holds '%s' but the config does not say guidance_embed: true" % have[0])
+
+
 class ShapeModel:
     """Weights + activation arena of one shape model on one GPU."""
 
     def __init__(self, cfg, state_dict, device=0, grid_chunk=0, private_ctx=False):
         if not torch.cuda.is_available():
             raise RuntimeError("r3g.ShapeModel needs an MI355X: libr3g has no CPU path")
+        check_guidance_keys(cfg, state_dict)
+        self.guidance_embed = bool(cfg["dit"].get("guidance_embed", False))
         self.cfg = cfg
         self.device = torch.device("cuda", device)
         self.private_ctx = bool(private_ctx)
@@ -193,6 +207,27 @@ class ShapeModel:
             _l.check(self.L.r3g_flow_sample_batch(self.ctx, latents.data_ptr(), cond2.data_ptr(), int(latents.shape[0]),
                                                   int(steps), float(guidance_scale), float(shift),
                                                   int(bool(uncond_uniform)), self._s()))
+        return latents
+
+    def flow_sample_sigmas(self, latents, cond2, sigmas, guidance_scale, uncond_uniform=None):
+        """the denoising loop over an explicit sigma table (r3g_flow_sample_sigmas): latents f32 [n,N,C] (modified in place and
+        returned), cond2 bf16 [n,2,Lc,D], sigmas float32 [steps + 1] on the host.  A guidance-distilled model (guidance_embed)
+        runs without the CFG batch -- guidance_scale feeds guidance_in, the unconditional half of cond2 is never read, up to 8
+        objects share a launch --; any other model runs classifier-free guidance as flow_sample_batch does."""
+        import numpy as np
+        latents = latents.to(self.device, torch.float32).contiguous()
+        cond2 = cond2.to(self.device, torch.bfloat16).contiguous()
+        if latents.ndim != 3 or cond2.ndim != 4 or cond2.shape[0] != latents.shape[0] or cond2.shape[1] != 2:
+            raise ValueError("flow_sample_sigmas: latents [n,N,C] and cond2 [n,2,Lc,D] expected")
+        sig = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float32).reshape(-1))
+        if sig.size < 2 or not np.isfinite(sig).all():
+            raise ValueError("flow_sample_sigmas: at least two finite sigmas expected")
+        if uncond_uniform is None:
+            uncond_uniform = self.guidance_embed or bool((cond2[:, 1] == cond2[:, 1, :1]).all().item())
+        with torch.cuda.device(self.device):
+            _l.check(self.L.r3g_flow_sample_sigmas(self.ctx, latents.data_ptr(), cond2.data_ptr(), int(latents.shape[0]),
+                                                   sig.ctypes.data_as(ctypes.c_void_p), int(sig.size), float(guidance_scale),
+                                                   int(bool(uncond_uniform)), self._s()))
         return latents
 
     def vae_decode(self, latents, return_z=False):

@@ -104,7 +104,16 @@ def param_shapes(cfg):
         lin(b + ".mlp.weights_out", Hc, F)
         s[b + ".layer_scale2.lambda1"] = (Hc,)
     ln(m + ".layernorm", Hc)
+    if d.get("guidance_embed", False):
+        # guidance-distilled checkpoints (upstream's -fast / -turbo subfolders): guidance_in = MLPEmbedder(256 -> H -> H).  AFTER
+        # every other key: synthetic_state_dict draws from one generator in this order, so all other tensors of a distilled
+        # synthetic checkpoint equal the undistilled one of the same seed
+        lin("model.guidance_in.in_layer", H, 256)
+        lin("model.guidance_in.out_layer", H, H)
     return s
+
+
+GUIDANCE_KEYS = tuple("model.guidance_in.%s.%s" % (l, k) for l in ("in_layer", "out_layer") for k in ("weight", "bias"))
 
 
 def _is_scale(name):

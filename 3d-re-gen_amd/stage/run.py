@@ -17,8 +17,12 @@ What differs, by design (MI355X-first):
   * per-object failures are collected into a status list and printed (the reference's pool path swallows them,
     :135-136); the exit code follows the reference: 0 when the stage ran, non-zero only on setup errors
     (no images / no weights), or when the sequential path hits an exception (as in the reference, :212-213);
-  * weights: private key `r3g_weights` (or env R3G_WEIGHTS) = local snapshot directory or 'synthetic:<full|mini>';
-    without it the HF cache is consulted offline, as there is no network on the target machines.
+  * weights: private key `r3g_weights` (or env R3G_WEIGHTS) = local snapshot directory or
+    'synthetic:<full|mini|full-fast|full-turbo|mini-turbo>'; '{model}' in it expands to full | mini, with `r3g_shape_variant` to
+    full-fast | full-turbo | mini-turbo; without it the HF cache is consulted offline, as there is no network on the target machines;
+  * private key `r3g_shape_variant: fast | turbo` selects upstream's guidance-distilled shape checkpoints (subfolders
+    hunyuan3d-dit-v2-0-fast / -turbo, hunyuan3d-dit-v2-mini-turbo): no CFG batch, up to 8 crops per launch; absent = the
+    reference's models.  (Upstream's turbo VAE swap and guidance-distilled texture models are not covered.)
 """
 import argparse
 import json
@@ -66,18 +70,39 @@ def list_images(input_folder):
     return [os.path.join(input_folder, f) for f in names]
 
 
+SHAPE_VARIANTS = {"full": ("fast", "turbo"), "mini": ("turbo",)}     # upstream's guidance-distilled subfolders
+
+
+def shape_variant(config):
+    """private key `r3g_shape_variant`: fast | turbo -- a guidance-distilled shape checkpoint (no CFG batch; turbo: ~5 steps on
+    the consistency scheduler its config.yaml names).  None when the key is absent: today's models."""
+    v = config.get("r3g_shape_variant")
+    if v is None:
+        return None
+    key = "mini" if config.get("mini", True) else "full"
+    if v not in SHAPE_VARIANTS[key]:
+        raise ValueError("r3g_shape_variant: %r is not one of %s for the '%s' model" % (v, ", ".join(SHAPE_VARIANTS[key]), key))
+    return v
+
+
 def select_model(config):
-    """reference :146-157 -- model ids / from_pretrained kwargs, plus the local weights override"""
+    """reference :146-157 -- model ids / from_pretrained kwargs, plus the local weights override; `r3g_shape_variant` is
+    appended to the subfolder (hunyuan3d-dit-v2-0-turbo, hunyuan3d-dit-v2-mini-turbo)"""
     models = {"full": {"id": "tencent/Hunyuan3D-2", "args": {}},
               "mini": {"id": "tencent/Hunyuan3D-2mini", "args": {"subfolder": "hunyuan3d-dit-v2-mini", "variant": "fp16"}}}
     key = "mini" if config.get("mini", True) else "full"
-    return key, models[key]
+    model = models[key]
+    v = shape_variant(config)
+    if v is not None:
+        model["args"] = dict(model["args"], subfolder="%s-%s" % (model["args"].get("subfolder", "hunyuan3d-dit-v2-0"), v))
+    return key, model
 
 
 def resolve_weights(config, key, model):
     w = config.get("r3g_weights") or os.environ.get("R3G_WEIGHTS")
     if w:
-        return w.replace("{model}", key)
+        v = shape_variant(config)
+        return w.replace("{model}", key if v is None else "%s-%s" % (key, v))
     try:
         from huggingface_hub import snapshot_download
         return snapshot_download(repo_id=model["id"], local_files_only=True)
@@ -142,8 +167,9 @@ def objects_per_launch(config):
     """private key `r3g_objects_per_launch` (default 4): how many crops share the launches of the denoising loop.  The DiT's
     GEMMs have 7.5 k rows per object; from two objects on every layer has enough rows for 256x256 tiles on all 256 CUs
     (measured: 1 663 / 1 499 / 1 476 ms per object at 1 / 2 / 4 objects per launch).  Results do not depend on it
-    (bit-identical per object)."""
-    return max(1, int(config.get("r3g_objects_per_launch", 4)))
+    (bit-identical per object).  A guidance-distilled model (`r3g_shape_variant`) has one entry per object instead of the CFG
+    pair: its default is 8, the same rows per launch."""
+    return max(1, int(config.get("r3g_objects_per_launch", 8 if shape_variant(config) else 4)))
 
 
 def volume_decoder(config):

@@ -220,6 +220,26 @@ int r3g_flow_sample(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond2, int
 int r3g_flow_sample_batch(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond2, int n_objects, int steps,
                           float guidance_scale, float shift, int uncond_uniform, void* stream);
 
+/* The same loop over an explicit sigma table, and the entry point of GUIDANCE-DISTILLED checkpoints (upstream's subfolders
+ * hunyuan3d-dit-v2-0-fast, -turbo, hunyuan3d-dit-v2-mini-turbo; [UPSTREAM-RECALLED]).
+ * sigmas: HOST array of n_sigmas = steps + 1 finite values; step i evaluates the model at t = sigmas[i] and updates
+ * x += (sigmas[i+1] - sigmas[i]) v; a step with d_sigma = 0 is skipped as in r3g_flow_sample.  r3g_flow_sample and
+ * r3g_flow_sample_batch are this function on linspace(0,1,steps) (shifted) + a trailing 1.
+ * Which engine runs is decided by what the model holds, not by an option:
+ *  - no "model.guidance_in.*" tensor registered: classifier-free guidance exactly as r3g_flow_sample_batch (up to 4 objects per
+ *    launch group); with the linspace table the result is bit-identical to it.
+ *  - all four of model.guidance_in.{in_layer,out_layer}.{weight,bias} registered: the model is guidance-distilled.
+ *    vec = time_in(timestep_embedding(t)) + guidance_in(timestep_embedding(guidance_scale)) -- the guidance scale goes through
+ *    the same embedding as t (times time_factor, cos first) --, there is NO CFG batch: one entry per object, conditional context
+ *    only, x += d_sigma v.  d_cond2 keeps the [n_objects][2][tokens][dim] layout, its unconditional half is never read, and
+ *    uncond_uniform is ignored.  Up to 8 objects share a launch group (same rows per launch as 4 CFG objects); each object's
+ *    result is bit-identical to its single-object run.
+ *  - a partial set is R3G_ERR_STATE at the first call, naming the missing key.
+ * r3g_dit_forward has no guidance input: on a distilled model it evaluates vec = time_in(timestep_embedding(t)) alone (the
+ * per-block parity hook).  Not covered: upstream's turbo VAE swap, top-k KV selection, guidance-distilled texture models. */
+int r3g_flow_sample_sigmas(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond2, int n_objects, const float* sigmas,
+                           int n_sigmas, float guidance_scale, int uncond_uniform, void* stream);
+
 /* ShapeVAE.forward(latents / scale_factor) (post_kl + transformer) and the geo decoder's K/V of the
  * result (computed once; upstream recomputes them for every chunk).  d_z_out (optional) f32
  * [num_latents][width] receives the decoded latents. */
@@ -496,6 +516,8 @@ int r3g_set_option(const char* name, int value);
 /* Process-wide event counters (round 6).  "dit_f16_fallbacks": launch groups of r3g_flow_sample_batch whose fp16 residual stream
  * produced non-finite latents and that therefore ran a second time on the fp32 stream ("dit_f16_guard"; such a group costs twice its
  * time -- bench.py and the stage report carry the count so that a slow run says why).  "dit_groups": launch groups run so far.
+ * "dit_evals": DiT evaluations issued so far, one per launch group and evaluated step (49 for upstream's 50-step schedule, whose
+ * last step is skipped; N for an N-step consistency table; an fp32 re-run counts again).
  * "geo_q_cache_builds": allocations of the geo decoder's query-side cache so far (a change of (R, bound) frees and allocates it
  * again; r3g_grid_query_points and the coarse levels of r3g_grid_query_hier never do).
  * r3g_flow_sample_batch is SYNCHRONOUS while the guard is on (one 4-byte read-back per group) and must not be captured into a
