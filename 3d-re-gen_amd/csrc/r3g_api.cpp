@@ -134,6 +134,7 @@ void r3g_destroy(r3g_ctx* ctx) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     (void)hipSetDevice(c->device);
     if (c->mc_ws) (void)hipFree(c->mc_ws);
+    if (c->dmc_ws) (void)hipFree(c->dmc_ws);
     if (c->mesh_ws) (void)hipFree(c->mesh_ws);
     if (c->tex_ws) (void)hipFree(c->tex_ws);
     if (c->hier_ws) (void)hipFree(c->hier_ws);
@@ -188,6 +189,55 @@ int r3g_mc_emit(r3g_ctx* ctx, float* d_verts, int32_t* d_faces, const double* xf
     hipError_t e = mc_emit_launch(c->mc_grid, c->mc_n[0], c->mc_n[1], c->mc_n[2], c->mc_level, c->mc_ws, c->mc_lay,
                                   d_verts, d_faces, xform, reverse_faces, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "mc_emit_launch");
+    return R3G_OK;
+}
+
+// ---- dual marching cubes ----------------------------------------------------------------
+int r3g_dmc_count(r3g_ctx* ctx, const float* d_grid, int n0, int n1, int n2, double level, int manifold,
+                  int64_t* n_verts, int64_t* n_faces, void* stream) {
+    if (!ctx || !d_grid || !n_verts || !n_faces) return fail(R3G_ERR_INVALID, "r3g_dmc_count: null argument");
+    if (n0 < 2 || n1 < 2 || n2 < 2) return fail(R3G_ERR_INVALID, "Input array must be at least 2x2x2.");
+    const uint64_t nnodes = (uint64_t)n0 * n1 * n2;
+    // at most 4 vertices and 6 triangles per cell: ids and triangle counts stay inside int32
+    if (nnodes * 6 >= (1ull << 31)) return fail(R3G_ERR_INVALID, "r3g_dmc_count: grid too large for int32 vertex ids");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    c->dmc_counted = false;
+    DmcWorkspaceLayout lay;
+    const size_t need = dmc_workspace_bytes(n0, n1, n2, &lay);
+    int rc = c->reserve(&c->dmc_ws, &c->dmc_ws_bytes, need, "hipMalloc(dmc workspace)");
+    if (rc) return rc;
+    hipError_t e = dmc_count_launch(d_grid, n0, n1, n2, level, manifold, c->dmc_ws, lay, s);
+    if (e != hipSuccess) return hip_fail(e, "dmc_count_launch");
+    e = hipMemcpyAsync(c->h_small, c->dmc_ws + lay.off_small, 64, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(dmc totals)");
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(dmc count)");
+    const unsigned status = *(const unsigned*)c->h_small;
+    const unsigned long long nv = ((const unsigned long long*)c->h_small)[2];
+    const unsigned long long nq = ((const unsigned long long*)c->h_small)[3];
+    *n_verts = (int64_t)nv;
+    *n_faces = (int64_t)(2 * nq);
+    if (!(status & 4u) && (!(status & 1u) || !(status & 2u)))
+        return fail(R3G_ERR_LEVEL_RANGE, "Surface level must be within volume data range.");
+    if (nq == 0) return fail(R3G_ERR_NO_SURFACE, "No surface found at the given iso value.");
+    c->dmc_lay = lay;
+    c->dmc_lay.nnz = (uint32_t)((const unsigned long long*)c->h_small)[4];
+    c->dmc_grid = d_grid;
+    c->dmc_n[0] = n0; c->dmc_n[1] = n1; c->dmc_n[2] = n2;
+    c->dmc_level = level;
+    c->dmc_counted = true;
+    return R3G_OK;
+}
+
+int r3g_dmc_emit(r3g_ctx* ctx, float* d_verts, int32_t* d_faces, const double* xform, int reverse_faces,
+                 void* stream) {
+    if (!ctx || !d_verts || !d_faces) return fail(R3G_ERR_INVALID, "r3g_dmc_emit: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->dmc_counted) return fail(R3G_ERR_STATE, "r3g_dmc_emit: no successful r3g_dmc_count precedes this call");
+    hipError_t e = dmc_emit_launch(c->dmc_grid, c->dmc_n[0], c->dmc_n[1], c->dmc_n[2], c->dmc_level, c->dmc_ws, c->dmc_lay,
+                                   d_verts, d_faces, xform, reverse_faces, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "dmc_emit_launch");
     return R3G_OK;
 }
 

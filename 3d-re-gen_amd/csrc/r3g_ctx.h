@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "dmc_kernels.h"
 #include "hier_kernels.h"
 #include "kernels.h"
 #include "mc_kernels.h"
@@ -26,6 +27,14 @@ struct Ctx {
     int mc_n[3] = {0, 0, 0};
     double mc_level = 0.0;
     bool mc_counted = false;
+    // dual marching cubes
+    char* dmc_ws = nullptr;
+    size_t dmc_ws_bytes = 0;
+    DmcWorkspaceLayout dmc_lay{};
+    const float* dmc_grid = nullptr;
+    int dmc_n[3] = {0, 0, 0};
+    double dmc_level = 0.0;
+    bool dmc_counted = false;
     // mesh cleaners
     char* mesh_ws = nullptr;
     size_t mesh_ws_bytes = 0;

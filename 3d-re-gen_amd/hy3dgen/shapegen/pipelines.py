@@ -15,6 +15,7 @@ import torch
 import yaml
 
 from r3g import flow as _flow
+from r3g import dmc as _dmc
 from r3g import mc as _mc
 from r3g import model as _model
 from r3g import weights as _weights
@@ -115,9 +116,10 @@ class Hunyuan3DDiTPipeline:
         self.hier_band = 0.95               # |logit - mc_level| below which a coarse point is refined
         self.hier_min_resolution = 63
         self.last_hier_stats = None
+        self.mc_algo = "mc"                # surface extractor of a call that passes mc_algo=None: "mc" | "dmc"
 
-    # The three places where this class touches the device.  (The API-contract test that runs the reference's stage
-    # script on a machine without a GPU overrides exactly these; the product has no CPU path.)
+    # The four places where this class touches the device.  (The API-contract test that runs the reference's stage
+    # script on a machine without a GPU overrides the first three, all that the reference path reaches; the product has no CPU path.)
     def _make_model(self, cfg, state_dict, grid_chunk):
         return _model.ShapeModel(cfg, state_dict, self.device.index, grid_chunk=grid_chunk,
                                  private_ctx=getattr(self, "private_ctx", False))
@@ -129,6 +131,10 @@ class Hunyuan3DDiTPipeline:
         return _mc.extract_mesh(grid, mc_level, box_v, octree_resolution,
                                 ctx=self.model.ctx if getattr(self, "private_ctx", False) else None)
 
+    def _extract_mesh_dmc(self, grid, mc_level, octree_resolution):
+        return _dmc.extract_mesh(grid, mc_level, octree_resolution,
+                                 ctx=self.model.ctx if getattr(self, "private_ctx", False) else None)
+
     # ---- construction (same entry points as upstream) -------------------------------------------
     @classmethod
     def from_pretrained(cls, model_path, device="cuda", dtype=None, use_safetensors=True, variant="fp16",
@@ -139,7 +145,7 @@ class Hunyuan3DDiTPipeline:
         config.yaml says `guidance_embed: true` (upstream's subfolders hunyuan3d-dit-v2-0-fast, hunyuan3d-dit-v2-0-turbo,
         hunyuan3d-dit-v2-mini-turbo) loads as a guidance-distilled model: no CFG batch, the turbo ones on the consistency
         scheduler their config names.  NOT covered: upstream's turbo VAE swap (enable_flashvdm(replace_vae=True) keeps the
-        snapshot's own VAE), top-k KV selection, mc_algo='dmc', guidance-distilled texture models."""
+        snapshot's own VAE), top-k KV selection, guidance-distilled texture models."""
         if isinstance(model_path, str) and model_path.startswith("synthetic:"):
             parts = model_path.split(":")
             cfg = builtin_config(parts[1])
@@ -306,9 +312,12 @@ class Hunyuan3DDiTPipeline:
         (r3g_grid_query_hier: a coarse grid densely, then only the points near the surface; defined in DESIGN.md, modelled on
         upstream's decoder but not pinned to it) and enable_flashvdm(False) restores the dense decoder.  `adaptive_kv_selection`,
         `topk_mode` and `replace_vae` concern upstream's top-k KV selection and its VAE swap: accepted and ignored, NOT
-        implemented -- the cross-attention stays exact.  mc_algo='dmc' stays unavailable."""
+        implemented -- the cross-attention stays exact.  The surface extractor is NOT chosen here: mc_algo other than 'mc' is
+        refused; dual marching cubes is selected per call (`pipeline(image, mc_algo="dmc")`) or by the pipeline attribute
+        `mc_algo` ("mc" | "dmc"), which a call that passes mc_algo=None uses."""
         if mc_algo not in (None, "mc"):
-            raise NotImplementedError("only mc_algo='mc' (Lewiner marching cubes) is on the reference path")
+            raise NotImplementedError("enable_flashvdm selects the volume decoder only: choose the surface extractor with "
+                                      "pipeline(image, mc_algo='dmc') or pipeline.mc_algo = 'dmc'")
         self.volume_decoder = "hierarchical" if enabled else "vanilla"
 
     def _query_grid(self, box_v, octree_resolution, mc_level):
@@ -334,9 +343,19 @@ class Hunyuan3DDiTPipeline:
         self.timings["grid_s"] = time.perf_counter() - t0
         return grid, latents
 
-    def _mesh_from_grid(self, grid, mc_level, box_v, octree_resolution, output_type):
+    def _resolve_mc_algo(self, mc_algo):
+        algo = getattr(self, "mc_algo", "mc") if mc_algo is None else mc_algo
+        if algo not in ("mc", "dmc"):
+            raise NotImplementedError("mc_algo=%r: the surface extractors are 'mc' (Lewiner marching cubes) and 'dmc' "
+                                      "(dual marching cubes)" % (algo,))
+        return algo
+
+    def _mesh_from_grid(self, grid, mc_level, box_v, octree_resolution, output_type, mc_algo="mc"):
         try:
-            v, f = self._extract_mesh(grid, mc_level, box_v, octree_resolution)
+            if mc_algo == "dmc":
+                v, f = self._extract_mesh_dmc(grid, mc_level, octree_resolution)
+            else:
+                v, f = self._extract_mesh(grid, mc_level, box_v, octree_resolution)
         except (ValueError, RuntimeError) as e:   # upstream: traceback + None for this object
             print("[hy3dgen] surface extraction failed: %s" % e)
             return None
@@ -352,13 +371,15 @@ class Hunyuan3DDiTPipeline:
         batch dimension): the objects of a list share every launch of the denoising loop and are decoded one after the
         other; the result has one entry per image.  `sigmas`: an explicit strictly ascending table inside [0, 1] replaces the
         scheduler's (it gets the trailing 1 as upstream's set_timesteps does; anything else is a ValueError).  A
-        guidance-distilled model runs without the CFG batch and groups up to 8 objects of a list per launch."""
+        guidance-distilled model runs without the CFG batch and groups up to 8 objects of a list per launch.  `mc_algo`:
+        "mc" (Lewiner marching cubes, the reference path), "dmc" (dual marching cubes, DESIGN.md section 4c: vertices in
+        upstream's dmc frame, box_v not applied) or None for the pipeline attribute `mc_algo`; anything else is a
+        NotImplementedError."""
         if image is None:
             raise ValueError("image is required")
         if sigmas is not None:
             _flow.scheduler_sigmas(self.cfg["sched"], num_inference_steps, sigmas)      # refuse a bad table before any GPU work
-        if mc_algo not in (None, "mc"):
-            raise NotImplementedError("only mc_algo='mc' (Lewiner marching cubes) is on the reference path")
+        mc_algo = self._resolve_mc_algo(mc_algo)
         g = self.cfg["guidance_scale"] if guidance_scale is None else guidance_scale
         box_v = self.cfg["box_v"] if box_v is None else box_v
         mc_level = self.cfg["mc_level"] if mc_level is None else mc_level
@@ -372,13 +393,13 @@ class Hunyuan3DDiTPipeline:
                     self.model.vae_decode(latents[i])
                     grid = self._query_grid(box_v, octree_resolution, mc_level)
                     self.last_grid = grid
-                    out.append(self._mesh_from_grid(grid, mc_level, box_v, octree_resolution, output_type))
+                    out.append(self._mesh_from_grid(grid, mc_level, box_v, octree_resolution, output_type, mc_algo))
                 self.timings["grid_s"] = time.perf_counter() - t0
                 return out
             grid, latents = self.generate_grid(image, num_inference_steps, g, generator, box_v, octree_resolution, mc_level,
                                                sigmas=sigmas)
             self.last_grid = grid
-            return [self._mesh_from_grid(grid, mc_level, box_v, octree_resolution, output_type)]
+            return [self._mesh_from_grid(grid, mc_level, box_v, octree_resolution, output_type, mc_algo)]
 
 
 class Hunyuan3DDiTFlowMatchingPipeline(Hunyuan3DDiTPipeline):

@@ -37,6 +37,8 @@ SYMBOLS = {
     "r3g_destroy": (None, [_P]),
     "r3g_mc_count": (_I, [_P, _P, _I, _I, _I, _D, _I, _I64P, _I64P, _P]),
     "r3g_mc_emit": (_I, [_P, _P, _P, _P, _I, _P]),
+    "r3g_dmc_count": (_I, [_P, _P, _I, _I, _I, _D, _I, _I64P, _I64P, _P]),
+    "r3g_dmc_emit": (_I, [_P, _P, _P, _P, _I, _P]),
     "r3g_mesh_remove_floaters": (_I, [_P, _P, _I64P, _P, _I64P, _D, _P]),
     "r3g_mesh_remove_degenerate": (_I, [_P, _P, _I64P, _P, _I64P, _P]),
     "r3g_mesh_reduce_faces": (_I, [_P, _P, _I64P, _P, _I64P, ctypes.c_int64, _P]),

@@ -189,6 +189,22 @@ def apply_volume_decoder(config, shapegen):
     return shapegen
 
 
+def mc_algo(config):
+    """private key `r3g_mc_algo`: mc (default: Lewiner marching cubes, the reference path) | dmc (dual marching cubes,
+    DESIGN.md section 4c).  None when the key is absent: the pipeline keeps its own `mc_algo`."""
+    v = config.get("r3g_mc_algo")
+    if v is not None and v not in ("mc", "dmc"):
+        raise ValueError("r3g_mc_algo: %r is not one of mc, dmc" % (v,))
+    return v
+
+
+def apply_mc_algo(config, shapegen):
+    v = mc_algo(config)
+    if v is not None:
+        shapegen.mc_algo = v
+    return shapegen
+
+
 def shape_meshes(images, shapegen, config):
     """reference :77-84 for a group of images: the raw marching-cubes meshes, in order (None where extraction failed).
     Every object gets a generator seeded with cfg.seed, exactly as the reference seeds each of its calls (:82)."""
@@ -309,6 +325,7 @@ def run_rank(config, image_paths, output_folder, rank, world, factory, swallow_e
     device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")) if torch.cuda.is_available() else "cpu"
     shapegen, texgen, cleaners = factory(config, device)
     apply_volume_decoder(config, shapegen)
+    apply_mc_algo(config, shapegen)
     results = []
     todo = partition(len(image_paths), rank, world)
     B = objects_per_launch(config)
@@ -409,6 +426,7 @@ def run_distributed(config, input_folder, output_folder, rank, world, factory):
             wd.beat("loading the models")
         shapegen, texgen, cleaners = factory(config, device)
         apply_volume_decoder(config, shapegen)
+        apply_mc_algo(config, shapegen)
         if wd is not None:
             wd.beat("models loaded")
 
@@ -488,6 +506,7 @@ def main(argv=None, factory=default_factory):
     ap.add_argument("--config", default="../src/config.yaml", type=str, help="Path to the configuration file.")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    mc_algo(config)     # a bad r3g_mc_algo is refused before the output folder is cleared or a model is loaded
     input_folder = config["input_folder_hy"]
     if config["use_banana"]:
         input_folder = config["prepped_for_hunyuan"]

@@ -72,6 +72,25 @@ int r3g_mc_count(r3g_ctx* ctx, const float* d_grid, int n0, int n1, int n2, doub
 int r3g_mc_emit(r3g_ctx* ctx, float* d_verts, int32_t* d_faces, const double* xform, int reverse_faces,
                 void* stream);
 
+/* ---- dual marching cubes ---------------------------------------------------------------------
+ * The extractor behind mc_algo="dmc": one vertex per surface patch of a cell, one quad (two triangles) per crossed
+ * grid edge that has four cells around it.  The semantics are this project's own and fixed to the bit in DESIGN.md
+ * section 4c; they are not pinned to upstream's extractor.
+ *
+ * r3g_dmc_count: classify all cells of the C-contiguous fp32 grid d_grid[n0][n1][n2] (inside = value > level), apply
+ *   the manifold rule (manifold != 0; 0 is the cross-check form without it), scan, and report the mesh size.
+ *   Synchronises `stream`.  R3G_ERR_LEVEL_RANGE under the condition of r3g_mc_count, R3G_ERR_NO_SURFACE when the
+ *   mesh has no face.
+ * r3g_dmc_emit: write the mesh of the preceding r3g_dmc_count (same grid, still resident): d_verts float32 [nV][3],
+ *   d_faces int32 [nF][3].  xform == NULL: index space, columns (axis0, axis1, axis2); otherwise the 9 doubles of
+ *   r3g_mc_emit with the same meaning.  reverse_faces == 0: outward for positive-inside fields; != 0: every triangle
+ *   (a, b, c) is written (c, b, a).  Without a successful count: R3G_ERR_STATE.
+ */
+int r3g_dmc_count(r3g_ctx* ctx, const float* d_grid, int n0, int n1, int n2, double level, int manifold,
+                  int64_t* n_verts, int64_t* n_faces, void* stream);
+int r3g_dmc_emit(r3g_ctx* ctx, float* d_verts, int32_t* d_faces, const double* xform, int reverse_faces,
+                 void* stream);
+
 /* ---- mesh cleaners ------------------------------------------------------
  * Replace `mesh = FloaterRemover()(mesh); mesh = DegenerateFaceRemover()(mesh); mesh = FaceReducer()(mesh)`
  * (reference src/2d_to_3d_models/run.py:93-94; upstream hy3dgen/shapegen/postprocessors.py runs pymeshlab on

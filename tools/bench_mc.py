@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the marching-cubes kernels on one grid (HIP events on the launch stream).
 
-    python tools/bench_mc.py [--n 257] [--iters 20]
-Prints one JSON line: per-phase times, algorithmic bytes (4*n^3 + 12 V + 12 F) and GB/s.
+    python tools/bench_mc.py [--n 257] [--iters 20] [--algo mc|dmc|both]
+Prints one JSON line per algorithm: per-phase times, algorithmic bytes (4*n^3 + 12 V + 12 F) and GB/s.
 """
 import argparse
 import json
@@ -45,42 +45,52 @@ def main():
     ap.add_argument("--field", default="blob", choices=["blob", "noise", "dot"])
     ap.add_argument("--n", type=int, default=257)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--algo", default="mc", choices=["mc", "dmc", "both"],
+                    help="mc: Lewiner marching cubes; dmc: dual marching cubes; both: the two alternating call by call "
+                         "in one run (one JSON line each)")
     a = ap.parse_args()
-    from r3g import mc
+    import ctypes
+    from r3g import dmc, ffi, mc
+    extract = {"mc": mc.extract_mesh, "dmc": dmc.extract_mesh}
+    algos = ["mc", "dmc"] if a.algo == "both" else [a.algo]
     g = {"blob": blob, "noise": field, "dot": dot}[a.field](a.n).cuda()
     for _ in range(3):
-        v, f = mc.extract_mesh(g)
+        for k in algos:
+            v, f = extract[k](g)
     torch.cuda.synchronize()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.iters + 1)]
-    ev[0].record()
+    # whole calls (count + read-back + allocation + emit), HIP events on the stream, the algorithms alternating
+    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)] for k in algos}
+    size = {}
     for i in range(a.iters):
-        v, f = mc.extract_mesh(g)
-        ev[i + 1].record()
+        for k in algos:
+            ev[k][i][0].record()
+            v, f = extract[k](g)
+            ev[k][i][1].record()
+            size[k] = (v.shape[0], f.shape[0])
     torch.cuda.synchronize()
-    ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(a.iters))
-    med = ms[len(ms) // 2]
-    V, F = v.shape[0], f.shape[0]
-    bytes_alg = 4 * a.n ** 3 + 12 * V + 12 * F
-    # the kernels alone (HIP events around each launch on its stream: r3g_prof_*): classify = family 6, the rest = 7
-    import ctypes
-    from r3g import ffi
     L = ffi.lib()
-    ffi.check(L.r3g_prof_enable(1))
-    for _ in range(a.iters):
-        mc.extract_mesh(g)
-    torch.cuda.synchronize()
-    cnt, pms, work = (ctypes.c_int64 * 9)(), (ctypes.c_double * 9)(), (ctypes.c_double * 9)()
-    ffi.check(L.r3g_prof_read(cnt, pms, work, 9))
-    ffi.check(L.r3g_prof_enable(0))
-    cls_us = 1e3 * pms[6] / max(1, cnt[6])
-    other_us = 1e3 * pms[7] / max(1, a.iters)
-    kern_ms = (cls_us + other_us) * 1e-3
-    print(json.dumps({"field": a.field, "n": a.n, "V": V, "F": F, "ms_median": med, "ms_min": ms[0], "alg_bytes": bytes_alg,
-                      "GBps_median": bytes_alg / med / 1e6, "frac_of_8TBps": bytes_alg / med / 1e6 / 8000,
-                      "classify_us": cls_us, "scan_vertices_faces_us": other_us,
-                      "classify_GBps": 4 * a.n ** 3 / cls_us / 1e3, "kernels_GBps": bytes_alg / kern_ms / 1e6,
-                      "kernels_frac_of_8TBps": bytes_alg / kern_ms / 1e6 / 8000,
-                      "options": os.environ.get("R3G_OPTIONS", "")}))
+    for k in algos:
+        ms = sorted(b.elapsed_time(e) for b, e in ev[k])
+        med = ms[len(ms) // 2]
+        V, F = size[k]
+        bytes_alg = 4 * a.n ** 3 + 12 * V + 12 * F
+        # the kernels alone (HIP events around each launch on its stream: r3g_prof_*): classify = family 6, the rest = 7
+        ffi.check(L.r3g_prof_enable(1))
+        for _ in range(a.iters):
+            extract[k](g)
+        torch.cuda.synchronize()
+        cnt, pms, work = (ctypes.c_int64 * 9)(), (ctypes.c_double * 9)(), (ctypes.c_double * 9)()
+        ffi.check(L.r3g_prof_read(cnt, pms, work, 9))
+        ffi.check(L.r3g_prof_enable(0))
+        cls_us = 1e3 * pms[6] / max(1, cnt[6])
+        other_us = 1e3 * pms[7] / max(1, a.iters)
+        kern_ms = (cls_us + other_us) * 1e-3
+        print(json.dumps({"algo": k, "field": a.field, "n": a.n, "V": V, "F": F, "ms_median": med, "ms_min": ms[0],
+                          "alg_bytes": bytes_alg, "GBps_median": bytes_alg / med / 1e6, "frac_of_8TBps": bytes_alg / med / 1e6 / 8000,
+                          "classify_us": cls_us, "scan_vertices_faces_us": other_us,
+                          "classify_GBps": 4 * a.n ** 3 / cls_us / 1e3, "kernels_GBps": bytes_alg / kern_ms / 1e6,
+                          "kernels_frac_of_8TBps": bytes_alg / kern_ms / 1e6 / 8000,
+                          "options": os.environ.get("R3G_OPTIONS", "")}))
 
 
 if __name__ == "__main__":
