@@ -26,6 +26,7 @@
 
 #include "../../include/r3g.h"
 #include "kernels.h"
+#include "kvsel_kernels.h"
 #include "mesh_kernels.h"
 #include "prof.h"
 #include "r3g_ctx.h"
@@ -73,6 +74,10 @@ static bool g_skip_zero_step = true;   // skip the DiT evaluation of a step whos
 // default: all of them).  Consecutive segments of one schedule, each continuing on the previous one's latents, are the same
 // launches as the whole schedule in one call: tests read the latents after 10, 20, ... of 50 steps this way.
 static int g_flow_first_step = 0, g_flow_last_step = 1 << 30;
+// adaptive top-k selection of the geo decoder's cross-attention keys (options "geo_kv_topk" / "geo_kv_group" /
+// "geo_kv_stride"): 0 exact (default) | k > 0 keys kept per (group, head), clamped to num_latents | -1 upstream's rule
+static int g_geo_kv_topk = 0, g_geo_kv_group = 8192, g_geo_kv_stride = 64;
+static int64_t g_geo_kv_groups = 0;      // (group, head) selections made so far (r3g_get_counter "geo_kv_groups")
 
 struct Model {
     r3g_model_config c{};
@@ -146,6 +151,14 @@ struct Model {
     // being built and its logits; grown on demand, released with the model
     char *hier_grids = nullptr, *hier_idx = nullptr, *hier_val = nullptr;
     size_t hier_grids_bytes = 0, hier_idx_bytes = 0, hier_val_bytes = 0;
+    // top-k KV selection (kvsel_kernels.h), grown on demand: the grouped Q of a pass, the compact K / V^T and the index table of its
+    // (group, head) pairs, and the row-major copy of the object's V (made by the first top-k pass after r3g_vae_decode)
+    char *kv_q = nullptr, *kv_k = nullptr, *kv_vt = nullptr, *kv_idx = nullptr, *kv_v = nullptr;
+    size_t kv_q_bytes = 0, kv_k_bytes = 0, kv_vt_bytes = 0, kv_idx_bytes = 0, kv_v_bytes = 0;
+    bool kv_v_valid = false;
+    int kv_last_groups = 0, kv_last_k = 0;      // shape of the table the last top-k pass left in kv_idx (0: none yet)
+    const uint16_t* kv_last_q = nullptr;        // ... and the Q rows it was made from: [H][kv_last_npad][64], kv_last_n of them valid
+    int kv_last_n = 0, kv_last_npad = 0;
     std::string err;
 
     const Tensor* find(const std::string& name) const {
@@ -783,6 +796,7 @@ static int vae_decode(Model& m, const float* latents, hipStream_t s) {
     }
     R3G_RC(gemm_qkv(m, m.xn, W, 0, l, 0, 2 * W, Nl, W, 1, q, QKV_HEAD_KV, s));
     m.have_z = true;
+    m.kv_v_valid = false;
     return R3G_OK;
 }
 
@@ -841,6 +855,61 @@ static int layernorm_fp8(const float* x, int64_t ldx, uint8_t* y8, int64_t ldy8,
     return R3G_OK;
 }
 
+// ---- top-k KV selection ---------------------------------------------------------------------
+static int kv_grow(char** buf, size_t* have, size_t need, hipStream_t s, const char* what) {
+    if (need <= *have) return R3G_OK;
+    if (*buf) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(*buf); *buf = nullptr; *have = 0; }
+    if (hipMalloc((void**)buf, need) != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        return fail(R3G_ERR_HIP, "hipMalloc(%s, %zu bytes) failed", what, need);
+    }
+    *have = need;
+    return R3G_OK;
+}
+
+// the keys kept per (group, head) under the current options: 0 = exact attention
+static int kv_topk_for(int num_latents) {
+    if (g_geo_kv_topk == 0) return 0;
+    const int k = g_geo_kv_topk < 0 ? kvsel_upstream_topk(num_latents) : g_geo_kv_topk;
+    return std::max(1, std::min(k, num_latents));
+}
+
+// The attention of one pass in top-k mode: Q [H][npad][64] (the pass's rows, as the exact path holds them) is cut into groups of
+// g_geo_kv_group rows; per (group, head) the k best keys are selected and gathered, and the groups run as the batches of one
+// attention launch with their own K / V^T (a shorter tail group as a second launch).  Output rows land in m.cat as in the exact path.
+static int kv_attention(Model& m, const uint16_t* Qp, int n, int npad, int k, hipStream_t s) {
+    const int W = m.W, Nl = m.c.vae_num_latents, heads = m.Wh, G = g_geo_kv_group, Lkp = (int)rup(Nl, 64), kpad = (int)rup(k, 64);
+    const KvselCut cut = kvsel_cut(n, G);
+    R3G_RC(kv_grow(&m.kv_q, &m.kv_q_bytes, 2 * (size_t)kvsel_grouped_elems(n, G, heads), s, "grouped Q"));
+    R3G_RC(kv_grow(&m.kv_k, &m.kv_k_bytes, 2 * (size_t)cut.groups * heads * kpad * 64, s, "compact K"));
+    R3G_RC(kv_grow(&m.kv_vt, &m.kv_vt_bytes, 2 * (size_t)cut.groups * heads * kpad * 64, s, "compact V^T"));
+    R3G_RC(kv_grow(&m.kv_idx, &m.kv_idx_bytes, 4 * (size_t)cut.groups * heads * k, s, "selection indices"));
+    R3G_RC(kv_grow(&m.kv_v, &m.kv_v_bytes, 2 * (size_t)heads * Nl * 64, s, "row-major V"));
+    uint16_t *gq = reinterpret_cast<uint16_t*>(m.kv_q), *kc = reinterpret_cast<uint16_t*>(m.kv_k), *vtc = reinterpret_cast<uint16_t*>(m.kv_vt);
+    uint16_t* vrows = reinterpret_cast<uint16_t*>(m.kv_v);
+    int32_t* idx = reinterpret_cast<int32_t*>(m.kv_idx);
+    if (!m.kv_v_valid) {
+        R3G_TRY(kvsel_vrows_launch(m.geoVt, Nl, Lkp, heads, vrows, s));
+        m.kv_v_valid = true;
+    }
+    m.kv_last_groups = 0;
+    R3G_TRY(kvsel_regroup_launch(Qp, heads, n, npad, G, gq, s));
+    R3G_TRY(kvsel_select_launch(Qp, n, npad, m.geoK, Nl, Lkp, heads, G, g_geo_kv_stride, k, idx, s));
+    R3G_TRY(kvsel_gather_launch(m.geoK, vrows, Nl, Lkp, heads, idx, cut.groups, k, kc, vtc, s));
+    if (cut.full) R3G_RC(attention(m, cut.full, heads, G, G, k, kpad, m.cat, W, (int64_t)G * W, kc, vtc, false, s, gq));
+    if (cut.tail) {
+        const int64_t kv_off = (int64_t)cut.full * heads * kpad * 64;
+        R3G_RC(attention(m, 1, heads, cut.tail, cut.tail_pad, k, kpad, m.cat + (int64_t)cut.full * G * W, W, 0, kc + kv_off, vtc + kv_off,
+                         false, s, gq + (int64_t)cut.full * heads * G * 64));
+    }
+    m.kv_last_groups = cut.groups;
+    m.kv_last_k = k;
+    m.kv_last_q = Qp; m.kv_last_n = n; m.kv_last_npad = npad;
+    g_geo_kv_groups += (int64_t)cut.groups * heads;
+    return R3G_OK;
+}
+
 // A pass takes its points either from the contiguous range [start, start + count) of the (R+1)^3 grid and writes their logits
 // to grid[start ...] (list == nullptr: the dense decoder), or from list[0 .. count) and writes them to grid[0 .. count) (the
 // hierarchical decoder's listed points; start is 0).  Everything between the Fourier features and the logits is the same
@@ -854,6 +923,9 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
     const int64_t total = (int64_t)(R + 1) * (R + 1) * (R + 1);
     if (start < 0 || count < 0 || start + count > total) return fail(R3G_ERR_INVALID, "grid_query: range outside the grid");
     if (list && start != 0) return fail(R3G_ERR_INVALID, "grid_query: listed points start at 0");
+    const int kv_k = kv_topk_for(Nl);
+    m.kv_last_q = nullptr;      // (r3g_kv_selection_operands: the rows it points to are about to be overwritten, or freed with the cache)
+    if (kv_k && g_geo_fp8) return fail(R3G_ERR_INVALID, "grid_query: top-k KV selection (option geo_kv_topk) is not available with option geo_fp8");
     const std::string g = "vae.geo_decoder";
     Lin lq, lcq, lproj, lfc, lfp;
     R3G_RC(get_lin(m, g + ".query_proj", true, &lq));
@@ -984,7 +1056,8 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
             else R3G_RC(gemm_qkv(m, m.xn, W, 0, lcq, 0, W, n, W, 1, q, QKV_Q_ONLY, s));
             if (canon) gq.built[(size_t)pidx] = 1;
         }
-        R3G_RC(attention(m, 1, heads, n, npad, Nl, Lkp, m.cat, W, 0, m.geoK, m.geoVt, true, s, Qp));
+        if (kv_k) R3G_RC(kv_attention(m, Qp, n, npad, kv_k, s));
+        else R3G_RC(attention(m, 1, heads, n, npad, Nl, Lkp, m.cat, W, 0, m.geoK, m.geoVt, true, s, Qp));
         {   // x1 = x0 + c_proj(attention): the old values come from the cached x0 where there is one
             GemmArgs pr = gemm_args(m.cat, W, 0, lproj, 0, W, m.f32a, W, 0, n, W, lnf ? (int)EPI_RESID_BF16_ST : epi_res, nullptr, 0);
             pr.lnd_part = m.lnd_part;
@@ -1099,6 +1172,8 @@ static void model_free(Model* m) {
     if (m->hier_grids) (void)hipFree(m->hier_grids);
     if (m->hier_idx) (void)hipFree(m->hier_idx);
     if (m->hier_val) (void)hipFree(m->hier_val);
+    for (char* p : {m->kv_q, m->kv_k, m->kv_vt, m->kv_idx, m->kv_v})
+        if (p) (void)hipFree(p);
     delete m;
 }
 
@@ -1331,6 +1406,7 @@ int r3g_get_counter(const char* name, int64_t* value) {
     else if (!strcmp(name, "dit_groups")) *value = g_dit_groups;
     else if (!strcmp(name, "dit_evals")) *value = g_dit_evals;
     else if (!strcmp(name, "geo_q_cache_builds")) *value = g_geo_q_cache_builds;
+    else if (!strcmp(name, "geo_kv_groups")) *value = g_geo_kv_groups;
     else return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
     return R3G_OK;
 }
@@ -1338,6 +1414,7 @@ int r3g_get_counter(const char* name, int64_t* value) {
 int r3g_model_trim(r3g_ctx* ctx) {
     NEED_MODEL("r3g_model_trim");
     Model::GeoCache& gq = m->gq;
+    m->kv_last_q = nullptr;
     if (gq.x0) {
         R3G_TRY(hipDeviceSynchronize());
         (void)hipFree(gq.x0);
@@ -1536,6 +1613,60 @@ int r3g_op_attention(const uint16_t* d_q, const uint16_t* d_k, const uint16_t* d
     return R3G_OK;
 }
 
+int r3g_op_kv_select(const uint16_t* d_q, int lq, int lq_pad, const uint16_t* d_k, int lk, int lk_pad, int heads, int group, int stride,
+                     int topk, int32_t* d_idx, void* stream) {
+    if (!d_q || !d_k || !d_idx) return fail(R3G_ERR_INVALID, "r3g_op_kv_select: null argument");
+    hipError_t e = kvsel_select_launch(d_q, lq, lq_pad, d_k, lk, lk_pad, heads, group, stride, topk, d_idx, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_kv_select (needs group % 256 == 0, stride >= 1, 1 <= topk <= lk <= 15360)");
+    return R3G_OK;
+}
+
+int r3g_op_kv_gather(const uint16_t* d_k, const uint16_t* d_vt, int lk, int lk_pad, int heads, const int32_t* d_idx, int groups, int topk,
+                     uint16_t* d_k_out, uint16_t* d_vt_out, void* stream) {
+    if (!d_k || !d_vt || !d_idx || !d_k_out || !d_vt_out || lk < 1 || heads < 1) return fail(R3G_ERR_INVALID, "r3g_op_kv_gather: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    uint16_t* v = nullptr;      // the row-major copy of V the model keeps per object: here per call (a test hook; synchronous)
+    R3G_TRY(hipMalloc((void**)&v, 2 * (size_t)heads * lk * 64));
+    hipError_t e = kvsel_vrows_launch(d_vt, lk, lk_pad, heads, v, s);
+    if (e == hipSuccess) e = kvsel_gather_launch(d_k, v, lk, lk_pad, heads, d_idx, groups, topk, d_k_out, d_vt_out, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    (void)hipFree(v);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_kv_gather");
+    if (e2 != hipSuccess) return hip_fail(e2, "r3g_op_kv_gather");
+    return R3G_OK;
+}
+
+int r3g_kv_selection_last(r3g_ctx* ctx, int32_t* d_idx, int64_t capacity, int* groups, int* heads, int* k, void* stream) {
+    NEED_MODEL("r3g_kv_selection_last");
+    if (!m->kv_last_groups) return fail(R3G_ERR_STATE, "r3g_kv_selection_last: no pass has been evaluated in top-k mode");
+    const int64_t count = (int64_t)m->kv_last_groups * m->Wh * m->kv_last_k;
+    if (groups) *groups = m->kv_last_groups;
+    if (heads) *heads = m->Wh;
+    if (k) *k = m->kv_last_k;
+    if (d_idx) {
+        if (capacity < count) return fail(R3G_ERR_INVALID, "r3g_kv_selection_last: the table has %lld entries, capacity %lld", (long long)count, (long long)capacity);
+        R3G_TRY(hipMemcpyAsync(d_idx, m->kv_idx, 4 * (size_t)count, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    return R3G_OK;
+}
+
+int r3g_kv_selection_operands(r3g_ctx* ctx, uint16_t* d_q, int64_t q_capacity, uint16_t* d_k, int64_t k_capacity, int* lq, int* lq_pad,
+                              int* lk, int* lk_pad, void* stream) {
+    NEED_MODEL("r3g_kv_selection_operands");
+    if (!m->kv_last_groups || !m->kv_last_q) return fail(R3G_ERR_STATE, "r3g_kv_selection_operands: no pass has been evaluated in top-k mode");
+    if (!m->have_z) return fail(R3G_ERR_STATE, "r3g_kv_selection_operands: r3g_vae_decode has not run");
+    const int Nl = m->c.vae_num_latents, Lkp = (int)rup(Nl, 64);
+    const int64_t qn = (int64_t)m->Wh * m->kv_last_npad * 64, kn = (int64_t)m->Wh * Lkp * 64;
+    if (lq) *lq = m->kv_last_n;
+    if (lq_pad) *lq_pad = m->kv_last_npad;
+    if (lk) *lk = Nl;
+    if (lk_pad) *lk_pad = Lkp;
+    if ((d_q && q_capacity < qn) || (d_k && k_capacity < kn)) return fail(R3G_ERR_INVALID, "r3g_kv_selection_operands: capacity too small");
+    if (d_q) R3G_TRY(hipMemcpyAsync(d_q, m->kv_last_q, 2 * (size_t)qn, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_k) R3G_TRY(hipMemcpyAsync(d_k, m->geoK, 2 * (size_t)kn, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return R3G_OK;
+}
+
 int r3g_prof_enable(int on) {
     prof_enable(on != 0);
     return R3G_OK;
@@ -1555,8 +1686,27 @@ int r3g_prof_read_bytes(double* bytes, int n) {
     return R3G_OK;
 }
 
+// the "geo_kv_*" options take validated values (a refused value leaves the setting as it was)
+static int kv_set_option(const char* what, int value) {
+    const std::string n = what;
+    if (n == "topk") {
+        if (value < -1) return fail(R3G_ERR_INVALID, "r3g_set_option: geo_kv_topk is 0 (exact), a key count, or -1 (upstream's rule)");
+        g_geo_kv_topk = value;
+    } else if (n == "group") {
+        if (value < 256 || value % 256) return fail(R3G_ERR_INVALID, "r3g_set_option: geo_kv_group must be a multiple of 256, at least 256");
+        g_geo_kv_group = value;
+    } else if (n == "stride") {
+        if (value < 1) return fail(R3G_ERR_INVALID, "r3g_set_option: geo_kv_stride must be at least 1");
+        g_geo_kv_stride = value;
+    } else {
+        return fail(R3G_ERR_INVALID, "r3g_set_option: unknown option 'geo_kv_%s'", what);
+    }
+    return R3G_OK;
+}
+
 int r3g_set_option(const char* name, int value) {
     if (!name) return fail(R3G_ERR_INVALID, "r3g_set_option: null name");
+    if (!strncmp(name, "geo_kv_", 7)) return kv_set_option(name + 7, value);     // (nothing cached depends on them: no new epoch)
     ++g_option_epoch;
     if (!strcmp(name, "fuse_qkv")) g_fuse_qkv = value != 0;
     else if (!strcmp(name, "batch_mods")) g_batch_mods = value != 0;

@@ -100,6 +100,17 @@ def volume_decoder_from_env():
     return v
 
 
+KV_SELECTIONS = ("exact", "topk")
+
+
+def kv_selection_from_env():
+    """R3G_KV_SELECTION = exact (default) | topk: the cross-attention of the geo decoder a pipeline starts with"""
+    v = os.environ.get("R3G_KV_SELECTION", "exact")
+    if v not in KV_SELECTIONS:
+        raise ValueError("R3G_KV_SELECTION=%r: expected one of %s" % (v, ", ".join(KV_SELECTIONS)))
+    return v
+
+
 class Hunyuan3DDiTPipeline:
     accepts_image_list = True     # `image` may be a list: its objects share the launches of the denoising loop
 
@@ -117,6 +128,12 @@ class Hunyuan3DDiTPipeline:
         self.hier_min_resolution = 63
         self.last_hier_stats = None
         self.mc_algo = "mc"                # surface extractor of a call that passes mc_algo=None: "mc" | "dmc"
+        # cross-attention of the geo decoder: "exact" | "topk" (adaptive top-k KV selection, DESIGN.md section 4d: an approximation,
+        # opt-in); kv_topk None = upstream's rule (1024 of 3072 keys), kv_group / kv_stride None = the library's 8192 / 64
+        self.kv_selection = kv_selection_from_env()
+        self.kv_topk = None
+        self.kv_group = None
+        self.kv_stride = None
 
     # The four places where this class touches the device.  (The API-contract test that runs the reference's stage
     # script on a machine without a GPU overrides the first three, all that the reference path reaches; the product has no CPU path.)
@@ -145,7 +162,7 @@ class Hunyuan3DDiTPipeline:
         config.yaml says `guidance_embed: true` (upstream's subfolders hunyuan3d-dit-v2-0-fast, hunyuan3d-dit-v2-0-turbo,
         hunyuan3d-dit-v2-mini-turbo) loads as a guidance-distilled model: no CFG batch, the turbo ones on the consistency
         scheduler their config names.  NOT covered: upstream's turbo VAE swap (enable_flashvdm(replace_vae=True) keeps the
-        snapshot's own VAE), top-k KV selection, guidance-distilled texture models."""
+        snapshot's own VAE), guidance-distilled texture models.  (Top-k KV selection: the attribute `kv_selection`.)"""
         if isinstance(model_path, str) and model_path.startswith("synthetic:"):
             parts = model_path.split(":")
             cfg = builtin_config(parts[1])
@@ -311,8 +328,11 @@ class Hunyuan3DDiTPipeline:
         """upstream's switch to its hierarchical volume decoder.  Here: `enabled` selects hierarchical volume decoding
         (r3g_grid_query_hier: a coarse grid densely, then only the points near the surface; defined in DESIGN.md, modelled on
         upstream's decoder but not pinned to it) and enable_flashvdm(False) restores the dense decoder.  `adaptive_kv_selection`,
-        `topk_mode` and `replace_vae` concern upstream's top-k KV selection and its VAE swap: accepted and ignored, NOT
-        implemented -- the cross-attention stays exact.  The surface extractor is NOT chosen here: mc_algo other than 'mc' is
+        `topk_mode` and `replace_vae` are accepted and IGNORED.  Top-k KV selection exists but is chosen
+        with the pipeline attribute `kv_selection = "topk"` (R3G_KV_SELECTION, stage key `r3g_kv_selection`), not here: this
+        signature is upstream's and its default is True, so honouring it would turn every enable_flashvdm() caller into an
+        approximation -- after this call the cross-attention is what `kv_selection` says, "exact" unless set.  The VAE swap is
+        not implemented.  The surface extractor is NOT chosen here: mc_algo other than 'mc' is
         refused; dual marching cubes is selected per call (`pipeline(image, mc_algo="dmc")`) or by the pipeline attribute
         `mc_algo` ("mc" | "dmc"), which a call that passes mc_algo=None uses."""
         if mc_algo not in (None, "mc"):
@@ -320,8 +340,27 @@ class Hunyuan3DDiTPipeline:
                                       "pipeline(image, mc_algo='dmc') or pipeline.mc_algo = 'dmc'")
         self.volume_decoder = "hierarchical" if enabled else "vanilla"
 
+    def _apply_kv_selection(self):
+        """hand `kv_selection` (and kv_topk / kv_group / kv_stride) to the model ahead of a grid query; timings["kv_selection"]
+        says what the query runs with"""
+        mode = getattr(self, "kv_selection", "exact")
+        if mode not in KV_SELECTIONS:
+            raise ValueError("kv_selection=%r: expected one of %s" % (mode, ", ".join(KV_SELECTIONS)))
+        if mode == "topk":
+            topk = getattr(self, "kv_topk", None)
+            kept = self.model.set_kv_selection(-1 if topk is None else topk, getattr(self, "kv_group", None),
+                                               getattr(self, "kv_stride", None))
+            self.timings["kv_selection"] = "topk:%d" % kept
+        else:
+            # (the library's options are process-wide: an exact pipeline switches off what a top-k one beside it left on)
+            reset = getattr(self.model, "set_kv_selection", None)
+            if reset is not None:
+                reset(0)
+            self.timings["kv_selection"] = "exact"
+
     def _query_grid(self, box_v, octree_resolution, mc_level):
         """the occupancy grid of the object whose latents the VAE has just decoded: always a full (R+1)^3 tensor"""
+        self._apply_kv_selection()
         n_dense = (octree_resolution + 1) ** 3
         if getattr(self, "volume_decoder", "vanilla") == "hierarchical":
             grid, stats = self.model.grid_query_hier(box_v, octree_resolution, mc_level, self.hier_band, self.hier_min_resolution)

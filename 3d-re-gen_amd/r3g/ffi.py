@@ -67,6 +67,8 @@ SYMBOLS = {
     "r3g_hier_merge": (_I, [_P, _P, _P, _P, _P]),
     "r3g_grid_query_points": (_I, [_P, _D, _I, _P, ctypes.c_int64, _P, _P]),
     "r3g_grid_query_hier": (_I, [_P, _D, _I, _D, _D, _I, _P, _I64P, _I, _P]),
+    "r3g_kv_selection_last": (_I, [_P, _P, ctypes.c_int64, _P, _P, _P, _P]),
+    "r3g_kv_selection_operands": (_I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "r3g_unet_create": (_I, [_P, _P]),
     "r3g_unet_set_tensor": (_I, [_P, ctypes.c_char_p, _P, _I, ctypes.c_int64, ctypes.c_int64]),
     "r3g_unet_resnet": (_I, [_P, ctypes.c_char_p, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -89,6 +91,8 @@ SYMBOLS = {
     "r3g_op_quant_fp8": (_I, [_P, ctypes.c_int64, _I, _I, _P, ctypes.c_int64, _P, _P]),
     "r3g_op_gemm_fp8": (_I, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _I, _I, _I, _I, _P]),
     "r3g_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "r3g_op_kv_select": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "r3g_op_kv_gather": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
     "r3g_set_staging": (_I, [_I]),
     "r3g_set_option": (_I, [ctypes.c_char_p, _I]),
     "r3g_get_counter": (_I, [ctypes.c_char_p, _P]),
@@ -155,7 +159,8 @@ def check(rc):
 
 
 def counter(name):
-    """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "dit_evals", "geo_q_cache_builds")"""
+    """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "dit_evals", "geo_q_cache_builds",
+    "geo_kv_groups")"""
     v = ctypes.c_int64(0)
     check(lib().r3g_get_counter(name.encode(), ctypes.byref(v)))
     return int(v.value)

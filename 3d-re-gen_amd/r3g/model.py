@@ -38,6 +38,20 @@ def make_config(cfg, grid_chunk=0):
     return m
 
 
+def kv_topk(topk, num_latents):
+    """keys the geo decoder keeps per (group, head) for option "geo_kv_topk" = topk (the library's rule, csrc/kvsel_kernels.h):
+    0 = exact attention; -1 = upstream's rule [UPSTREAM-RECALLED], 1024 of 3072 latents, 256 of 512, otherwise a third; k > 0 is
+    clamped to num_latents"""
+    topk, num_latents = int(topk), int(num_latents)
+    if topk < -1:
+        raise ValueError("kv_topk: topk is 0 (exact), a key count or -1 (upstream's rule), not %d" % topk)
+    if topk == 0:
+        return 0
+    if topk == -1:
+        topk = 1024 if num_latents == 3072 else 256 if num_latents == 512 else num_latents // 3
+    return max(1, min(topk, num_latents))
+
+
 def _pad_k(w):
     n, k = w.shape
     kp = (k + 63) // 64 * 64
@@ -260,6 +274,45 @@ class ShapeModel:
             _l.check(self.L.r3g_grid_query_points(self.ctx, float(bound), int(octree_resolution), idx.data_ptr() if idx.numel() else None,
                                                   int(idx.numel()), out.data_ptr() if idx.numel() else None, self._s()))
         return out
+
+    def set_kv_selection(self, topk=0, group=None, stride=None):
+        """adaptive top-k selection of the geo decoder's cross-attention keys (options "geo_kv_topk" /
+        "geo_kv_group" / "geo_kv_stride" of the library, which are process-wide): topk 0 = exact attention (the default), k > 0 =
+        keep k keys per group of `group` consecutive points and head (clamped to num_latents), -1 = upstream's rule (1024 of 3072,
+        256 of 512, otherwise a third).  group / stride None: left as they are (8192 / 64 unless set before).  A value outside its
+        range raises R3GError and changes nothing.  Returns the number of keys a grid query of this model will keep (0: exact)."""
+        if group is not None:
+            _l.check(self.L.r3g_set_option(b"geo_kv_group", int(group)))
+        if stride is not None:
+            _l.check(self.L.r3g_set_option(b"geo_kv_stride", int(stride)))
+        _l.check(self.L.r3g_set_option(b"geo_kv_topk", int(topk)))
+        return kv_topk(int(topk), self.num_latents)
+
+    def kv_selection_last(self):
+        """the index table of the last pass evaluated in top-k mode: int32 [groups, heads, k] on the device (ascending key indices
+        per group and head; a pass's tail group last).  R3GError (R3G_ERR_STATE) when no pass has run in top-k mode."""
+        self._activate()
+        g, h, k = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        with torch.cuda.device(self.device):
+            _l.check(self.L.r3g_kv_selection_last(self.ctx, None, 0, ctypes.byref(g), ctypes.byref(h), ctypes.byref(k), self._s()))
+            out = torch.empty((g.value, h.value, k.value), dtype=torch.int32, device=self.device)
+            _l.check(self.L.r3g_kv_selection_last(self.ctx, out.data_ptr(), out.numel(), None, None, None, self._s()))
+        return out
+
+    def kv_selection_operands(self):
+        """what kv_selection_last()'s table was selected from (r3g_kv_selection_operands): the pass's Q rows bf16 [heads, lq, 64]
+        as the attention kernel reads them and the object's K bf16 [heads, num_latents, 64].  Valid until the next grid query."""
+        self._activate()
+        n = [ctypes.c_int(0) for _ in range(4)]
+        with torch.cuda.device(self.device):
+            _l.check(self.L.r3g_kv_selection_operands(self.ctx, None, 0, None, 0, *[ctypes.byref(v) for v in n], self._s()))
+            lq, lq_pad, lk, lk_pad = (v.value for v in n)
+            heads = self.cfg["vae"]["heads"]
+            q = torch.empty((heads, lq_pad, 64), dtype=torch.bfloat16, device=self.device)
+            k = torch.empty((heads, lk_pad, 64), dtype=torch.bfloat16, device=self.device)
+            _l.check(self.L.r3g_kv_selection_operands(self.ctx, q.data_ptr(), q.numel(), k.data_ptr(), k.numel(), None, None, None,
+                                                      None, self._s()))
+        return q[:, :lq], k[:, :lk]
 
     def grid_query_hier(self, bound, octree_resolution, mc_level=0.0, band=0.95, min_resolution=63, out=None, stats=True):
         """hierarchical volume decoding (r3g_grid_query_hier): a full (R+1)^3 grid whose points near the surface hold the dense

@@ -205,6 +205,23 @@ def apply_mc_algo(config, shapegen):
     return shapegen
 
 
+def kv_selection(config):
+    """private key `r3g_kv_selection`: exact (default) | topk (adaptive top-k selection of the geo decoder's cross-attention keys,
+    DESIGN.md section 4d: an approximation).  None when the key is absent: the pipeline keeps its own `kv_selection`
+    (R3G_KV_SELECTION, default exact)."""
+    v = config.get("r3g_kv_selection")
+    if v is not None and v not in ("exact", "topk"):
+        raise ValueError("r3g_kv_selection: %r is not one of exact, topk" % (v,))
+    return v
+
+
+def apply_kv_selection(config, shapegen):
+    v = kv_selection(config)
+    if v is not None:
+        shapegen.kv_selection = v
+    return shapegen
+
+
 def shape_meshes(images, shapegen, config):
     """reference :77-84 for a group of images: the raw marching-cubes meshes, in order (None where extraction failed).
     Every object gets a generator seeded with cfg.seed, exactly as the reference seeds each of its calls (:82)."""
@@ -326,6 +343,7 @@ def run_rank(config, image_paths, output_folder, rank, world, factory, swallow_e
     shapegen, texgen, cleaners = factory(config, device)
     apply_volume_decoder(config, shapegen)
     apply_mc_algo(config, shapegen)
+    apply_kv_selection(config, shapegen)
     results = []
     todo = partition(len(image_paths), rank, world)
     B = objects_per_launch(config)
@@ -427,6 +445,7 @@ def run_distributed(config, input_folder, output_folder, rank, world, factory):
         shapegen, texgen, cleaners = factory(config, device)
         apply_volume_decoder(config, shapegen)
         apply_mc_algo(config, shapegen)
+        apply_kv_selection(config, shapegen)
         if wd is not None:
             wd.beat("models loaded")
 
@@ -507,6 +526,7 @@ def main(argv=None, factory=default_factory):
     args = ap.parse_args(argv)
     config = load_config(args.config)
     mc_algo(config)     # a bad r3g_mc_algo is refused before the output folder is cleared or a model is loaded
+    kv_selection(config)
     input_folder = config["input_folder_hy"]
     if config["use_banana"]:
         input_folder = config["prepped_for_hunyuan"]

@@ -255,7 +255,8 @@ int r3g_flow_sample_batch(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond
  *    result is bit-identical to its single-object run.
  *  - a partial set is R3G_ERR_STATE at the first call, naming the missing key.
  * r3g_dit_forward has no guidance input: on a distilled model it evaluates vec = time_in(timestep_embedding(t)) alone (the
- * per-block parity hook).  Not covered: upstream's turbo VAE swap, top-k KV selection, guidance-distilled texture models. */
+ * per-block parity hook).  Not covered: upstream's turbo VAE swap, guidance-distilled texture models.  (Top-k KV selection: the
+ * "geo_kv_*" options below r3g_grid_query_hier) */
 int r3g_flow_sample_sigmas(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond2, int n_objects, const float* sigmas,
                            int n_sigmas, float guidance_scale, int uncond_uniform, void* stream);
 
@@ -302,7 +303,11 @@ int r3g_grid_query(r3g_ctx* ctx, double bound, int octree_resolution, float* d_g
  *   are not all on one side of mc_level and not all active (their triangles rest on a filled value) --, then per level
  *   [4 + 2l] R_l and [5 + 2l] points evaluated.
  * Both grid entry points refuse the fp8 mode (option "geo_fp8" != 0) with R3G_ERR_INVALID: it is not covered by the bit-equality
- * tests of the listed-points path. */
+ * tests of the listed-points path.
+ * "The dense grid's bit for bit" holds for EXACT cross-attention (the default).  Under top-k KV selection (below) the keys a point
+ * attends to depend on the group of consecutive points it is evaluated with: the groups of a dense pass and of a list differ, so a
+ * listed point's logit is no longer the dense grid's, and the hierarchical decoder's grid is not the dense decoder's at the points
+ * it evaluates. */
 int r3g_hier_select(r3g_ctx* ctx, const float* d_coarse, int n_coarse, double level, double band, int is_finest, int64_t* count,
                     void* stream);
 int r3g_hier_indices(r3g_ctx* ctx, int32_t* d_idx_out, void* stream);
@@ -311,6 +316,30 @@ int r3g_grid_query_points(r3g_ctx* ctx, double bound, int octree_resolution, con
                           void* stream);
 int r3g_grid_query_hier(r3g_ctx* ctx, double bound, int octree_resolution, double mc_level, double band, int min_resolution,
                         float* d_grid, int64_t* stats, int n_stats, void* stream);
+
+/* ---- adaptive top-k KV selection in the geo decoder (upstream: FlashVDM's adaptive_kv_selection; opt-in, the default is exact) --
+ * [UPSTREAM-RECALLED], parity-unpinned; DEFINED in DESIGN.md section 4d.  An approximation: per group of `geo_kv_group` consecutive
+ * points of a pass (the evaluation order of r3g_grid_query / r3g_grid_query_points; the last group of a pass may be shorter) and
+ * per head, every key is scored by q-bar . k in fp32 -- q-bar the mean of the group's query rows r with r % geo_kv_stride == 0, the
+ * bf16 rows the attention kernel reads --, the k keys of largest score are kept (equal scores: the lower key index; NaN below
+ * every number) in ascending key index, and the group's attention runs over those keys only.  With k >= num_latents the selection
+ * is the identity and the logits equal the exact path's bit for bit.  Everything around the attention call, the query-side cache
+ * included, is unchanged.  The error against exact attention depends on how peaked the checkpoint's attention is: it is
+ * reported (tools/bench_kvsel.py, profiles/kvsel.md), not bounded.
+ * Options of r3g_set_option: "geo_kv_topk" (0 default: exact | k > 0: keys kept, clamped to num_latents | -1: upstream's rule, 1024
+ * of 3072, 256 of 512, otherwise num_latents / 3; below -1 refused), "geo_kv_group" (8192; a multiple of 256, at least 256, anything
+ * else is refused), "geo_kv_stride" (64; below 1 is refused).  A refused value is R3G_ERR_INVALID and changes nothing.  With option
+ * "geo_fp8" != 0 every grid query in top-k mode is R3G_ERR_INVALID.  Counter "geo_kv_groups": (group, head) selections so far.
+ * r3g_kv_selection_last: the index table int32 [groups][heads][k] of the LAST pass evaluated in top-k mode -> d_idx (capacity in
+ * entries; d_idx may be null to read the shape alone); groups in the pass's order, a tail group last.  R3G_ERR_STATE when there
+ * is none.
+ * r3g_kv_selection_operands: what that table was selected from -- the pass's Q rows bf16 [heads][lq_pad][64] (lq valid; q-normed,
+ * pre-scaled, as the attention kernel reads them) -> d_q and the object's K bf16 [heads][lk_pad][64] -> d_k (capacities in
+ * elements; either pointer may be null, the four shape outputs too).  Valid until the next grid query, r3g_vae_decode or
+ * r3g_model_trim.  For tests: r3g_op_kv_select on these operands reproduces the table. */
+int r3g_kv_selection_last(r3g_ctx* ctx, int32_t* d_idx, int64_t capacity, int* groups, int* heads, int* k, void* stream);
+int r3g_kv_selection_operands(r3g_ctx* ctx, uint16_t* d_q, int64_t q_capacity, uint16_t* d_k, int64_t k_capacity, int* lq, int* lq_pad,
+                              int* lk, int* lk_pad, void* stream);
 
 /* ---- texture stage: UNet blocks (first slice) -------------------------------------------
  * The two diffusion models behind upstream's Hunyuan3DPaintPipeline.__call__ (reference call site
@@ -452,6 +481,16 @@ int r3g_op_gemm_splitk(const uint16_t* d_a, int64_t lda, const uint16_t* d_w, in
  * the two middle 4-key blocks are swapped (key 8g+4h+e at position 8h+4g+e; python: r3g.layout.make_vt). */
 int r3g_op_attention(const uint16_t* d_q, const uint16_t* d_k, const uint16_t* d_vt, uint16_t* d_o, int batch, int heads,
                      int lq, int lq_pad, int lk, int lk_pad, int shared_kv, int use_lds_dma, void* stream);
+/* The two steps of top-k KV selection (above) on caller-owned operands.  kv_select: Q bf16 [heads][lq_pad][64], K bf16
+ * [heads][lk_pad][64] -> d_idx int32 [ceil(lq / group)][heads][topk], ascending per (group, head); 1 <= topk <= lk <= 15360.
+ * kv_gather: K as before, Vt bf16 [heads][64][lk_pad] in the attention kernel's key order (r3g_op_attention) -> d_k_out bf16
+ * [groups][heads][kpad][64] = K[idx] and d_vt_out bf16 [groups][heads][64][kpad] = the transposed V[idx] with compact key j at the
+ * kernel's position of j; kpad = topk rounded up to 64, padded keys zero: the operands of r3g_op_attention(batch = groups,
+ * shared_kv = 0).  kv_gather is synchronous (it makes its own row-major copy of V). */
+int r3g_op_kv_select(const uint16_t* d_q, int lq, int lq_pad, const uint16_t* d_k, int lk, int lk_pad, int heads, int group, int stride,
+                     int topk, int32_t* d_idx, void* stream);
+int r3g_op_kv_gather(const uint16_t* d_k, const uint16_t* d_vt, int lk, int lk_pad, int heads, const int32_t* d_idx, int groups, int topk,
+                     uint16_t* d_k_out, uint16_t* d_vt_out, void* stream);
 /* FP8 operands (BASELINE.json configs[3]).  quant_fp8: bf16 [rows][k] -> OCP e4m3 bytes [rows][k] + one fp32 scale per row
  * (amax / 448; round to nearest even, saturating).  gemm_fp8: C = epilogue((scale_a[m] scale_w[n]) sum_k a8[m][k] w8[n][k] +
  * bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the bf16 matrix rate); k % 256 == 0, lda / ldw in bytes and multiples
@@ -528,7 +567,8 @@ int r3g_prof_read_bytes(double* bytes, int n);
  * blocks' img + txt pair -- one tile per workgroup instead of the persistent phased kernel; with round 4's 32-row epilogue passes the
  * persistent form was 17 ms per object slower, with "gemm_epi_slices" it is 4 ms faster, profiles/r06_ab.md), "flow_first_step" / "flow_last_step" (0 / -1: r3g_flow_sample runs steps [first, last) of its schedule; consecutive
  * segments continuing on each other's latents are the same launches as one call -- how tests read the latents after 10, 20, ...
- * of 50 steps).  None of them changes a
+ * of 50 steps), "geo_kv_topk" / "geo_kv_group" / "geo_kv_stride" (0 / 8192 / 64: adaptive top-k KV selection in the geo decoder,
+ * described above r3g_kv_selection_last; values outside their ranges are refused).  None of them changes a
  * result bit, except fuse_qkv / batch_mods / cfg_dedup (different summation order, same function) and attn_generation
  * (different rounding points inside the softmax). */
 int r3g_set_option(const char* name, int value);
@@ -539,6 +579,7 @@ int r3g_set_option(const char* name, int value);
  * last step is skipped; N for an N-step consistency table; an fp32 re-run counts again).
  * "geo_q_cache_builds": allocations of the geo decoder's query-side cache so far (a change of (R, bound) frees and allocates it
  * again; r3g_grid_query_points and the coarse levels of r3g_grid_query_hier never do).
+ * "geo_kv_groups": (group, head) selections of top-k KV selection so far.
  * r3g_flow_sample_batch is SYNCHRONOUS while the guard is on (one 4-byte read-back per group) and must not be captured into a
  * hipGraph then; with "dit_f16_guard" 0 or "dit_resid_f16" 0 it only enqueues work.  Unknown name: R3G_ERR_INVALID. */
 int r3g_get_counter(const char* name, int64_t* value);
