@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/r3g.h"
+#include "geo_narrow.h"
 #include "kernels.h"
 #include "kvsel_kernels.h"
 #include "mesh_kernels.h"
@@ -78,6 +79,10 @@ static int g_flow_first_step = 0, g_flow_last_step = 1 << 30;
 // "geo_kv_stride"): 0 exact (default) | k > 0 keys kept per (group, head), clamped to num_latents | -1 upstream's rule
 static int g_geo_kv_topk = 0, g_geo_kv_group = 8192, g_geo_kv_stride = 64;
 static int64_t g_geo_kv_groups = 0;      // (group, head) selections made so far (r3g_get_counter "geo_kv_groups")
+// narrow geo decoder: option "geo_narrow_fused" -- everything behind the cross-attention of a decoder of width
+// 256 in one launch per pass (geo_narrow.hip) instead of the generic five
+static bool g_geo_narrow_fused = false;
+static int64_t g_geo_narrow_passes = 0;   // passes served by that kernel (r3g_get_counter "geo_narrow_passes")
 
 struct Model {
     r3g_model_config c{};
@@ -86,6 +91,11 @@ struct Model {
     // derived
     int T = 0, Tpad = 0, Lc = 0, Lcpad = 0, H = 0, Hd = 0, W = 0, Wh = 0, Hc = 0, Hch = 0, Fc = 0;
     int cin_pad = 0, qc = 0;
+    // the geo decoder's own width and head count: W / Wh unless the checkpoint carries a narrow decoder; read off
+    // vae.geo_decoder.query_proj.weight by geo_dims() at the start of every r3g_vae_decode / grid query
+    int Wg = 0, Hg = 0;
+    void* geo_tail_packed = nullptr;      // geo_tail_pack_launch's fragment stream (fused tail of a narrow decoder)
+    size_t geo_tail_packed_bytes = 0;
     // device buffers
     char* arena = nullptr;
     size_t arena_bytes = 0;
@@ -119,6 +129,7 @@ struct Model {
     float *fp8_sa = nullptr, *fp8_sconst = nullptr;
     uint16_t* lnf_w = nullptr;                       // ln_3 fold: bf16(c_fc.weight * ln_3.weight) [N][W]
     float *lnf_c = nullptr, *lnf_stats = nullptr;    //   c1 | c2 [2 N], (mean, rstd) per row of a pass [qc][2]
+    int lnf_n = 0, lnf_k = 0, lnd_w = 0;             // the shapes lnf_* / lnd_* were allocated for (a re-registered decoder may differ)
     float *lnd_gw = nullptr, *lnd_part = nullptr;   // EPI_RESID_BF16_LND: gamma * w [W] + 2 constants, chunk statistics [qc][W / 64][4]
     // activation arena of the grouped DiT engine for `cap_obj` objects and `cap_lat` latent blocks (= attention entries) per
     // launch (allocated on first use), and the segment tables of its fused QKV epilogues for `nb` objects of `epo` entries each
@@ -139,7 +150,7 @@ struct Model {
     // recomputing them (bit-identical by construction; -4 launches and ~36 TFLOP per object).  Built lazily pass by pass;
     // dropped when a weight is (re)registered, the grid changes, or the memory is not there (513^3 would need 557 GB).
     struct GeoCache {
-        int R = -1;
+        int R = -1, W = 0;                      // W: the decoder width the rows were laid out for
         double bound = 0.0;
         int64_t passes = 0;
         uint16_t *x0 = nullptr, *Q = nullptr;   // [passes][qc][W] each
@@ -339,12 +350,20 @@ static int build_mod_jobs(Model& m) {
     return R3G_OK;
 }
 
+// The joint sequence keeps the cond rows behind the latent rows: the DiT needs num_latents tile aligned.  (The VAE and the geo
+// decoder do not -- their padded keys are masked -- so the model itself is created for any count.)
+static int dit_latents_aligned(const Model& m) {
+    if (m.c.vae_num_latents % 64) return fail(R3G_ERR_INVALID, "the DiT needs num_latents to be a multiple of 64 (got %d)", m.c.vae_num_latents);
+    return R3G_OK;
+}
+
 static int dit_forward(Model& m, const float* x_in, const float* t_dev, float t_scalar, const uint16_t* cond, float* out,
                        int B, int n_double, int n_single, hipStream_t s) {
     const r3g_model_config& c = m.c;
     const int H = m.H, Nl = c.vae_num_latents, Lc = m.Lc, T = m.T, Tpad = m.Tpad, heads = m.Hd;
     const int64_t xs = (int64_t)Tpad * H;  // batch stride of the residual stream
     if (B < 1 || B > 2) return fail(R3G_ERR_INVALID, "dit_forward: batch %d not in [1,2]", B);
+    R3G_RC(dit_latents_aligned(m));
     Lin l;
     // latent_in / cond_in -> joint residual stream [latent | cond]
     R3G_TRY(cast_pad_launch(x_in, c.dit_in_channels, m.inb, m.cin_pad, B * Nl, c.dit_in_channels, m.cin_pad, 1.0f, s));
@@ -737,10 +756,32 @@ static int dit_forward_grouped(Model& m, const float* x_lat, float t_scalar, flo
     return R3G_OK;
 }
 
+// ---- the geo decoder's dimensions ------------------------------------------------------------------
+// r3g_model_config has no field for them: as with guidance_in, the tensors decide.  width_g = rows of query_proj.weight, heads_g =
+// width_g / 64; a decoder narrower than the VAE transformer needs latents_proj (width -> width_g) in front of its ln_2.
+static int geo_dims(Model& m) {
+    const char* name = "vae.geo_decoder.query_proj.weight";
+    const Tensor* t = m.find(name);
+    if (!t || t->dtype != 1) return fail(R3G_ERR_STATE, "missing bf16 weight '%s'", name);
+    const int64_t wg = t->rows;
+    if (wg < 64 || wg % 64) return fail(R3G_ERR_INVALID, "'%s' has %lld rows: the geo decoder's width must be a multiple of 64", name, (long long)wg);
+    if (wg > m.W) return fail(R3G_ERR_INVALID, "'%s' has %lld rows: the geo decoder cannot be wider than the VAE (width %d)", name, (long long)wg, m.W);
+    m.Wg = (int)wg;
+    m.Hg = (int)(wg / 64);
+    if (m.Wg != m.W) {
+        Lin l;
+        R3G_RC(get_lin(m, "vae.geo_decoder.latents_proj", true, &l));
+        if (l.N != m.Wg || l.K != m.W)
+            return fail(R3G_ERR_INVALID, "'vae.geo_decoder.latents_proj.weight' is [%d][%d], expected [%d][%d]", l.N, l.K, m.Wg, m.W);
+    }
+    return R3G_OK;
+}
+
 // ---- VAE transformer + geo-decoder K/V -------------------------------------------------------------
 static int vae_decode(Model& m, const float* latents, hipStream_t s) {
     const r3g_model_config& c = m.c;
     const int W = m.W, Nl = c.vae_num_latents, heads = m.Wh;
+    R3G_RC(geo_dims(m));
     Lin l;
     R3G_TRY(cast_pad_launch(latents, c.vae_embed_dim, m.inb, m.cin_pad, Nl, c.vae_embed_dim, m.cin_pad,
                             1.0f / c.vae_scale_factor, s));
@@ -779,22 +820,32 @@ static int vae_decode(Model& m, const float* latents, hipStream_t s) {
     }
     // geo decoder: K / V^T of the latents, computed ONCE (upstream recomputes c_kv for every query chunk)
     const std::string g = "vae.geo_decoder.cross_attn_decoder";
-    R3G_RC(get_vec(m, g + ".ln_2.weight", W, &lw));
-    R3G_RC(get_vec(m, g + ".ln_2.bias", W, &lb));
-    R3G_RC(layernorm(m.z, W, 0, m.xn, W, 0, Nl, 1, W, lw, lb, nullptr, nullptr, 0, 1e-6f, s));
+    const int Wg = m.Wg;
+    const float* zg = m.z;
+    if (Wg != W) {
+        // a narrow decoder: latents_proj (width -> width_g, with bias) on the transformer's output, BEFORE ln_2.  The bf16 operand
+        // goes through m.xn, the fp32 result lives in m.hid (idle between the transformer and the grid query)
+        R3G_RC(get_lin(m, "vae.geo_decoder.latents_proj", true, &l));
+        R3G_TRY(cast_pad_launch(m.z, W, m.xn, W, Nl, W, W, 1.0f, s));
+        R3G_RC(gemm(m.xn, W, 0, l, 0, Wg, m.hid, Wg, 0, Nl, W, EPI_F32, nullptr, 0, 1, s));
+        zg = reinterpret_cast<const float*>(m.hid);
+    }
+    R3G_RC(get_vec(m, g + ".ln_2.weight", Wg, &lw));
+    R3G_RC(get_vec(m, g + ".ln_2.bias", Wg, &lb));
+    R3G_RC(layernorm(zg, Wg, 0, m.xn, Wg, 0, Nl, 1, Wg, lw, lb, nullptr, nullptr, 0, 1e-6f, s));
     R3G_RC(get_lin(m, g + ".attn.c_kv", c.vae_qkv_bias != 0, &l));
     QkvSplitArgs q{};
-    q.src = m.qkv; q.ld = 2 * W; q.src_batch_stride = 0;
+    q.src = m.qkv; q.ld = 2 * Wg; q.src_batch_stride = 0;
     q.q_off = -1; q.k_off = 0; q.v_off = 64; q.head_stride = 128;  // per-head interleaved (k,v)
     q.Q = nullptr; q.K = m.geoK; q.Vt = m.geoVt; q.Lq_pad = 0; q.Lk_pad = (int)rup(Nl, 64); q.dst_row0 = 0;
-    q.B = 1; q.H = heads; q.L = Nl; q.eps = 1e-6f; q.q_scale = attn_q_scale(0.125f);
+    q.B = 1; q.H = m.Hg; q.L = Nl; q.eps = 1e-6f; q.q_scale = attn_q_scale(0.125f);
     const bool qkn = c.vae_qk_norm && c.vae_ln_post;
     q.norm = qkn ? QKN_LAYERNORM : QKN_NONE;
     if (qkn) {
         R3G_RC(get_vec(m, g + ".attn.attention.k_norm.weight", 64, &q.kw));
         R3G_RC(get_vec(m, g + ".attn.attention.k_norm.bias", 64, &q.kb));
     }
-    R3G_RC(gemm_qkv(m, m.xn, W, 0, l, 0, 2 * W, Nl, W, 1, q, QKV_HEAD_KV, s));
+    R3G_RC(gemm_qkv(m, m.xn, Wg, 0, l, 0, 2 * Wg, Nl, Wg, 1, q, QKV_HEAD_KV, s));
     m.have_z = true;
     m.kv_v_valid = false;
     return R3G_OK;
@@ -879,7 +930,7 @@ static int kv_topk_for(int num_latents) {
 // g_geo_kv_group rows; per (group, head) the k best keys are selected and gathered, and the groups run as the batches of one
 // attention launch with their own K / V^T (a shorter tail group as a second launch).  Output rows land in m.cat as in the exact path.
 static int kv_attention(Model& m, const uint16_t* Qp, int n, int npad, int k, hipStream_t s) {
-    const int W = m.W, Nl = m.c.vae_num_latents, heads = m.Wh, G = g_geo_kv_group, Lkp = (int)rup(Nl, 64), kpad = (int)rup(k, 64);
+    const int W = m.Wg, Nl = m.c.vae_num_latents, heads = m.Hg, G = g_geo_kv_group, Lkp = (int)rup(Nl, 64), kpad = (int)rup(k, 64);
     const KvselCut cut = kvsel_cut(n, G);
     R3G_RC(kv_grow(&m.kv_q, &m.kv_q_bytes, 2 * (size_t)kvsel_grouped_elems(n, G, heads), s, "grouped Q"));
     R3G_RC(kv_grow(&m.kv_k, &m.kv_k_bytes, 2 * (size_t)cut.groups * heads * kpad * 64, s, "compact K"));
@@ -919,7 +970,10 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
                       const int32_t* list = nullptr, bool cache = true) {
     const r3g_model_config& c = m.c;
     if (!m.have_z) return fail(R3G_ERR_STATE, "r3g_grid_query: r3g_vae_decode has not run");
-    const int W = m.W, Nl = c.vae_num_latents, heads = m.Wh;
+    R3G_RC(geo_dims(m));
+    const int W = m.Wg, Nl = c.vae_num_latents, heads = m.Hg;      // the decoder's own width and heads from here on
+    const bool narrow = W != m.W;
+    if (narrow && g_geo_fp8) return fail(R3G_ERR_INVALID, "grid_query: option geo_fp8 is not available with a narrow geo decoder (width %d of %d)", W, m.W);
     const int64_t total = (int64_t)(R + 1) * (R + 1) * (R + 1);
     if (start < 0 || count < 0 || start + count > total) return fail(R3G_ERR_INVALID, "grid_query: range outside the grid");
     if (list && start != 0) return fail(R3G_ERR_INVALID, "grid_query: listed points start at 0");
@@ -960,9 +1014,9 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
     Model::GeoCache& gq = m.gq;
     const int64_t passes_all = (total + m.qc - 1) / m.qc;
     bool use_cache = g_geo_q_cache && xb && !f8q && cache && !list;
-    if (use_cache && (gq.R != R || gq.bound != bound)) {
+    if (use_cache && (gq.R != R || gq.bound != bound || gq.W != W)) {
         if (gq.x0) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(gq.x0); gq.x0 = nullptr; gq.Q = nullptr; }
-        gq.R = R; gq.bound = bound; gq.passes = 0; gq.built.clear(); gq.refused = false;
+        gq.R = R; gq.bound = bound; gq.W = W; gq.passes = 0; gq.built.clear(); gq.refused = false;
     }
     // (no allocation for a call that contains no canonical pass, e.g. a test's 3 000-point slice of the grid)
     const bool has_canon = start % m.qc == 0 && count >= std::min<int64_t>(m.qc, total - start);
@@ -994,6 +1048,9 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
         std::fill(gq.built.begin(), gq.built.end(), 0);
         gq.epoch = g_option_epoch;
     }
+    // a narrow decoder of width 256: everything behind the attention in one launch per pass (geo_narrow.hip, option "geo_narrow_fused")
+    const bool tail = narrow && g_geo_narrow_fused && xb && !f8 && geo_tail_supported(W, lfc.N) && lproj.N == W && lproj.K == W &&
+                      lfc.K == W && lfp.N == W && lfp.K == lfc.N;
     // Round 6: ln_post + output_proj inside the last residual GEMM (EPI_RESID_BF16_LND): the final stream x2 is never written or
     // read again (2 x 268 MB per pass) and the ln_dot launch becomes a 33 MB merge of per-chunk statistics.  bf16 stream, bf16 MLP.
     const bool lnd = g_geo_lnd_fused && xb && !f8m && c.vae_ln_post && W % 256 == 0 && W <= 4096 && lfc.N % 128 == 0 && lfc.N >= 256;
@@ -1002,14 +1059,34 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
     // epilogue rstd (acc - mean c1) + c2 in front of its GELU (EPI_BF16_GELU_ERF_LNF) -- no LayerNorm launch, no normalised copy of the
     // stream (2 x 268 MB per pass).
     const bool lnf = g_geo_ln3_fold && xb && !f8m && W % 256 == 0 && W <= 4096 && lfc.N % 256 == 0;
-    if ((lnd || lnf) && !m.lnd_part) R3G_TRY(hipMalloc((void**)&m.lnd_part, 16 * (size_t)m.qc * (size_t)(W / 64)));
-    if (lnd) {
+    if ((lnd || lnf) && !tail && m.lnd_w < W) {
+        if (m.lnd_part || m.lnd_gw) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(m.lnd_part); (void)hipFree(m.lnd_gw); m.lnd_part = m.lnd_gw = nullptr; }
+        m.lnd_w = W;
+    }
+    if ((lnd || lnf) && !tail && !m.lnd_part) R3G_TRY(hipMalloc((void**)&m.lnd_part, 16 * (size_t)m.qc * (size_t)(W / 64)));
+    if (lnd && !tail) {
         if (!m.lnd_gw) R3G_TRY(hipMalloc((void**)&m.lnd_gw, 4 * (size_t)(W + 64)));
         R3G_TRY(lnd_prepare_launch(lpw, lpb, ow, ob, W, m.lnd_gw, m.lnd_gw + W, s));      // (per call: the weights may have been re-registered)
     }
+    if (tail) {
+        const size_t need = geo_tail_packed_bytes(lfc.N);
+        if (m.geo_tail_packed_bytes < need) {
+            if (m.geo_tail_packed) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(m.geo_tail_packed); m.geo_tail_packed = nullptr; m.geo_tail_packed_bytes = 0; }
+            R3G_TRY(hipMalloc(&m.geo_tail_packed, need));
+            m.geo_tail_packed_bytes = need;
+        }
+        // (per call: the weights may have been re-registered)
+        R3G_TRY(geo_tail_pack_launch(lproj.w, lproj.ldw, lfc.w, lfc.ldw, lfp.w, lfp.ldw, lfc.N, m.geo_tail_packed, s));
+    }
     Lin lfc2 = lfc;
-    if (lnf) {
+    if (lnf && !tail) {
+        if (m.lnf_w && (m.lnf_n != lfc.N || m.lnf_k != W)) {
+            R3G_TRY(hipStreamSynchronize(s));
+            (void)hipFree(m.lnf_w); (void)hipFree(m.lnf_c); (void)hipFree(m.lnf_stats);
+            m.lnf_w = nullptr; m.lnf_c = nullptr; m.lnf_stats = nullptr;
+        }
         if (!m.lnf_w) {
+            m.lnf_n = lfc.N; m.lnf_k = W;
             R3G_TRY(hipMalloc((void**)&m.lnf_w, 2 * (size_t)lfc.N * (size_t)W));
             R3G_TRY(hipMalloc((void**)&m.lnf_c, 4 * 2 * (size_t)lfc.N));
             R3G_TRY(hipMalloc((void**)&m.lnf_stats, 8 * (size_t)m.qc));
@@ -1058,6 +1135,18 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
         }
         if (kv_k) R3G_RC(kv_attention(m, Qp, n, npad, kv_k, s));
         else R3G_RC(attention(m, 1, heads, n, npad, Nl, Lkp, m.cat, W, 0, m.geoK, m.geoVt, true, s, Qp));
+        if (tail) {
+            GeoTailArgs ta{};
+            ta.cat = m.cat; ta.ld_cat = W;
+            ta.x0 = canon ? x0 : reinterpret_cast<const uint16_t*>(m.f32a); ta.ld_x0 = W;
+            ta.packed = m.geo_tail_packed;
+            ta.b_proj = lproj.b; ta.ln3_w = l3w; ta.ln3_b = l3b; ta.b_fc = lfc.b; ta.b_fp = lfp.b;
+            ta.lnp_w = lpw; ta.lnp_b = lpb; ta.out_w = ow; ta.out_b = ob;
+            ta.hidden = lfc.N; ta.n = n; ta.out = grid + start + off;
+            R3G_TRY(geo_tail_launch(ta, s));
+            ++g_geo_narrow_passes;
+            continue;
+        }
         {   // x1 = x0 + c_proj(attention): the old values come from the cached x0 where there is one
             GemmArgs pr = gemm_args(m.cat, W, 0, lproj, 0, W, m.f32a, W, 0, n, W, lnf ? (int)EPI_RESID_BF16_ST : epi_res, nullptr, 0);
             pr.lnd_part = m.lnd_part;
@@ -1169,6 +1258,7 @@ static void model_free(Model* m) {
     if (m->fp8_sconst) (void)hipFree(m->fp8_sconst);
     if (m->db.base) (void)hipFree(m->db.base);
     if (m->gq.x0) (void)hipFree(m->gq.x0);
+    if (m->geo_tail_packed) (void)hipFree(m->geo_tail_packed);
     if (m->hier_grids) (void)hipFree(m->hier_grids);
     if (m->hier_idx) (void)hipFree(m->hier_idx);
     if (m->hier_val) (void)hipFree(m->hier_val);
@@ -1194,7 +1284,7 @@ static int model_create(Ctx* ctx, const r3g_model_config* cfg) {
     auto bad = [&](const char* what) { model_free(m); return fail(R3G_ERR_INVALID, "r3g_model_create: %s", what); };
     if (m->H != 64 * m->Hd || m->W != 64 * m->Wh || m->Hc != 64 * m->Hch) return bad("every attention here needs head_dim == 64");
     if (m->H % 64 || m->W % 64 || m->Hc % 64 || m->Fc % 64 || c.dit_context_dim % 64) return bad("hidden sizes must be multiples of 64");
-    if (c.vae_num_latents % 64) return bad("num_latents must be a multiple of 64");
+    if (c.vae_num_latents < 1) return bad("num_latents must be positive");
     if (c.dit_context_dim != m->Hc) return bad("dit_context_dim must equal the conditioner hidden size");
     if (c.dit_in_channels != c.vae_embed_dim) return bad("dit_in_channels must equal vae_embed_dim");
     if (c.dit_in_channels % 4) return bad("in_channels must be a multiple of 4");
@@ -1309,6 +1399,7 @@ static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int 
     const int64_t n = (int64_t)c.vae_num_latents * c.dit_in_channels;
     const int64_t cond_elems = (int64_t)m->Lc * c.dit_context_dim;
     bool distilled = false;
+    R3G_RC(dit_latents_aligned(*m));
     R3G_RC(model_distilled(*m, &distilled));
     const bool dedup = g_cfg_dedup && uncond_uniform != 0;
     if (!dedup && !distilled) {
@@ -1407,6 +1498,7 @@ int r3g_get_counter(const char* name, int64_t* value) {
     else if (!strcmp(name, "dit_evals")) *value = g_dit_evals;
     else if (!strcmp(name, "geo_q_cache_builds")) *value = g_geo_q_cache_builds;
     else if (!strcmp(name, "geo_kv_groups")) *value = g_geo_kv_groups;
+    else if (!strcmp(name, "geo_narrow_passes")) *value = g_geo_narrow_passes;
     else return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
     return R3G_OK;
 }
@@ -1636,12 +1728,37 @@ int r3g_op_kv_gather(const uint16_t* d_k, const uint16_t* d_vt, int lk, int lk_p
     return R3G_OK;
 }
 
+int r3g_op_geo_tail(const uint16_t* d_cat, const uint16_t* d_x0, int n, int hidden, const uint16_t* d_w_proj, const float* d_b_proj,
+                    const float* d_ln3_w, const float* d_ln3_b, const uint16_t* d_w_fc, const float* d_b_fc, const uint16_t* d_w_fp,
+                    const float* d_b_fp, const float* d_lnpost_w, const float* d_lnpost_b, const float* d_out_w, float out_b, float* d_logits,
+                    void* stream) {
+    if (!d_cat || !d_x0 || !d_w_proj || !d_w_fc || !d_w_fp || !d_logits || n < 1 || !geo_tail_supported(GEO_TAIL_WIDTH, hidden))
+        return fail(R3G_ERR_INVALID, "r3g_op_geo_tail: bad argument (width 256, hidden 256 | 512 | 1024, n >= 1)");
+    hipStream_t s = (hipStream_t)stream;
+    void* packed = nullptr;      // the fragment stream the model keeps per grid query: here per call (a test hook; synchronous)
+    R3G_TRY(hipMalloc(&packed, geo_tail_packed_bytes(hidden)));
+    hipError_t e = geo_tail_pack_launch(d_w_proj, 256, d_w_fc, 256, d_w_fp, hidden, hidden, packed, s);
+    if (e == hipSuccess) {
+        GeoTailArgs ta{};
+        ta.cat = d_cat; ta.ld_cat = 256; ta.x0 = d_x0; ta.ld_x0 = 256; ta.packed = packed;
+        ta.b_proj = d_b_proj; ta.ln3_w = d_ln3_w; ta.ln3_b = d_ln3_b; ta.b_fc = d_b_fc; ta.b_fp = d_b_fp;
+        ta.lnp_w = d_lnpost_w; ta.lnp_b = d_lnpost_b; ta.out_w = d_out_w; ta.out_b = out_b;
+        ta.hidden = hidden; ta.n = n; ta.out = d_logits;
+        e = geo_tail_launch(ta, s);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);
+    (void)hipFree(packed);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_geo_tail");
+    if (e2 != hipSuccess) return hip_fail(e2, "r3g_op_geo_tail");
+    return R3G_OK;
+}
+
 int r3g_kv_selection_last(r3g_ctx* ctx, int32_t* d_idx, int64_t capacity, int* groups, int* heads, int* k, void* stream) {
     NEED_MODEL("r3g_kv_selection_last");
     if (!m->kv_last_groups) return fail(R3G_ERR_STATE, "r3g_kv_selection_last: no pass has been evaluated in top-k mode");
-    const int64_t count = (int64_t)m->kv_last_groups * m->Wh * m->kv_last_k;
+    const int64_t count = (int64_t)m->kv_last_groups * m->Hg * m->kv_last_k;
     if (groups) *groups = m->kv_last_groups;
-    if (heads) *heads = m->Wh;
+    if (heads) *heads = m->Hg;
     if (k) *k = m->kv_last_k;
     if (d_idx) {
         if (capacity < count) return fail(R3G_ERR_INVALID, "r3g_kv_selection_last: the table has %lld entries, capacity %lld", (long long)count, (long long)capacity);
@@ -1656,7 +1773,7 @@ int r3g_kv_selection_operands(r3g_ctx* ctx, uint16_t* d_q, int64_t q_capacity, u
     if (!m->kv_last_groups || !m->kv_last_q) return fail(R3G_ERR_STATE, "r3g_kv_selection_operands: no pass has been evaluated in top-k mode");
     if (!m->have_z) return fail(R3G_ERR_STATE, "r3g_kv_selection_operands: r3g_vae_decode has not run");
     const int Nl = m->c.vae_num_latents, Lkp = (int)rup(Nl, 64);
-    const int64_t qn = (int64_t)m->Wh * m->kv_last_npad * 64, kn = (int64_t)m->Wh * Lkp * 64;
+    const int64_t qn = (int64_t)m->Hg * m->kv_last_npad * 64, kn = (int64_t)m->Hg * Lkp * 64;
     if (lq) *lq = m->kv_last_n;
     if (lq_pad) *lq_pad = m->kv_last_npad;
     if (lk) *lk = Nl;
@@ -1707,6 +1824,7 @@ static int kv_set_option(const char* what, int value) {
 int r3g_set_option(const char* name, int value) {
     if (!name) return fail(R3G_ERR_INVALID, "r3g_set_option: null name");
     if (!strncmp(name, "geo_kv_", 7)) return kv_set_option(name + 7, value);     // (nothing cached depends on them: no new epoch)
+    if (!strcmp(name, "geo_narrow_fused")) { g_geo_narrow_fused = value != 0; return R3G_OK; }     // (behind the cached query side: no new epoch)
     ++g_option_epoch;
     if (!strcmp(name, "fuse_qkv")) g_fuse_qkv = value != 0;
     else if (!strcmp(name, "batch_mods")) g_batch_mods = value != 0;

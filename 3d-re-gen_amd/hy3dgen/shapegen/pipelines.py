@@ -69,6 +69,8 @@ def config_from_yaml(doc):
     for k in c["vae"]:
         if k in vp:
             c["vae"][k] = vp[k]
+    if "geo_decoder_downsample_ratio" in vp:       # upstream's turbo VAEs; absent = 1, and the key stays absent
+        c["vae"]["geo_decoder_downsample_ratio"] = int(vp["geo_decoder_downsample_ratio"])
     enc = doc.get("conditioner", {}).get("params", {}).get("main_image_encoder", {}).get("kwargs", {})
     for k in c["cond"]:
         if k in enc.get("config", {}):
@@ -161,8 +163,10 @@ class Hunyuan3DDiTPipeline:
         'synthetic:<full|mini|full-fast|full-turbo|mini-turbo>[:seed]' for seeded synthetic weights.  A snapshot whose
         config.yaml says `guidance_embed: true` (upstream's subfolders hunyuan3d-dit-v2-0-fast, hunyuan3d-dit-v2-0-turbo,
         hunyuan3d-dit-v2-mini-turbo) loads as a guidance-distilled model: no CFG batch, the turbo ones on the consistency
-        scheduler their config names.  NOT covered: upstream's turbo VAE swap (enable_flashvdm(replace_vae=True) keeps the
-        snapshot's own VAE), guidance-distilled texture models.  (Top-k KV selection: the attribute `kv_selection`.)"""
+        scheduler their config names.  A snapshot whose config.yaml says `geo_decoder_downsample_ratio: 4` loads with its narrow
+        geo decoder; upstream's turbo VAE swap is `replace_vae(...)` (enable_flashvdm(replace_vae=True) keeps
+        the snapshot's own VAE).  NOT covered: guidance-distilled texture models.  (Top-k KV selection: the attribute
+        `kv_selection`.)"""
         if isinstance(model_path, str) and model_path.startswith("synthetic:"):
             parts = model_path.split(":")
             cfg = builtin_config(parts[1])
@@ -328,17 +332,56 @@ class Hunyuan3DDiTPipeline:
         """upstream's switch to its hierarchical volume decoder.  Here: `enabled` selects hierarchical volume decoding
         (r3g_grid_query_hier: a coarse grid densely, then only the points near the surface; defined in DESIGN.md, modelled on
         upstream's decoder but not pinned to it) and enable_flashvdm(False) restores the dense decoder.  `adaptive_kv_selection`,
-        `topk_mode` and `replace_vae` are accepted and IGNORED.  Top-k KV selection exists but is chosen
+        `topk_mode` and `replace_vae` are accepted and IGNORED (the VAE swap is the method `replace_vae(model_path, ...)`, not this flag: its
+        default is True upstream, so honouring it would change the decoder of every enable_flashvdm() caller).  Top-k KV selection exists but is chosen
         with the pipeline attribute `kv_selection = "topk"` (R3G_KV_SELECTION, stage key `r3g_kv_selection`), not here: this
         signature is upstream's and its default is True, so honouring it would turn every enable_flashvdm() caller into an
-        approximation -- after this call the cross-attention is what `kv_selection` says, "exact" unless set.  The VAE swap is
-        not implemented.  The surface extractor is NOT chosen here: mc_algo other than 'mc' is
+        approximation -- after this call the cross-attention is what `kv_selection` says, "exact" unless set.  The surface extractor is NOT chosen here: mc_algo other than 'mc' is
         refused; dual marching cubes is selected per call (`pipeline(image, mc_algo="dmc")`) or by the pipeline attribute
         `mc_algo` ("mc" | "dmc"), which a call that passes mc_algo=None uses."""
         if mc_algo not in (None, "mc"):
             raise NotImplementedError("enable_flashvdm selects the volume decoder only: choose the surface extractor with "
                                       "pipeline(image, mc_algo='dmc') or pipeline.mc_algo = 'dmc'")
         self.volume_decoder = "hierarchical" if enabled else "vanilla"
+
+    def replace_vae(self, model_path, subfolder="hunyuan3d-vae-v2-0-turbo", variant="fp16", use_safetensors=True):
+        """upstream's turbo VAE swap (what its enable_flashvdm(replace_vae=True) does): replace the WHOLE VAE --
+        post_kl, transformer, geo decoder, scale_factor -- by the one under <model_path>/<subfolder>/ (config.yaml + model[.variant]
+        .safetensors | .ckpt, keys without prefix; upstream's subfolders hunyuan3d-vae-v2-0-turbo / hunyuan3d-vae-v2-mini-turbo), or
+        by 'synthetic:turbo-vae[:seed]': this pipeline's own VAE dims with geo_decoder_downsample_ratio 4, MLP expand ratio 1 and no
+        ln_post, seeded synthetic weights.  num_latents and embed_dim must equal the DiT's (ValueError).  The latents are then
+        divided by the new VAE's scale_factor; the DiT and the conditioner are untouched and not uploaded again; the query-side
+        cache is rebuilt on the next grid query.  timings["vae"] names what decodes."""
+        if isinstance(model_path, str) and model_path.startswith("synthetic:"):
+            parts = model_path.split(":")
+            if parts[1] != "turbo-vae":
+                raise KeyError("replace_vae: %r (the synthetic VAE is 'synthetic:turbo-vae[:seed]')" % model_path)
+            vcfg = _weights.turbo_vae_config(self.cfg["vae"])
+            sd = _weights.synthetic_vae_state_dict(vcfg, int(parts[2]) if len(parts) > 2 else 0, device=self.device)
+            name = model_path
+        else:
+            path = os.path.join(os.path.expanduser(model_path), subfolder)
+            if not os.path.isdir(path):
+                raise FileNotFoundError("VAE directory not found: %s (no network access: pass a local snapshot directory or "
+                                        "'synthetic:turbo-vae')" % path)
+            params, sd = _weights.load_vae_dir(path, variant, use_safetensors=use_safetensors)
+            vcfg = dict(self.cfg["vae"])
+            for k in list(vcfg) + ["geo_decoder_downsample_ratio"]:
+                if k in params:
+                    vcfg[k] = params[k]
+            if "geo_decoder_downsample_ratio" not in params:
+                vcfg.pop("geo_decoder_downsample_ratio", None)
+            name = path
+        self.replace_vae_tensors(vcfg, sd, name)
+
+    def replace_vae_tensors(self, vcfg, vae_state_dict, name="tensors"):
+        """replace_vae with the VAE given as (config, 'vae.'-prefixed state dict)"""
+        with self._device_ctx():
+            self.model.replace_vae(vcfg, vae_state_dict)
+        self.cfg = dict(self.cfg)
+        self.cfg["vae"] = dict(vcfg)
+        self.vae_name = name
+        self.timings["vae"] = name
 
     def _apply_kv_selection(self):
         """hand `kv_selection` (and kv_topk / kv_group / kv_stride) to the model ahead of a grid query; timings["kv_selection"]
@@ -378,6 +421,7 @@ class Hunyuan3DDiTPipeline:
         t0 = time.perf_counter()
         latents = self.generate_latents([image], num_inference_steps, guidance_scale, generator, sigmas=sigmas)[0]
         self.model.vae_decode(latents)
+        self.timings["vae"] = getattr(self, "vae_name", "checkpoint")
         grid = self._query_grid(box_v, octree_resolution, self.cfg["mc_level"] if mc_level is None else mc_level)
         self.timings["grid_s"] = time.perf_counter() - t0
         return grid, latents
@@ -428,6 +472,7 @@ class Hunyuan3DDiTPipeline:
                 t0 = time.perf_counter()
                 latents = self.generate_latents(list(image), num_inference_steps, g, generator, sigmas=sigmas)
                 out = []
+                self.timings["vae"] = getattr(self, "vae_name", "checkpoint")
                 for i in range(len(image)):
                     self.model.vae_decode(latents[i])
                     grid = self._query_grid(box_v, octree_resolution, mc_level)

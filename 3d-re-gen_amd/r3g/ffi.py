@@ -93,6 +93,7 @@ SYMBOLS = {
     "r3g_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "r3g_op_kv_select": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "r3g_op_kv_gather": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "r3g_op_geo_tail": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, _P, _P]),
     "r3g_set_staging": (_I, [_I]),
     "r3g_set_option": (_I, [ctypes.c_char_p, _I]),
     "r3g_get_counter": (_I, [ctypes.c_char_p, _P]),
@@ -160,7 +161,7 @@ def check(rc):
 
 def counter(name):
     """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "dit_evals", "geo_q_cache_builds",
-    "geo_kv_groups")"""
+    "geo_kv_groups", "geo_narrow_passes")"""
     v = ctypes.c_int64(0)
     check(lib().r3g_get_counter(name.encode(), ctypes.byref(v)))
     return int(v.value)

@@ -116,6 +116,22 @@ def check_guidance_keys(cfg, state_dict):
         raise ValueError("the checkpoint holds '%s' but the config does not say guidance_embed: true" % have[0])
 
 
+def check_geo_decoder_keys(cfg, state_dict):
+    """config and checkpoint must agree on the geo decoder's width: `geo_decoder_downsample_ratio` other than
+    1 needs vae.geo_decoder.latents_proj.{weight,bias} (the first missing one is named), and a checkpoint that holds either needs
+    the ratio -- the library decides by the tensors it is given (include/r3g.h r3g_vae_decode: the rows of query_proj.weight), so a
+    silent disagreement would change the decoder"""
+    from .weights import LATENTS_PROJ_KEYS, geo_decoder_ratio
+    have = [k for k in LATENTS_PROJ_KEYS if k in state_dict]
+    if geo_decoder_ratio(cfg["vae"]) != 1:
+        missing = [k for k in LATENTS_PROJ_KEYS if k not in state_dict]
+        if missing:
+            raise KeyError("narrow geo decoder (geo_decoder_downsample_ratio: %d): the checkpoint lacks '%s'"
+                           % (geo_decoder_ratio(cfg["vae"]), missing[0]))
+    elif have:
+        raise ValueError("the checkpoint holds '%s' but the config does not say geo_decoder_downsample_ratio" % have[0])
+
+
 class ShapeModel:
     """Weights + activation arena of one shape model on one GPU."""
 
@@ -123,6 +139,7 @@ class ShapeModel:
         if not torch.cuda.is_available():
             raise RuntimeError("r3g.ShapeModel needs an MI355X: libr3g has no CPU path")
         check_guidance_keys(cfg, state_dict)
+        check_geo_decoder_keys(cfg, state_dict)
         self.guidance_embed = bool(cfg["dit"].get("guidance_embed", False))
         self.cfg = cfg
         self.device = torch.device("cuda", device)
@@ -154,6 +171,36 @@ class ShapeModel:
         if not self.private_ctx:
             ShapeModel._current[self.device.index] = self
         self._have_z = False
+
+    def replace_vae(self, vcfg, vae_state_dict):
+        """swap the WHOLE VAE (post_kl, transformer, geo decoder, scale_factor) for another one: `vcfg` its config (the `vae` part
+        of a pipeline config), `vae_state_dict` its tensors under 'vae.'-prefixed names.  num_latents and embed_dim must equal the
+        DiT's.  Only the VAE's tensors are uploaded; the DiT's and the conditioner's stay where they are and are registered again
+        with the new model, whose arena and query-side cache are built afresh."""
+        from .weights import geo_decoder_ratio
+        old = self.cfg["vae"]
+        for k in ("num_latents", "embed_dim"):
+            if int(vcfg[k]) != int(old[k]):
+                raise ValueError("replace_vae: the new VAE has %s=%s, the DiT was trained on %s" % (k, vcfg[k], old[k]))
+        geo_decoder_ratio(vcfg)
+        extra = [k for k in vae_state_dict if not k.startswith("vae.")]
+        if extra:
+            raise ValueError("replace_vae: '%s' is not a VAE tensor" % extra[0])
+        cfg = dict(self.cfg)
+        cfg["vae"] = dict(vcfg)
+        check_geo_decoder_keys(cfg, vae_state_dict)
+        c = make_config(cfg, self._c.grid_chunk)
+        with torch.cuda.device(self.device):
+            w, scalars = prepare_weights(vae_state_dict, self.device)
+            if not self.private_ctx and ShapeModel._current.get(self.device.index) is self:
+                self.trim()                       # the old cache goes before the new arena comes
+            torch.cuda.synchronize()
+            self._w = {k: v for k, v in self._w.items() if not k.startswith("vae.")}
+            self._scalars = {k: v for k, v in self._scalars.items() if not k.startswith("vae.")}
+            self._w.update(w)
+            self._scalars.update(scalars)
+            self.cfg, self._c = cfg, c
+            self._install()
 
     def trim(self):
         """give the query-side cache of the geo decoder back to the device (r3g_model_trim); it is rebuilt on the next grid query"""
@@ -307,7 +354,8 @@ class ShapeModel:
         with torch.cuda.device(self.device):
             _l.check(self.L.r3g_kv_selection_operands(self.ctx, None, 0, None, 0, *[ctypes.byref(v) for v in n], self._s()))
             lq, lq_pad, lk, lk_pad = (v.value for v in n)
-            heads = self.cfg["vae"]["heads"]
+            from .weights import geo_decoder_ratio
+            heads = self.cfg["vae"]["heads"] // geo_decoder_ratio(self.cfg["vae"])
             q = torch.empty((heads, lq_pad, 64), dtype=torch.bfloat16, device=self.device)
             k = torch.empty((heads, lk_pad, 64), dtype=torch.bfloat16, device=self.device)
             _l.check(self.L.r3g_kv_selection_operands(self.ctx, q.data_ptr(), q.numel(), k.data_ptr(), k.numel(), None, None, None,

@@ -46,43 +46,11 @@ def param_shapes(cfg):
     lin("model.final_layer.linear", d["in_channels"], H)
     lin("model.final_layer.adaLN_modulation.1", 2 * H, H)
 
-    W, whd = v["width"], v["width"] // v["heads"]
-    lin("vae.post_kl", W, v["embed_dim"])
-
-    def qknorm(base):
-        if v["qk_norm"]:
-            for n in ("q_norm", "k_norm"):
-                s["%s.%s.weight" % (base, n)] = (whd,)
-                s["%s.%s.bias" % (base, n)] = (whd,)
+    _vae_shapes(v, lin, s)
 
     def ln(name, n):
         s[name + ".weight"] = (n,)
         s[name + ".bias"] = (n,)
-
-    for i in range(v["num_decoder_layers"]):
-        b = "vae.transformer.resblocks.%d" % i
-        lin(b + ".attn.c_qkv", 3 * W, W, v["qkv_bias"])
-        lin(b + ".attn.c_proj", W, W)
-        qknorm(b + ".attn.attention")
-        ln(b + ".ln_1", W)
-        lin(b + ".mlp.c_fc", 4 * W, W)
-        lin(b + ".mlp.c_proj", W, 4 * W)
-        ln(b + ".ln_2", W)
-    g = "vae.geo_decoder"
-    e = v.get("geo_decoder_mlp_expand_ratio", 4)
-    lin(g + ".query_proj", W, 3 * (2 * v["num_freqs"] + 1))
-    lin(g + ".cross_attn_decoder.attn.c_q", W, W, v["qkv_bias"])
-    lin(g + ".cross_attn_decoder.attn.c_kv", 2 * W, W, v["qkv_bias"])
-    lin(g + ".cross_attn_decoder.attn.c_proj", W, W)
-    if v.get("geo_decoder_ln_post", True):
-        qknorm(g + ".cross_attn_decoder.attn.attention")
-    for n in ("ln_1", "ln_2", "ln_3"):
-        ln(g + ".cross_attn_decoder." + n, W)
-    lin(g + ".cross_attn_decoder.mlp.c_fc", e * W, W)
-    lin(g + ".cross_attn_decoder.mlp.c_proj", W, e * W)
-    if v.get("geo_decoder_ln_post", True):
-        ln(g + ".ln_post", W)
-    lin(g + ".output_proj", 1, W)
 
     Hc, P = c["hidden_size"], c["image_size"] // c["patch_size"]
     F = swiglu_hidden(Hc, c["mlp_ratio"])
@@ -110,7 +78,96 @@ def param_shapes(cfg):
         # synthetic checkpoint equal the undistilled one of the same seed
         lin("model.guidance_in.in_layer", H, 256)
         lin("model.guidance_in.out_layer", H, H)
+    if geo_decoder_ratio(v) != 1:
+        # the turbo VAE's narrow geo decoder: latents_proj = Linear(width -> width_g), AFTER every other key for
+        # the same reason -- and only then, so that every checkpoint of ratio 1 keeps its keys, their order and its tensors
+        lin(LATENTS_PROJ, geo_decoder_width(v), v["width"])
     return s
+
+
+LATENTS_PROJ = "vae.geo_decoder.latents_proj"
+LATENTS_PROJ_KEYS = (LATENTS_PROJ + ".weight", LATENTS_PROJ + ".bias")
+
+
+def geo_decoder_ratio(v):
+    """`geo_decoder_downsample_ratio` of a VAE config (upstream's turbo VAEs: 4; absent = 1)"""
+    r = int(v.get("geo_decoder_downsample_ratio", 1))
+    if r < 1 or v["width"] % r or v["heads"] % r or (v["width"] // r) // (v["heads"] // r) != v["width"] // v["heads"]:
+        raise ValueError("geo_decoder_downsample_ratio=%r does not divide width %d / heads %d" % (r, v["width"], v["heads"]))
+    return r
+
+
+def geo_decoder_width(v):
+    """width_g = width // ratio (heads_g = heads // ratio: the head dimension stays)"""
+    return v["width"] // geo_decoder_ratio(v)
+
+
+def _vae_shapes(v, lin, s):
+    """the ShapeVAE's decoder-side parameters ('vae.' prefix) in checkpoint order, without latents_proj (param_shapes and
+    vae_param_shapes append it last).  The geo decoder is built at width_g = width // geo_decoder_downsample_ratio."""
+    W, whd = v["width"], v["width"] // v["heads"]
+    Wg = geo_decoder_width(v)
+    lin("vae.post_kl", W, v["embed_dim"])
+
+    def qknorm(base):
+        if v["qk_norm"]:
+            for n in ("q_norm", "k_norm"):
+                s["%s.%s.weight" % (base, n)] = (whd,)
+                s["%s.%s.bias" % (base, n)] = (whd,)
+
+    def ln(name, n):
+        s[name + ".weight"] = (n,)
+        s[name + ".bias"] = (n,)
+
+    for i in range(v["num_decoder_layers"]):
+        b = "vae.transformer.resblocks.%d" % i
+        lin(b + ".attn.c_qkv", 3 * W, W, v["qkv_bias"])
+        lin(b + ".attn.c_proj", W, W)
+        qknorm(b + ".attn.attention")
+        ln(b + ".ln_1", W)
+        lin(b + ".mlp.c_fc", 4 * W, W)
+        lin(b + ".mlp.c_proj", W, 4 * W)
+        ln(b + ".ln_2", W)
+    g = "vae.geo_decoder"
+    e = v.get("geo_decoder_mlp_expand_ratio", 4)
+    lin(g + ".query_proj", Wg, 3 * (2 * v["num_freqs"] + 1))
+    lin(g + ".cross_attn_decoder.attn.c_q", Wg, Wg, v["qkv_bias"])
+    lin(g + ".cross_attn_decoder.attn.c_kv", 2 * Wg, Wg, v["qkv_bias"])
+    lin(g + ".cross_attn_decoder.attn.c_proj", Wg, Wg)
+    if v.get("geo_decoder_ln_post", True):
+        qknorm(g + ".cross_attn_decoder.attn.attention")
+    for n in ("ln_1", "ln_2", "ln_3"):
+        ln(g + ".cross_attn_decoder." + n, Wg)
+    lin(g + ".cross_attn_decoder.mlp.c_fc", e * Wg, Wg)
+    lin(g + ".cross_attn_decoder.mlp.c_proj", Wg, e * Wg)
+    if v.get("geo_decoder_ln_post", True):
+        ln(g + ".ln_post", Wg)
+    lin(g + ".output_proj", 1, Wg)
+
+
+def vae_param_shapes(vcfg):
+    """name ('vae.' prefix) -> shape of a VAE-only checkpoint (upstream's hunyuan3d-vae-v2-0-turbo / -mini-turbo subfolders): the
+    decoder side of the ShapeVAE, latents_proj last when the geo decoder is narrow"""
+    s = {}
+
+    def lin(name, n, k, bias=True):
+        s[name + ".weight"] = (n, k)
+        if bias:
+            s[name + ".bias"] = (n,)
+
+    _vae_shapes(vcfg, lin, s)
+    if geo_decoder_ratio(vcfg) != 1:
+        lin(LATENTS_PROJ, geo_decoder_width(vcfg), vcfg["width"])
+    return s
+
+
+def turbo_vae_config(vcfg):
+    """the VAE config of 'synthetic:turbo-vae': `vcfg`'s own dims with upstream's turbo values [UPSTREAM-RECALLED] -- downsample
+    ratio 4, MLP expand ratio 1, no ln_post (hence no q/k norm in the decoder)"""
+    v = dict(vcfg)
+    v.update(geo_decoder_downsample_ratio=4, geo_decoder_mlp_expand_ratio=1, geo_decoder_ln_post=False)
+    geo_decoder_ratio(v)
+    return v
 
 
 GUIDANCE_KEYS = tuple("model.guidance_in.%s.%s" % (l, k) for l in ("in_layer", "out_layer") for k in ("weight", "bias"))
@@ -122,6 +179,13 @@ def _is_scale(name):
                 "norm1.", "norm2.", "q_norm.", "k_norm.", "ln_1.", "ln_2.", "ln_3.", "ln_post.", "layernorm."))))
 
 
+def synthetic_vae_state_dict(vcfg, seed=0, device="cuda"):
+    """seeded synthetic VAE-only checkpoint ('vae.'-prefixed names) at unit scale, drawn from its OWN generator in
+    vae_param_shapes order: it does not depend on what model it is swapped into"""
+    g = torch.Generator(device=device).manual_seed(seed)
+    return {name: _draw(name, shape, g, device, None) for name, shape in vae_param_shapes(vcfg).items()}
+
+
 def synthetic_state_dict(cfg, seed=0, device="cuda", std=None):
     """Seeded synthetic checkpoint generated on `device` (timing / plumbing).  Default: every layer at
     unit scale -- Linear ~ N(0, 1/fan_in), adaLN modulation layers ~ N(0, 9/fan_in) with bias N(0, 0.3^2), norm scales
@@ -131,25 +195,27 @@ def synthetic_state_dict(cfg, seed=0, device="cuda", std=None):
     g = torch.Generator(device=device).manual_seed(seed)
     sd = {}
     for name, shape in param_shapes(cfg).items():
-        is_mod = ".lin." in name or "adaLN" in name
-        emb = name.endswith(("cls_token", "mask_token", "position_embeddings"))
-        if _is_scale(name):
-            t = 1.0 + (0.1 if std is None else 0.05) * torch.randn(shape, generator=g, device=device)
-        elif emb:
-            t = (0.5 if std is None else std) * torch.randn(shape, generator=g, device=device)
-        elif len(shape) >= 2:
-            if std is None:
-                fan_in = 1
-                for d in shape[1:]:
-                    fan_in *= d
-                scale = (3.0 if is_mod else 1.0) / fan_in ** 0.5
-            else:
-                scale = 0.2 if "output_proj" in name else std
-            t = scale * torch.randn(shape, generator=g, device=device)
-        else:
-            t = ((0.3 if is_mod else 0.1) if std is None else 0.01) * torch.randn(shape, generator=g, device=device)
-        sd[name] = t
+        sd[name] = _draw(name, shape, g, device, std)
     return sd
+
+
+def _draw(name, shape, g, device, std):
+    is_mod = ".lin." in name or "adaLN" in name
+    emb = name.endswith(("cls_token", "mask_token", "position_embeddings"))
+    if _is_scale(name):
+        return 1.0 + (0.1 if std is None else 0.05) * torch.randn(shape, generator=g, device=device)
+    if emb:
+        return (0.5 if std is None else std) * torch.randn(shape, generator=g, device=device)
+    if len(shape) >= 2:
+        if std is None:
+            fan_in = 1
+            for d in shape[1:]:
+                fan_in *= d
+            scale = (3.0 if is_mod else 1.0) / fan_in ** 0.5
+        else:
+            scale = 0.2 if "output_proj" in name else std
+        return scale * torch.randn(shape, generator=g, device=device)
+    return ((0.3 if is_mod else 0.1) if std is None else 0.01) * torch.randn(shape, generator=g, device=device)
 
 
 def load_safetensors_dir(path, variant=None, use_safetensors=True):
@@ -190,3 +256,57 @@ def flatten_ckpt(ckpt):
     if not flat:
         raise ValueError("checkpoint holds no tensors under its top-level keys %s" % sorted(ckpt))
     return flat
+
+
+def _model_file(path, variant, use_safetensors):
+    stems = (["model.%s" % variant] if variant else []) + ["model", "model.fp16"]
+    exts = ([".safetensors"] if use_safetensors else []) + [".ckpt"]
+    for ext in exts:
+        for n in stems:
+            f = os.path.join(path, n + ext)
+            if os.path.exists(f):
+                return f
+    raise FileNotFoundError("no model*.safetensors / model*.ckpt under " + path)
+
+
+def vae_config_from_yaml(doc):
+    """the `params` of a VAE-only snapshot's config.yaml, written either as {params: ...} (upstream's own layout, beside `target`)
+    or as {vae: {params: ...}}"""
+    if not isinstance(doc, dict):
+        raise ValueError("VAE config.yaml is not a mapping")
+    node = doc["vae"] if isinstance(doc.get("vae"), dict) else doc
+    params = node.get("params")
+    if not isinstance(params, dict):
+        raise ValueError("VAE config.yaml has neither `params` nor `vae.params`")
+    return dict(params)
+
+
+def load_vae_dir(path, variant=None, use_safetensors=True):
+    """a VAE-only snapshot folder (upstream's hunyuan3d-vae-v2-0-turbo layout): <path>/config.yaml + model[.variant].safetensors or
+    .ckpt whose keys carry NO prefix (post_kl.weight, transformer.resblocks.0..., geo_decoder....) -> (params of config.yaml, state
+    dict with the 'vae.' prefix added).  The encoder side (encoder.*, pre_kl.*) is not used here and is dropped."""
+    import yaml
+    with open(os.path.join(path, "config.yaml")) as f:
+        params = vae_config_from_yaml(yaml.safe_load(f))
+    f = _model_file(path, variant, use_safetensors)
+    if f.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        raw = load_file(f)
+    else:
+        raw = torch.load(f, map_location="cpu", weights_only=True)
+        if isinstance(raw, dict) and isinstance(raw.get("state_dict"), dict):
+            raw = raw["state_dict"]
+        if isinstance(raw, dict) and isinstance(raw.get("vae"), dict):
+            raw = raw["vae"]
+    if not isinstance(raw, dict) or not raw:
+        raise ValueError("VAE checkpoint %s is not a state dict" % f)
+    sd = {}
+    for k, t in raw.items():
+        if not torch.is_tensor(t):
+            continue
+        if k.startswith("vae."):
+            k = k[4:]
+        if k.startswith(("encoder.", "pre_kl.")):
+            continue
+        sd["vae." + k] = t
+    return params, sd

@@ -22,7 +22,10 @@ What differs, by design (MI355X-first):
     full-fast | full-turbo | mini-turbo; without it the HF cache is consulted offline, as there is no network on the target machines;
   * private key `r3g_shape_variant: fast | turbo` selects upstream's guidance-distilled shape checkpoints (subfolders
     hunyuan3d-dit-v2-0-fast / -turbo, hunyuan3d-dit-v2-mini-turbo): no CFG batch, up to 8 crops per launch; absent = the
-    reference's models.  (Upstream's turbo VAE swap and guidance-distilled texture models are not covered.)
+    reference's models.  (Guidance-distilled texture models are not covered.)
+  * private key `r3g_turbo_vae: <snapshot dir | synthetic:turbo-vae[:seed]>` (or env R3G_TURBO_VAE) swaps upstream's turbo VAE in
+    after the shape model is loaded (`pipeline.replace_vae`); `r3g_turbo_vae_subfolder` names the folder
+    under the snapshot dir (default hunyuan3d-vae-v2-0-turbo).  Absent: the checkpoint's own VAE.
 """
 import argparse
 import json
@@ -222,6 +225,25 @@ def apply_kv_selection(config, shapegen):
     return shapegen
 
 
+def turbo_vae(config):
+    """private keys `r3g_turbo_vae` (env R3G_TURBO_VAE): a local snapshot directory or 'synthetic:turbo-vae[:seed]', and
+    `r3g_turbo_vae_subfolder` (default hunyuan3d-vae-v2-0-turbo) -> (path, subfolder), or None when neither is set: the
+    checkpoint's own VAE decodes"""
+    v = config.get("r3g_turbo_vae") or os.environ.get("R3G_TURBO_VAE")
+    if not v:
+        return None
+    if not isinstance(v, str):
+        raise ValueError("r3g_turbo_vae: %r is not a path or synthetic:turbo-vae" % (v,))
+    return v, str(config.get("r3g_turbo_vae_subfolder") or "hunyuan3d-vae-v2-0-turbo")
+
+
+def apply_turbo_vae(config, shapegen):
+    v = turbo_vae(config)
+    if v is not None:
+        shapegen.replace_vae(v[0], subfolder=v[1])
+    return shapegen
+
+
 def shape_meshes(images, shapegen, config):
     """reference :77-84 for a group of images: the raw marching-cubes meshes, in order (None where extraction failed).
     Every object gets a generator seeded with cfg.seed, exactly as the reference seeds each of its calls (:82)."""
@@ -344,6 +366,7 @@ def run_rank(config, image_paths, output_folder, rank, world, factory, swallow_e
     apply_volume_decoder(config, shapegen)
     apply_mc_algo(config, shapegen)
     apply_kv_selection(config, shapegen)
+    apply_turbo_vae(config, shapegen)
     results = []
     todo = partition(len(image_paths), rank, world)
     B = objects_per_launch(config)
@@ -446,6 +469,7 @@ def run_distributed(config, input_folder, output_folder, rank, world, factory):
         apply_volume_decoder(config, shapegen)
         apply_mc_algo(config, shapegen)
         apply_kv_selection(config, shapegen)
+        apply_turbo_vae(config, shapegen)
         if wd is not None:
             wd.beat("models loaded")
 
@@ -527,6 +551,7 @@ def main(argv=None, factory=default_factory):
     config = load_config(args.config)
     mc_algo(config)     # a bad r3g_mc_algo is refused before the output folder is cleared or a model is loaded
     kv_selection(config)
+    turbo_vae(config)
     input_folder = config["input_folder_hy"]
     if config["use_banana"]:
         input_folder = config["prepped_for_hunyuan"]

@@ -255,14 +255,22 @@ int r3g_flow_sample_batch(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond
  *    result is bit-identical to its single-object run.
  *  - a partial set is R3G_ERR_STATE at the first call, naming the missing key.
  * r3g_dit_forward has no guidance input: on a distilled model it evaluates vec = time_in(timestep_embedding(t)) alone (the
- * per-block parity hook).  Not covered: upstream's turbo VAE swap, guidance-distilled texture models.  (Top-k KV selection: the
- * "geo_kv_*" options below r3g_grid_query_hier) */
+ * per-block parity hook).  Not covered: guidance-distilled texture models.  (Top-k KV selection: the "geo_kv_*" options below
+ * r3g_grid_query_hier, DESIGN.md section 4d.  Upstream's turbo VAE: a narrow geo decoder, see r3g_vae_decode.) */
 int r3g_flow_sample_sigmas(r3g_ctx* ctx, float* d_latents, const uint16_t* d_cond2, int n_objects, const float* sigmas,
                            int n_sigmas, float guidance_scale, int uncond_uniform, void* stream);
 
 /* ShapeVAE.forward(latents / scale_factor) (post_kl + transformer) and the geo decoder's K/V of the
  * result (computed once; upstream recomputes them for every chunk).  d_z_out (optional) f32
- * [num_latents][width] receives the decoded latents. */
+ * [num_latents][width] receives the decoded latents.
+ * NARROW GEO DECODER (upstream's turbo VAE, geo_decoder_downsample_ratio; [UPSTREAM-RECALLED], DEFINED in DESIGN.md section 4e).
+ * r3g_model_config has no field for it: the registered tensors decide.  width_g = rows of "vae.geo_decoder.query_proj.weight",
+ * heads_g = width_g / 64, the MLP's hidden size = rows of its mlp.c_fc.weight.  width_g == vae_width is the ordinary decoder.
+ * Otherwise "vae.geo_decoder.latents_proj.{weight,bias}" ([width_g][vae_width], with bias) must be registered: it is applied to the
+ * transformer's output before the decoder's ln_2, and every tensor of the decoder has width_g where it had vae_width.  A width_g
+ * that is no multiple of 64 or exceeds vae_width is R3G_ERR_INVALID (the message names the tensor); a missing latents_proj is
+ * R3G_ERR_STATE.  r3g_grid_query, r3g_grid_query_points, r3g_grid_query_hier and top-k KV selection work unchanged on it; with
+ * option "geo_fp8" != 0 every grid query of a narrow decoder is R3G_ERR_INVALID. */
 int r3g_vae_decode(r3g_ctx* ctx, const float* d_latents, float* d_z_out, void* stream);
 
 /* VanillaVolumeDecoder: occupancy logits of dense grid points [start, start+count) of the (R+1)^3 grid
@@ -491,6 +499,15 @@ int r3g_op_kv_select(const uint16_t* d_q, int lq, int lq_pad, const uint16_t* d_
                      int topk, int32_t* d_idx, void* stream);
 int r3g_op_kv_gather(const uint16_t* d_k, const uint16_t* d_vt, int lk, int lk_pad, int heads, const int32_t* d_idx, int groups, int topk,
                      uint16_t* d_k_out, uint16_t* d_vt_out, void* stream);
+/* The fused tail of a narrow geo decoder of width 256 (csrc/geo_narrow.hip) on caller-owned operands: d_cat
+ * (the attention output) and d_x0 (the start of the residual stream) bf16 [n][256]; weights bf16 row-major d_w_proj [256][256],
+ * d_w_fc [hidden][256], d_w_fp [256][hidden], hidden 256 | 512 | 1024; biases and LayerNorm vectors f32; d_lnpost_w / d_lnpost_b
+ * both null: no ln_post.  d_logits f32 [n] = output_proj(ln_post(x1 + mlp(ln_3(x1)))), x1 = x0 + c_proj(cat).  Rows past n are
+ * neither read nor written.  Synchronous (it packs the weights into its own scratch buffer per call). */
+int r3g_op_geo_tail(const uint16_t* d_cat, const uint16_t* d_x0, int n, int hidden, const uint16_t* d_w_proj, const float* d_b_proj,
+                    const float* d_ln3_w, const float* d_ln3_b, const uint16_t* d_w_fc, const float* d_b_fc, const uint16_t* d_w_fp,
+                    const float* d_b_fp, const float* d_lnpost_w, const float* d_lnpost_b, const float* d_out_w, float out_b,
+                    float* d_logits, void* stream);
 /* FP8 operands (BASELINE.json configs[3]).  quant_fp8: bf16 [rows][k] -> OCP e4m3 bytes [rows][k] + one fp32 scale per row
  * (amax / 448; round to nearest even, saturating).  gemm_fp8: C = epilogue((scale_a[m] scale_w[n]) sum_k a8[m][k] w8[n][k] +
  * bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the bf16 matrix rate); k % 256 == 0, lda / ldw in bytes and multiples
@@ -568,7 +585,10 @@ int r3g_prof_read_bytes(double* bytes, int n);
  * persistent form was 17 ms per object slower, with "gemm_epi_slices" it is 4 ms faster, profiles/r06_ab.md), "flow_first_step" / "flow_last_step" (0 / -1: r3g_flow_sample runs steps [first, last) of its schedule; consecutive
  * segments continuing on each other's latents are the same launches as one call -- how tests read the latents after 10, 20, ...
  * of 50 steps), "geo_kv_topk" / "geo_kv_group" / "geo_kv_stride" (0 / 8192 / 64: adaptive top-k KV selection in the geo decoder,
- * described above r3g_kv_selection_last; values outside their ranges are refused).  None of them changes a
+ * described above r3g_kv_selection_last; values outside their ranges are refused), "geo_narrow_fused" (0 default; only a
+ * narrow geo decoder of width 256 with hidden 256 | 512 | 1024 on the bf16 stream is affected -- 1: everything behind its
+ * cross-attention, c_proj to output_proj, is one launch per pass (r3g_op_geo_tail's kernel) | 0: the generic launches; the same
+ * function with other rounding points; profiles/turbo_vae.md has the timing).  None of them changes a
  * result bit, except fuse_qkv / batch_mods / cfg_dedup (different summation order, same function) and attn_generation
  * (different rounding points inside the softmax). */
 int r3g_set_option(const char* name, int value);
@@ -580,6 +600,7 @@ int r3g_set_option(const char* name, int value);
  * "geo_q_cache_builds": allocations of the geo decoder's query-side cache so far (a change of (R, bound) frees and allocates it
  * again; r3g_grid_query_points and the coarse levels of r3g_grid_query_hier never do).
  * "geo_kv_groups": (group, head) selections of top-k KV selection so far.
+ * "geo_narrow_passes": grid passes served by the fused tail of a narrow geo decoder ("geo_narrow_fused") so far.
  * r3g_flow_sample_batch is SYNCHRONOUS while the guard is on (one 4-byte read-back per group) and must not be captured into a
  * hipGraph then; with "dit_f16_guard" 0 or "dit_resid_f16" 0 it only enqueues work.  Unknown name: R3G_ERR_INVALID. */
 int r3g_get_counter(const char* name, int64_t* value);
