@@ -5,7 +5,7 @@
 
 Each translation unit is compiled to build/<name>.o and linked into 3d-re-gen_amd/libr3g.so.
 mc_kernels.hip is compiled with -ffp-contract=off (its fp64 ambiguity tests and interpolation must
-reproduce the sequential reference bit-for-bit), dmc_kernels.hip likewise (its positions are fixed to the bit); the MFMA kernels keep hipcc's default contraction.
+reproduce the sequential reference bit-for-bit), dmc_kernels.hip likewise (its positions are fixed to the bit), and meshdist_kernels.hip (its distances equal the host twin's); the MFMA kernels keep hipcc's default contraction.
 hipcc cross-compiles without a GPU, so this also runs in the CPU-only build container.
 
 Staleness is decided by CONTENT, not by mtimes: build/manifest.json records, per object, the SHA-256 of its source,
@@ -29,7 +29,8 @@ MANIFEST = os.path.join(OBJ, "manifest.json")
 STAMP = os.path.join(HERE, "libr3g.digest")     # travels with the .so (the GPU box gets both)
 ARCH = "gfx950"
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-missing-braces", "-I" + INC, "-I" + CSRC]
-PER_FILE = {"mc_kernels.hip": ["-ffp-contract=off"], "dmc_kernels.hip": ["-ffp-contract=off"], "tex_kernels.hip": ["-ffp-contract=off"]}
+PER_FILE = {"mc_kernels.hip": ["-ffp-contract=off"], "dmc_kernels.hip": ["-ffp-contract=off"], "tex_kernels.hip": ["-ffp-contract=off"],
+            "meshdist_kernels.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -1,0 +1,281 @@
+// meshdist_core.h -- per-element bodies of the mesh-to-mesh distance (exact nearest-triangle query on a uniform grid).
+//
+// The contract: for a point p and a triangle mesh, dist2 = min over all usable faces t of
+// tri_dist2(p, t), face = the lowest face index attaining it.  tri_dist2 below IS the definition: one float32 function,
+// evaluated without contraction (-ffp-contract=off on both sides), so the host instantiation (tests/emu/meshdist_emu.cpp)
+// and the kernels (meshdist_kernels.hip) give identical bits.  The grid only prunes: the ring walk's stop rule carries a
+// slack that covers the rounding of tri_dist2 on faces it never visits, so the result does not depend on the resolution.
+#ifndef R3G_MESHDIST_CORE_H
+#define R3G_MESHDIST_CORE_H
+#include <stdint.h>
+
+#ifndef R3G_MD_HD
+#define R3G_MD_HD static inline
+#endif
+
+namespace r3g_md {
+
+constexpr int kMaxRes = 256;                          // cap: 256^3 = 2^24 cells
+constexpr int kPairMult = 8;                          // automatic resolution: halve while pairs > kPairMult * F
+constexpr float kBinMargin = 1.0f / 256.0f;           // cells; widens a triangle's cell range (rounding can only add cells)
+constexpr float kSlackRel = 1.0f / 262144.0f;         // 2^-18 of the squared ring bound
+constexpr float kSlackAbs = 1.0f / 262144.0f;         // 2^-18 of the squared distance to the farthest corner of the box
+constexpr float kInf = __builtin_huge_valf();
+constexpr int32_t kNoFace = 0x7fffffff;
+
+// one face, padded to 48 bytes: three 16-byte loads
+struct alignas(16) Tri {
+    float ax, ay, az;
+    int32_t valid;       // 0: out of the structure (non-finite vertex)
+    float bx, by, bz;
+    int32_t pad1;
+    float cx, cy, cz;
+    int32_t pad2;
+};
+
+struct Grid {
+    float lo[3];
+    float hi[3];
+    float h[3];          // cell size per axis
+    float inv[3];        // 1 / h: defines the cell coordinate t = (x - lo) * inv
+    int res;             // cells per axis
+};
+
+R3G_MD_HD bool finite(float x) { return (x - x) == 0.0f; }
+R3G_MD_HD float fmin2(float a, float b) { return b < a ? b : a; }
+R3G_MD_HD float fmax2(float a, float b) { return b > a ? b : a; }
+R3G_MD_HD float fabs1(float a) { return a < 0.0f ? -a : a; }
+
+// order-preserving float -> uint32 (bounding box by integer atomicMin / atomicMax) and back
+R3G_MD_HD uint32_t enc_float(float x) {
+    union { float f; uint32_t u; } c;
+    c.f = x;
+    return (c.u & 0x80000000u) ? ~c.u : (c.u | 0x80000000u);
+}
+R3G_MD_HD float dec_float(uint32_t u) {
+    union { float f; uint32_t u; } c;
+    c.u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return c.f;
+}
+
+// the NaN a non-finite query point gets: one bit pattern on host and device (inf - inf has the sign bit set on x86 only)
+R3G_MD_HD float quiet_nan() {
+    union { float f; uint32_t u; } c;
+    c.u = 0x7fc00000u;
+    return c.f;
+}
+
+// squared distance from the point with offset (apx, apy, apz) = p - a to the segment a + t * ab, t in [0, 1];
+// a == b gives the point distance
+R3G_MD_HD float seg_dist2(float apx, float apy, float apz, float abx, float aby, float abz) {
+    const float den = abx * abx + aby * aby + abz * abz;
+    const float num = apx * abx + apy * aby + apz * abz;
+    float t = den > 0.0f ? num / den : 0.0f;
+    t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+    const float qx = apx - t * abx, qy = apy - t * aby, qz = apz - t * abz;
+    return qx * qx + qy * qy + qz * qz;
+}
+
+// Squared distance from p to the closest point of triangle (a, b, c): the minimum over the three edges (which hold the
+// vertex and edge regions, and are all there is of a degenerate triangle) and, where p projects strictly inside, the
+// interior point of Ericson's barycentric form (Real-Time Collision Detection 5.1.5).  Every candidate is the distance to
+// a point OF the triangle, so the value never undershoots the true distance by more than its own rounding.
+R3G_MD_HD float tri_dist2(float px, float py, float pz, const Tri& t) {
+    const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az;
+    const float acx = t.cx - t.ax, acy = t.cy - t.ay, acz = t.cz - t.az;
+    const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
+    const float apx = px - t.ax, apy = py - t.ay, apz = pz - t.az;
+    const float bpx = px - t.bx, bpy = py - t.by, bpz = pz - t.bz;
+    const float cpx = px - t.cx, cpy = py - t.cy, cpz = pz - t.cz;
+    float best = seg_dist2(apx, apy, apz, abx, aby, abz);
+    best = fmin2(best, seg_dist2(bpx, bpy, bpz, bcx, bcy, bcz));
+    best = fmin2(best, seg_dist2(apx, apy, apz, acx, acy, acz));
+    const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
+    const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
+    const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    if (va > 0.0f && vb > 0.0f && vc > 0.0f) {
+        const float den = va + vb + vc;                      // > 0 here
+        const float v = vb / den, w = vc / den;              // v, w > 0 and v + w < 1: a point of the triangle
+        float qx = apx - v * abx - w * acx, qy = apy - v * aby - w * acy, qz = apz - v * abz - w * acz;
+        // One step of iterative refinement.  The barycentrics above come from products of dot products and lose a factor
+        // 1 / sin^2 of the smallest angle (marching cubes is full of slivers); the residual q is small, so solving the
+        // normal equations once more for it removes that.  Kept only while the point stays one of the triangle.
+        const float g11 = abx * abx + aby * aby + abz * abz, g12 = abx * acx + aby * acy + abz * acz;
+        const float g22 = acx * acx + acy * acy + acz * acz, det = g11 * g22 - g12 * g12;
+        if (det > 0.0f) {
+            const float e1 = abx * qx + aby * qy + abz * qz, e2 = acx * qx + acy * qy + acz * qz;
+            const float v2 = v + (g22 * e1 - g12 * e2) / det, w2 = w + (g11 * e2 - g12 * e1) / det;
+            if (v2 >= 0.0f && w2 >= 0.0f && v2 + w2 <= 1.0f)
+                qx = apx - v2 * abx - w2 * acx, qy = apy - v2 * aby - w2 * acy, qz = apz - v2 * abz - w2 * acz;
+        }
+        best = fmin2(best, qx * qx + qy * qy + qz * qz);
+    }
+    return best;
+}
+
+// (dist2, face) in lexicographic order: the order in which candidates arrive does not matter
+R3G_MD_HD void take(float d, int32_t f, float& best, int32_t& bface) {
+    if (d < best || (d == best && f < bface)) {
+        best = d;
+        bface = f;
+    }
+}
+
+R3G_MD_HD bool tri_finite(const Tri& t) {
+    return finite(t.ax) && finite(t.ay) && finite(t.az) && finite(t.bx) && finite(t.by) && finite(t.bz) && finite(t.cx) &&
+           finite(t.cy) && finite(t.cz);
+}
+
+// first resolution tried for F faces: a closed surface of F faces crosses ~3 R^2 cells, so R = sqrt(F / 2) leaves one to a
+// few triangles in an occupied cell
+R3G_MD_HD int initial_resolution(int64_t nf) {
+    int r = 1;
+    while (r < kMaxRes && (int64_t)(r + 1) * (r + 1) * 2 <= nf) ++r;
+    return r;
+}
+
+R3G_MD_HD Grid make_grid(const float lo[3], const float hi[3], int res) {
+    Grid g;
+    g.res = res;
+    float ext[3], maxext = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = lo[a];
+        g.hi[a] = hi[a];
+        ext[a] = hi[a] - lo[a];
+        maxext = fmax2(maxext, ext[a]);
+    }
+    for (int a = 0; a < 3; ++a) {
+        float h = ext[a] / (float)res;
+        if (!(h >= 1e-30f && h <= 1e30f)) h = maxext / (float)res;     // a flat axis: every face lands in its cell 0
+        if (!(h >= 1e-30f && h <= 1e30f)) h = 1.0f;
+        g.h[a] = h;
+        g.inv[a] = 1.0f / h;
+    }
+    return g;
+}
+
+R3G_MD_HD float cell_coord(const Grid& g, int a, float x) { return (x - g.lo[a]) * g.inv[a]; }
+
+// floor(t) clamped to [0, res - 1]; NaN -> 0
+R3G_MD_HD int cell_clamp(float t, int res) {
+    if (!(t > 0.0f)) return 0;
+    if (t >= (float)res) return res - 1;
+    return (int)t;
+}
+
+// the cells a triangle's axis-aligned box overlaps, widened by kBinMargin on both sides
+R3G_MD_HD void tri_range(const Grid& g, const Tri& t, int lo[3], int hi[3]) {
+    const float mn[3] = {fmin2(t.ax, fmin2(t.bx, t.cx)), fmin2(t.ay, fmin2(t.by, t.cy)), fmin2(t.az, fmin2(t.bz, t.cz))};
+    const float mx[3] = {fmax2(t.ax, fmax2(t.bx, t.cx)), fmax2(t.ay, fmax2(t.by, t.cy)), fmax2(t.az, fmax2(t.bz, t.cz))};
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = cell_clamp(cell_coord(g, a, mn[a]) - kBinMargin, g.res);
+        hi[a] = cell_clamp(cell_coord(g, a, mx[a]) + kBinMargin, g.res);
+    }
+}
+
+R3G_MD_HD int64_t tri_pairs(const Grid& g, const Tri& t) {
+    int lo[3], hi[3];
+    tri_range(g, t, lo, hi);
+    return (int64_t)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1);
+}
+
+R3G_MD_HD int cell_index(const Grid& g, int x, int y, int z) { return (z * g.res + y) * g.res + x; }
+
+R3G_MD_HD void visit_cell(const Tri* tris, const uint32_t* starts, const int32_t* pairs, int cell, float px, float py,
+                          float pz, float& best, int32_t& bface, uint32_t& ntests) {
+    const uint32_t e = starts[cell + 1];
+    for (uint32_t k = starts[cell]; k < e; ++k) {
+        const int32_t f = pairs[k];
+        take(tri_dist2(px, py, pz, tris[f]), f, best, bface);
+        ++ntests;
+    }
+}
+
+// distance along axis a from the point (cell coordinate tp) to cell k's slab [k, k + 1]
+R3G_MD_HD float cell_axis_dist(const Grid& g, int a, int k, float tp) {
+    const float d = fmax2((float)k - tp, tp - (float)(k + 1));
+    return d > 0.0f ? d * g.h[a] : 0.0f;
+}
+
+// true when a squared lower bound v, less the slack, still exceeds the best value: nothing behind it can win or tie
+R3G_MD_HD bool beyond(float v, float slack_abs, float best) { return v - (v * kSlackRel + slack_abs) > best; }
+
+// A cell is skipped when its own box is beyond the best value: a face's closest point lies in a cell that lists the face,
+// and that cell is no farther than the face, so the winner is always met in a cell that is not skipped.
+// The query of one point: Chebyshev rings of cells around the point's (clamped) cell.  After ring r every face not yet seen
+// has no cell inside the box [c - r, c + r], so on some axis its whole cell range lies beyond that box, past a face of the
+// box that is interior to the grid.  Its distance is at least the point's axis distance to that face; and since every face
+// lies inside the bounding box, on the other two axes it is at least as far as the point is outside the box (this keeps
+// points far outside from walking the whole grid).  The walk stops once the best value is below the smallest such bound
+// squared, less the slack.  Once the box of cells covers the grid nothing is left.
+R3G_MD_HD void nearest(const Grid& g, const Tri* tris, const uint32_t* starts, const int32_t* pairs, float px, float py,
+                       float pz, float* dist2_out, int32_t* face_out, uint32_t* ntests_out) {
+    if (!(finite(px) && finite(py) && finite(pz))) {
+        *dist2_out = quiet_nan();
+        *face_out = -1;
+        return;
+    }
+    const float p[3] = {px, py, pz};
+    const int R = g.res;
+    float tp[3], out2[3], far2 = 0.0f;
+    int c[3], rmax = 0;
+    for (int a = 0; a < 3; ++a) {
+        tp[a] = cell_coord(g, a, p[a]);
+        c[a] = cell_clamp(tp[a], R);
+        const int m = c[a] > R - 1 - c[a] ? c[a] : R - 1 - c[a];
+        rmax = m > rmax ? m : rmax;
+        const float f = fmax2(fabs1(p[a] - g.lo[a]), fabs1(p[a] - g.hi[a]));
+        far2 = far2 + f * f;
+        const float o = fmax2(0.0f, fmax2(g.lo[a] - p[a], p[a] - g.hi[a]));     // how far outside the box on this axis
+        out2[a] = o * o;
+    }
+    const float other2[3] = {out2[1] + out2[2], out2[0] + out2[2], out2[0] + out2[1]};
+    const float slack_abs = kSlackAbs * far2;
+    float best = kInf;
+    int32_t bface = kNoFace;
+    uint32_t ntests = 0;
+    for (int r = 0;; ++r) {
+        const int z0 = c[2] - r < 0 ? 0 : c[2] - r, z1 = c[2] + r > R - 1 ? R - 1 : c[2] + r;
+        const int y0 = c[1] - r < 0 ? 0 : c[1] - r, y1 = c[1] + r > R - 1 ? R - 1 : c[1] + r;
+        const int x0 = c[0] - r < 0 ? 0 : c[0] - r, x1 = c[0] + r > R - 1 ? R - 1 : c[0] + r;
+        for (int z = z0; z <= z1; ++z) {
+            const float dz = cell_axis_dist(g, 2, z, tp[2]);
+            for (int y = y0; y <= y1; ++y) {
+                const float dy = cell_axis_dist(g, 1, y, tp[1]);
+                const float yz2 = dz * dz + dy * dy;
+                if (beyond(yz2, slack_abs, best)) continue;
+                const bool shell = (z - c[2] == r) || (c[2] - z == r) || (y - c[1] == r) || (c[1] - y == r);
+                const int xa = shell ? x0 : c[0] - r, xb = shell ? x1 : c[0] + r;
+                const int step = shell ? 1 : 2 * r;             // inside the shell's z and y: only the two x faces (r > 0 there)
+                for (int x = xa; x <= xb; x += step) {
+                    if (x < 0 || x > R - 1) continue;
+                    const float dx = cell_axis_dist(g, 0, x, tp[0]);
+                    if (beyond(yz2 + dx * dx, slack_abs, best)) continue;
+                    visit_cell(tris, starts, pairs, cell_index(g, x, y, z), px, py, pz, best, bface, ntests);
+                }
+            }
+        }
+        if (r >= rmax) break;
+        float b2 = kInf;
+        for (int a = 0; a < 3; ++a) {
+            if (c[a] - r > 0) {
+                const float dt = tp[a] - (float)(c[a] - r);
+                const float d = dt > 0.0f ? dt * g.h[a] : 0.0f;
+                b2 = fmin2(b2, d * d + other2[a]);
+            }
+            if (c[a] + r < R - 1) {
+                const float dt = (float)(c[a] + r + 1) - tp[a];
+                const float d = dt > 0.0f ? dt * g.h[a] : 0.0f;
+                b2 = fmin2(b2, d * d + other2[a]);
+            }
+        }
+        if (beyond(b2, slack_abs, best)) break;
+    }
+    *dist2_out = best;
+    *face_out = bface == kNoFace ? -1 : bface;
+    if (ntests_out) *ntests_out = ntests;
+}
+
+}  // namespace r3g_md
+#endif

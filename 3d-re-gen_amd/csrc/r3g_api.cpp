@@ -136,6 +136,8 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->mc_ws) (void)hipFree(c->mc_ws);
     if (c->dmc_ws) (void)hipFree(c->dmc_ws);
     if (c->mesh_ws) (void)hipFree(c->mesh_ws);
+    if (c->meshdist_ws) (void)hipFree(c->meshdist_ws);
+    if (c->meshdist_pairs) (void)hipFree(c->meshdist_pairs);
     if (c->tex_ws) (void)hipFree(c->tex_ws);
     if (c->hier_ws) (void)hipFree(c->hier_ws);
     if (c->h_small) (void)hipHostFree(c->h_small);
@@ -318,6 +320,87 @@ int r3g_mesh_cluster_faces(r3g_ctx* ctx, float* d_verts, int64_t* n_verts, int32
     hipError_t e = mesh_cluster_faces(c->mesh_ws, c->mesh_ws_bytes, (unsigned*)c->h_small, d_verts, n_verts, d_faces,
                                       n_faces, max_faces, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "mesh_cluster_faces");
+}
+
+// ---- mesh distance ------------------------------------------------------------------------------------------------
+static int meshdist_small(Ctx* c, hipStream_t s, MeshdistSmall* out) {
+    hipError_t e = hipMemcpyAsync(c->h_small, c->meshdist_ws + c->meshdist_lay.off_small, sizeof(MeshdistSmall), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshdist)");
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshdist)");
+    memcpy(out, c->h_small, sizeof(MeshdistSmall));
+    return R3G_OK;
+}
+
+int r3g_meshdist_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces,
+                       int resolution, int* resolution_out, int64_t* pairs_out, int64_t* skipped_out, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshdist_build: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    c->meshdist_built = false;
+    if (n_verts < 0 || n_verts >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 30))
+        return fail(R3G_ERR_INVALID, "r3g_meshdist_build: mesh size out of range");
+    if (n_faces == 0) return fail(R3G_ERR_INVALID, "r3g_meshdist_build: the target mesh has no face");
+    if (!d_faces || (n_verts && !d_verts)) return fail(R3G_ERR_INVALID, "r3g_meshdist_build: null buffer");
+    if (resolution < 0 || resolution > r3g_md::kMaxRes)
+        return fail(R3G_ERR_INVALID, "r3g_meshdist_build: resolution outside [0, %d] (0 = automatic)", r3g_md::kMaxRes);
+    hipStream_t s = (hipStream_t)stream;
+    int res = resolution ? resolution : r3g_md::initial_resolution(n_faces);
+    MeshdistLayout lay;
+    int rc = c->reserve(&c->meshdist_ws, &c->meshdist_ws_bytes, meshdist_workspace_bytes(n_faces, res, &lay), "hipMalloc(meshdist workspace)");
+    if (rc) return rc;
+    c->meshdist_lay = lay;
+    hipError_t e = meshdist_records(c->meshdist_ws, lay, d_verts, n_verts, d_faces, n_faces, s);
+    if (e != hipSuccess) return hip_fail(e, "meshdist_records");
+    MeshdistSmall sm;
+    if ((rc = meshdist_small(c, s, &sm))) return rc;
+    // (-2 by the contract of include/r3g.h: found on the device, before anything is read through the index)
+    if (sm.bad_index) return fail(-2, "r3g_meshdist_build: a face index lies outside [0, %lld)", (long long)n_verts);
+    if ((int64_t)sm.skipped >= n_faces)
+        return fail(R3G_ERR_INVALID, "r3g_meshdist_build: every face has a non-finite vertex (%lld skipped)", (long long)sm.skipped);
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) lo[a] = r3g_md::dec_float(sm.box[a]), hi[a] = r3g_md::dec_float(sm.box[3 + a]);
+    r3g_md::Grid g;
+    int64_t pairs = 0;
+    for (;;) {
+        g = r3g_md::make_grid(lo, hi, res);
+        e = meshdist_count_pairs(c->meshdist_ws, lay, n_faces, g, s);
+        if (e != hipSuccess) return hip_fail(e, "meshdist_count_pairs");
+        if ((rc = meshdist_small(c, s, &sm))) return rc;
+        pairs = (int64_t)sm.pairs;
+        if (resolution || res == 1 || pairs <= r3g_md::kPairMult * n_faces) break;
+        res /= 2;       // e.g. one triangle that spans the box: R^3 pairs of its own
+    }
+    if (pairs >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshdist_build: %lld (face, cell) pairs at resolution %d; force a lower one", (long long)pairs, res);
+    rc = c->reserve(&c->meshdist_pairs, &c->meshdist_pairs_bytes, 4 * (size_t)pairs, "hipMalloc(meshdist pairs)");
+    if (rc) return rc;
+    e = meshdist_fill(c->meshdist_ws, lay, n_faces, g, (int32_t*)c->meshdist_pairs, s);
+    if (e != hipSuccess) return hip_fail(e, "meshdist_fill");
+    e = hipStreamSynchronize(s);      // the caller may free its mesh buffers, and a fault would surface here
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshdist_fill)");
+    c->meshdist_grid = g;
+    c->meshdist_built = true;
+    if (resolution_out) *resolution_out = res;
+    if (pairs_out) *pairs_out = pairs;
+    if (skipped_out) *skipped_out = (int64_t)sm.skipped;
+    return R3G_OK;
+}
+
+int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, float* d_dist2, int32_t* d_face, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshdist_query: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->meshdist_built) return fail(R3G_ERR_STATE, "r3g_meshdist_query: no successful r3g_meshdist_build on this context");
+    if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshdist_query: n_points out of range");
+    if (n_points == 0) return R3G_OK;
+    if (!d_points || !d_dist2 || !d_face) return fail(R3G_ERR_INVALID, "r3g_meshdist_query: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = meshdist_query(c->meshdist_ws, c->meshdist_lay, c->meshdist_grid, (const int32_t*)c->meshdist_pairs, d_points,
+                                  n_points, d_dist2, d_face, s);
+    if (e != hipSuccess) return hip_fail(e, "meshdist_query");
+    MeshdistSmall sm;
+    int rc = meshdist_small(c, s, &sm);
+    if (rc) return rc;
+    meshdist_add_tests((int64_t)sm.tests);
+    return R3G_OK;
 }
 
 // ---- texture stage ------------------------------------------------------------------------------------------------

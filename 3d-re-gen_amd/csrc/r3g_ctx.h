@@ -9,6 +9,7 @@
 #include "hier_kernels.h"
 #include "kernels.h"
 #include "mc_kernels.h"
+#include "meshdist_kernels.h"
 
 namespace r3g {
 
@@ -38,6 +39,14 @@ struct Ctx {
     // mesh cleaners
     char* mesh_ws = nullptr;
     size_t mesh_ws_bytes = 0;
+    // mesh distance: the grid of the last r3g_meshdist_build (records, CSR starts; the pair list has its own buffer)
+    char* meshdist_ws = nullptr;
+    size_t meshdist_ws_bytes = 0;
+    char* meshdist_pairs = nullptr;
+    size_t meshdist_pairs_bytes = 0;
+    MeshdistLayout meshdist_lay{};
+    r3g_md::Grid meshdist_grid{};
+    bool meshdist_built = false;
     // texture stage (z-buffer / inpainting workspace)
     char* tex_ws = nullptr;
     size_t tex_ws_bytes = 0;

@@ -138,6 +138,14 @@ class Mesh:
         v, f = meshops.reduce_faces(*self.device_buffers(), int(face_count))
         return Mesh.from_device(v, f, self.metadata)
 
+    def distance_to(self, other, **kw):
+        """Chamfer / Hausdorff / F-score between this mesh and `other` on the GPU: r3g.meshdist.compare on both meshes'
+        device buffers (keywords: samples, taus, include_vertices, resolution, seed) -> its dict"""
+        from . import meshdist
+        if self.is_empty or other.is_empty:
+            raise ValueError("Mesh.distance_to: an empty mesh has no distance")
+        return meshdist.compare(self.device_buffers(), other.device_buffers(), **kw)
+
     def process(self, validate=False):
         """merge bit-identical vertices (trimesh.Trimesh.process default), drop degenerate faces if validate"""
         if len(self.vertices):

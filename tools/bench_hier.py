@@ -126,6 +126,12 @@ def main():
         for k, fn in variants:
             ms[k].append(timed(fn))
     p_scopes, p_ms, p_bytes = planner_profile(m, L, R, 0.0, band)
+    dense_cached()                 # the error in space: the dense and the hierarchical grid through marching cubes
+    dense_grid = out.clone()
+    hierarchical()
+    from r3g import meshdist
+    mesh_distance = meshdist.grid_mesh_distance(dense_grid, out, 0.0, 1.01, R)
+    del dense_grid
 
     def summary(v):
         return {"median": statistics.median(v), "min": min(v), "max": max(v), "n": len(v)}
@@ -136,7 +142,7 @@ def main():
     print(json.dumps({
         "bench": "hier_decode", "field": a.field, "resolution": R, "band": band, "levels": stats["levels"],
         "evaluated_per_level": stats["evaluated_per_level"], "evaluated": stats["evaluated"], "dense_points": stats["dense_points"],
-        "f": stats["evaluated"] / stats["dense_points"], "unsafe_cells": stats["unsafe_cells"],
+        "f": stats["evaluated"] / stats["dense_points"], "unsafe_cells": stats["unsafe_cells"], "mesh_distance": mesh_distance,
         "ms": {k: summary(v) for k, v in ms.items()},
         "us_per_point_dense_uncached": us_dense, "us_per_point_hierarchical": us_hier,
         "per_point_ratio_hier_over_dense_uncached": us_hier / us_dense, "dense_uncached_spread": spread,

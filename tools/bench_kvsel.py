@@ -12,6 +12,7 @@ decoder) the two modes call by call.  Prints one JSON line per (decoder, mode):
   *_per_pass_us        the same per pass of the dense decoder
   max_abs_dlogit / mean_abs_dlogit     against the exact mode's grid of the same decoder, and the logits' scale
   sign_flip_share      share of grid points on the other side of mc_level than in the exact grid
+  mesh_distance        (top-k lines) both grids through marching cubes: chamfer_l1, hausdorff, p99, share within one voxel
 Nothing is asserted: the numbers go to profiles/kvsel.md.  Synthetic N(0, 0.02^2) weights give nearly uniform attention; the errors
 measured on them say nothing about a real snapshot.
 """
@@ -40,7 +41,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     from hy3dgen.shapegen import Hunyuan3DDiTFlowMatchingPipeline
-    from r3g import ffi
+    from r3g import ffi, meshdist
     pipe = Hunyuan3DDiTFlowMatchingPipeline.from_pretrained(a.model, device="cuda:0")
     m, L = pipe.model, ffi.lib()
     bound, level = pipe.cfg["box_v"], pipe.cfg["mc_level"]
@@ -104,6 +105,8 @@ def main():
                        "gather_ms": fam[mode][5] - fam["exact"][5],
                        "max_abs_dlogit": float(d.max()), "mean_abs_dlogit": float(d.mean()), "logit_scale": scale,
                        "sign_flip_share": float(flips), "options": os.environ.get("R3G_OPTIONS", "")}
+                if mode != "exact":       # the same error in space: both grids through marching cubes
+                    out["mesh_distance"] = meshdist.grid_mesh_distance(grids["exact"], grids[mode], level, bound, a.R)
                 if decoder == "dense":
                     for k in ("attention", "regroup", "select", "gather"):
                         out[k + "_per_pass_us"] = 1e3 * out[k + "_ms"] / passes

@@ -99,6 +99,12 @@ def part_a(a):
     def cache_gb(width):
         return passes * 131072 * width * 2 * 2 / 1e9
     med = {k: statistics.median(v) for k, v in ms.items()}
+    from r3g import meshdist
+    query(m_tur, 0)()              # the fused tail against the generic launches of the same decoder, as meshes
+    generic_grid = out.clone()
+    query(m_tur, 1)()
+    mesh_distance = dict(meshdist.grid_mesh_distance(generic_grid, out, 0.0, 1.01, R), between="B_turbo_generic / C_turbo_fused")
+    del generic_grid
     set_fused(0)
     for m in (m_std, m_tur):
         m.trim()
@@ -107,7 +113,7 @@ def part_a(a):
             "query_side_cache_gb": {"standard_width_1024": cache_gb(1024), "turbo_width_256": cache_gb(256)},
             "ratio_B_over_A": med["B_turbo_generic"] / med["A_standard"], "ratio_C_over_A": med["C_turbo_fused"] / med["A_standard"],
             "ratio_C_over_B": med["C_turbo_fused"] / med["B_turbo_generic"],
-            "fused_faster_than_generic": bool(med["C_turbo_fused"] < med["B_turbo_generic"])}
+            "fused_faster_than_generic": bool(med["C_turbo_fused"] < med["B_turbo_generic"]), "mesh_distance": mesh_distance}
 
 
 def part_b(a):
