@@ -1500,6 +1500,7 @@ int r3g_get_counter(const char* name, int64_t* value) {
     else if (!strcmp(name, "geo_kv_groups")) *value = g_geo_kv_groups;
     else if (!strcmp(name, "geo_narrow_passes")) *value = g_geo_narrow_passes;
     else if (!strcmp(name, "meshdist_tests")) *value = meshdist_tests_total();
+    else if (!strcmp(name, "meshinside_tests")) *value = meshinside_tests_total();
     else return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
     return R3G_OK;
 }

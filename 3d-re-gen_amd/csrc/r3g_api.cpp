@@ -138,6 +138,8 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->mesh_ws) (void)hipFree(c->mesh_ws);
     if (c->meshdist_ws) (void)hipFree(c->meshdist_ws);
     if (c->meshdist_pairs) (void)hipFree(c->meshdist_pairs);
+    if (c->meshinside_ws) (void)hipFree(c->meshinside_ws);
+    if (c->meshinside_pairs) (void)hipFree(c->meshinside_pairs);
     if (c->tex_ws) (void)hipFree(c->tex_ws);
     if (c->hier_ws) (void)hipFree(c->hier_ws);
     if (c->h_small) (void)hipHostFree(c->h_small);
@@ -400,6 +402,89 @@ int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, fl
     int rc = meshdist_small(c, s, &sm);
     if (rc) return rc;
     meshdist_add_tests((int64_t)sm.tests);
+    return R3G_OK;
+}
+
+// ---- point in mesh ------------------------------------------------------------------------------------------------
+static int meshinside_small(Ctx* c, hipStream_t s, MeshinsideSmall* out) {
+    hipError_t e = hipMemcpyAsync(c->h_small, c->meshinside_ws + c->meshinside_lay.off_small, sizeof(MeshinsideSmall), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshinside)");
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshinside)");
+    memcpy(out, c->h_small, sizeof(MeshinsideSmall));
+    return R3G_OK;
+}
+
+int r3g_meshinside_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces, int axis,
+                         int resolution, int* resolution_out, int64_t* pairs_out, int64_t* skipped_out, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    c->meshinside_built = false;
+    if (n_verts < 0 || n_verts >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 30))
+        return fail(R3G_ERR_INVALID, "r3g_meshinside_build: mesh size out of range");
+    if (n_faces == 0) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: the mesh has no face");
+    if (!d_faces || (n_verts && !d_verts)) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: null buffer");
+    if (axis < 0 || axis > 2) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: axis outside 0..2");
+    if (resolution < 0 || resolution > r3g_mi::kMaxRes)
+        return fail(R3G_ERR_INVALID, "r3g_meshinside_build: resolution outside [0, %d] (0 = automatic)", r3g_mi::kMaxRes);
+    hipStream_t s = (hipStream_t)stream;
+    int res = resolution ? resolution : r3g_mi::initial_resolution(n_faces);
+    MeshinsideLayout lay;
+    int rc = c->reserve(&c->meshinside_ws, &c->meshinside_ws_bytes, meshinside_workspace_bytes(n_faces, res, &lay), "hipMalloc(meshinside workspace)");
+    if (rc) return rc;
+    c->meshinside_lay = lay;
+    hipError_t e = meshinside_records(c->meshinside_ws, lay, d_verts, n_verts, d_faces, n_faces, axis, s);
+    if (e != hipSuccess) return hip_fail(e, "meshinside_records");
+    MeshinsideSmall sm;
+    if ((rc = meshinside_small(c, s, &sm))) return rc;
+    // (-2 by the contract of include/r3g.h: found on the device, before anything is read through the index)
+    if (sm.bad_index) return fail(-2, "r3g_meshinside_build: a face index lies outside [0, %lld)", (long long)n_verts);
+    if ((int64_t)sm.skipped >= n_faces)
+        return fail(R3G_ERR_INVALID, "r3g_meshinside_build: every face has a non-finite vertex (%lld skipped)", (long long)sm.skipped);
+    float lo[2], hi[2];
+    for (int a = 0; a < 2; ++a) lo[a] = r3g_mi::dec_float(sm.box[a]), hi[a] = r3g_mi::dec_float(sm.box[2 + a]);
+    r3g_mi::Grid2 g;
+    int64_t pairs = 0;
+    for (;;) {
+        g = r3g_mi::make_grid(lo, hi, res);
+        e = meshinside_count_pairs(c->meshinside_ws, lay, n_faces, g, s);
+        if (e != hipSuccess) return hip_fail(e, "meshinside_count_pairs");
+        if ((rc = meshinside_small(c, s, &sm))) return rc;
+        pairs = (int64_t)sm.pairs;
+        if (resolution || res == 1 || pairs <= r3g_mi::kPairMult * n_faces) break;
+        res /= 2;       // e.g. one face that spans the box: R^2 pairs of its own
+    }
+    if (pairs >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: %lld (face, column) pairs at resolution %d; force a lower one", (long long)pairs, res);
+    rc = c->reserve(&c->meshinside_pairs, &c->meshinside_pairs_bytes, 4 * (size_t)pairs, "hipMalloc(meshinside pairs)");
+    if (rc) return rc;
+    e = meshinside_fill(c->meshinside_ws, lay, n_faces, g, (int32_t*)c->meshinside_pairs, s);
+    if (e != hipSuccess) return hip_fail(e, "meshinside_fill");
+    e = hipStreamSynchronize(s);      // the caller may free its mesh buffers, and a fault would surface here
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshinside_fill)");
+    c->meshinside_grid = g;
+    c->meshinside_axis = axis;
+    c->meshinside_built = true;
+    if (resolution_out) *resolution_out = res;
+    if (pairs_out) *pairs_out = pairs;
+    if (skipped_out) *skipped_out = (int64_t)sm.skipped;
+    return R3G_OK;
+}
+
+int r3g_meshinside_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, int32_t* d_count, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshinside_query: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->meshinside_built) return fail(R3G_ERR_STATE, "r3g_meshinside_query: no successful r3g_meshinside_build on this context");
+    if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshinside_query: n_points out of range");
+    if (n_points == 0) return R3G_OK;
+    if (!d_points || !d_count) return fail(R3G_ERR_INVALID, "r3g_meshinside_query: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = meshinside_query(c->meshinside_ws, c->meshinside_lay, c->meshinside_grid, c->meshinside_axis,
+                                    (const int32_t*)c->meshinside_pairs, d_points, n_points, d_count, s);
+    if (e != hipSuccess) return hip_fail(e, "meshinside_query");
+    MeshinsideSmall sm;
+    int rc = meshinside_small(c, s, &sm);
+    if (rc) return rc;
+    meshinside_add_tests((int64_t)sm.tests);
     return R3G_OK;
 }
 

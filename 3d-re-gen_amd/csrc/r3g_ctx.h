@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "mc_kernels.h"
 #include "meshdist_kernels.h"
+#include "meshinside_kernels.h"
 
 namespace r3g {
 
@@ -47,6 +48,15 @@ struct Ctx {
     MeshdistLayout meshdist_lay{};
     r3g_md::Grid meshdist_grid{};
     bool meshdist_built = false;
+    // point in mesh: the columns of the last r3g_meshinside_build (separate from the distance grid: both may be held at once)
+    char* meshinside_ws = nullptr;
+    size_t meshinside_ws_bytes = 0;
+    char* meshinside_pairs = nullptr;
+    size_t meshinside_pairs_bytes = 0;
+    MeshinsideLayout meshinside_lay{};
+    r3g_mi::Grid2 meshinside_grid{};
+    int meshinside_axis = 0;
+    bool meshinside_built = false;
     // texture stage (z-buffer / inpainting workspace)
     char* tex_ws = nullptr;
     size_t tex_ws_bytes = 0;

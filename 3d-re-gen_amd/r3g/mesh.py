@@ -146,6 +146,42 @@ class Mesh:
             raise ValueError("Mesh.distance_to: an empty mesh has no distance")
         return meshdist.compare(self.device_buffers(), other.device_buffers(), **kw)
 
+    def _query_points(self, points, what):
+        """points as a CUDA float32 tensor on the mesh's device, and whether they came as a host array"""
+        import torch
+        if self.is_empty:
+            raise ValueError("Mesh.%s: an empty mesh has no inside" % what)
+        v, _ = self.device_buffers()
+        if torch.is_tensor(points):
+            return points.to(v.device, torch.float32).reshape(-1, 3), False
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(v.device), True
+
+    def contains(self, points, axes=(2,)):
+        """trimesh.Trimesh.contains: is each of points [N,3] inside the mesh?  r3g.meshinside.contains on the device buffers
+        (the parity of the ray-crossing count along axes[0], or the majority over three axes).  A numpy array (or anything
+        numpy converts) is uploaded and answered with a numpy bool array [N]; a torch tensor is answered with a CUDA tensor."""
+        from . import meshinside
+        p, host = self._query_points(points, "contains")
+        r = meshinside.contains(p, *self.device_buffers(), axes=axes)
+        inside = r if len(tuple(axes)) == 1 else r[0]
+        return inside.cpu().numpy() if host else inside
+
+    def signed_distance(self, points, axes=(2,)):
+        """r3g.meshinside.signed_distance of points [N,3] to this mesh -> float32 [N], NEGATIVE inside (the SDF convention;
+        trimesh.proximity.signed_distance is positive inside).  numpy in, numpy out; a torch tensor gives a CUDA tensor."""
+        from . import meshinside
+        p, host = self._query_points(points, "signed_distance")
+        sd, _ = meshinside.signed_distance(p, *self.device_buffers(), axes=axes)
+        return sd.cpu().numpy() if host else sd
+
+    def volume_iou(self, other, **kw):
+        """Volumetric IoU of this mesh and `other` on the GPU: r3g.meshinside.volume_iou on both meshes' device buffers
+        (keywords: n, axes) -> its dict"""
+        from . import meshinside
+        if self.is_empty or other.is_empty:
+            raise ValueError("Mesh.volume_iou: an empty mesh has no volume")
+        return meshinside.volume_iou(self.device_buffers(), other.device_buffers(), **kw)
+
     def process(self, validate=False):
         """merge bit-identical vertices (trimesh.Trimesh.process default), drop degenerate faces if validate"""
         if len(self.vertices):

@@ -189,7 +189,8 @@ def grid_mesh_distance(grid_exact, grid_approx, mc_level, box_v, octree_resoluti
     """The mesh-level error of an approximate grid of logits: both grids through marching cubes (r3g.mc.extract_mesh, the
     pipeline's extraction), then `compare` with tau = one voxel.  -> dict(chamfer_l1, hausdorff, p99 (the larger of the two
     directions), within_one_voxel (the smaller of the two shares), voxel, faces (exact, approx), query_ms), all lengths in
-    mesh units; dict(error=...) when a grid has no surface.  For the tools that time an opt-in approximation."""
+    mesh units; dict(error=...) when a grid has no surface.  For the tools that time an opt-in approximation.  These figures
+    are unsigned: on which side of the exact surface the approximation lies is r3g.meshinside.signed_distance's to say."""
     from . import mc
     try:
         a = mc.extract_mesh(grid_exact, mc_level, box_v, octree_resolution)

@@ -150,6 +150,36 @@ int r3g_meshdist_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, cons
                        int resolution, int* resolution_out, int64_t* pairs_out, int64_t* skipped_out, void* stream);
 int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, float* d_dist2, int32_t* d_face, void* stream);
 
+/* ---- point in mesh -------------------------------------------------------------------
+ * Ray-crossing count, the primitive under contains / signed distance / volumetric IoU (r3g/meshinside.py): on which side of
+ * a surface a point lies, which the unsigned distance above cannot tell.
+ *
+ * r3g_meshinside_build: take the mesh (d_verts float32 [n_verts][3], d_faces int32 [n_faces][3]) into a grid of R x R columns
+ *   over its bounding box projected along `axis` (0, 1, 2 = x, y, z: the direction of the rays), in CSR form, built on the
+ *   device (count, scan, fill).  resolution = columns per projected axis, 1..1024; 0 = automatic: floor(sqrt(n_faces)) capped
+ *   at 1024, halved while the grid holds more than 8 * n_faces (face, column) pairs.  Resolution 1 is brute force.
+ *   *resolution_out = the resolution used, *pairs_out = the pairs stored, *skipped_out = faces with a non-finite vertex (they
+ *   take part in nothing); each may be NULL.  Faces whose projection has zero area take part in nothing either and are not
+ *   counted as skipped.  The build copies what the query needs: the mesh buffers may be freed afterwards.  The grid is
+ *   separate from the one of r3g_meshdist_build: a context holds both at once.  Synchronises `stream`.  Errors: a face index
+ *   outside [0, n_verts) is found on the device before anything is read through it and fails the call with -2; axis outside
+ *   0..2, a resolution outside [0, 1024], n_faces == 0 or a mesh whose every face is skipped: R3G_ERR_INVALID.  A failed build
+ *   leaves the context without a grid.
+ * r3g_meshinside_query: for each of d_points float32 [n_points][3]
+ *       d_count[i] = the number of usable faces t with crossed(p_i, t)      (csrc/meshinside_core.h: float64 arithmetic on
+ *                    the float32 inputs, one operation per difference and product)
+ *   i.e. the faces the ray from p_i in the +axis direction crosses, against the grid of the last successful build on this
+ *   context (none: R3G_ERR_STATE).  p_i is inside when the count is odd.  A ray through a shared edge or vertex is decided by
+ *   one rule for both faces (E == 0 counts as the positive side of the edge's canonical direction), so a closed surface is
+ *   crossed once where it continues and twice or not at all where it folds back; a point exactly on a face is not below it.
+ *   A point with a non-finite coordinate gets -1.  The result is a pure function of the mesh, the axis and the points: it
+ *   depends neither on the resolution nor on the order in which the build's integer atomics land
+ *   (tests/emu/meshinside_emu.cpp reproduces it exactly on the host).  n_points == 0 is a no-op.  Synchronises `stream` (the
+ *   number of point-face tests is read back into the counter "meshinside_tests"). */
+int r3g_meshinside_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces,
+                         int axis, int resolution, int* resolution_out, int64_t* pairs_out, int64_t* skipped_out, void* stream);
+int r3g_meshinside_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, int32_t* d_count, void* stream);
+
 /* ---- texture stage: native pieces ------------------------------------------------------------
  * SURVEY.md 8(f) rank 3.  Upstream's Hunyuan3DPaintPipeline (reference call site src/2d_to_3d_models/run.py:97, built at
  * :126-128) uses two native extensions, `custom_rasterizer` (CUDA) and `mesh_processor.cpp`, and bakes the generated views
@@ -626,6 +656,7 @@ int r3g_set_option(const char* name, int value);
  * "geo_kv_groups": (group, head) selections of top-k KV selection so far.
  * "geo_narrow_passes": grid passes served by the fused tail of a narrow geo decoder ("geo_narrow_fused") so far.
  * "meshdist_tests": point-triangle tests made by r3g_meshdist_query so far.
+ * "meshinside_tests": point-face tests made by r3g_meshinside_query so far.
  * r3g_flow_sample_batch is SYNCHRONOUS while the guard is on (one 4-byte read-back per group) and must not be captured into a
  * hipGraph then; with "dit_f16_guard" 0 or "dit_resid_f16" 0 it only enqueues work.  Unknown name: R3G_ERR_INVALID. */
 int r3g_get_counter(const char* name, int64_t* value);
