@@ -16,6 +16,7 @@
 // 16-byte LDS-DMA with the bank swizzle on the source chunk index (same scheme as gemm.hip).
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -951,7 +952,7 @@ __global__ __launch_bounds__(NW * 64, (PIPE || NW == 8) ? 2 : 3) void attn2_kern
             for (int r = 0; r < 16; ++r) pe[r] = (ABL & 1) ? s[r] * 0.001f : __builtin_amdgcn_exp2f(s[r]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) pk[e] = pack_bf16(pe[2 * e], pe[2 * e + 1]);
-            {   // even / odd partial sums: packed fp32 adder, or (variant bit 1) plain adds in the same order
+            {   // even / odd partial sums on the packed fp32 adder
                 const float psum = sum16(pe);
                 l_run += psum;
                 if (kFast && !first_block) sticky |= __ballot(!(psum <= PSUM_LIMIT2)) & valid_lanes;
@@ -1683,6 +1684,21 @@ void attn_set_prio(int v) { if (v >= 0 && v <= 2) g_attn6_prio = v; }
 static int g_attn_stamps = 0;      // option "attn_stamps": generation 9 prints its per-phase s_memtime sums (timing experiments)
 void attn_set_stamps(int on) { g_attn_stamps = on; }
 
+bool attn_glds() { return g_attn_glds; }
+bool attn_get_option(const char* name, int* value) {
+    if (!strcmp(name, "attn_variant")) *value = g_attn_variant;
+    else if (!strcmp(name, "attn_interleave")) *value = g_attn_interleave;
+    else if (!strcmp(name, "attn_async_stage")) *value = g_attn_async_stage;
+    else if (!strcmp(name, "attn_pipelined")) *value = g_attn_pipelined ? 1 : 0;
+    else if (!strcmp(name, "attn_ablate")) *value = g_attn_ablate;
+    else if (!strcmp(name, "attn_generation")) *value = g_attn_gen;
+    else if (!strcmp(name, "attn_stamps")) *value = g_attn_stamps;
+    else if (!strcmp(name, "attn_prio")) *value = g_attn6_prio;
+    else if (!strcmp(name, "attn_wide_min")) *value = g_wide6_min_items;
+    else return false;
+    return true;
+}
+
 // (the first-generation kernels -- attn_generation 1 and the attn_pipelined option -- scale the scores themselves and
 // reject a pre-scaled Q: producers must then leave q plain)
 float attn_q_scale(float scale) { return (g_attn_gen >= 2 && !g_attn_pipelined) ? scale * 1.4426950408889634f : 1.0f; }
@@ -1719,6 +1735,7 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
         if (gen == 7) gen = (g_attn_glds && count(256) >= g_wide6_min_items) ? 6 : 2;
         const int qtile = (g_attn_glds && gen == 9) ? 384 : (g_attn_glds && gen >= 4) ? 256 : 128;
         const int items = count(qtile);
+        if (!g_attn_glds) launch_count(LC_ATTN_REGISTER_STAGED);
         if (gen == 9 && g_attn_glds) {     // phased 12-wave kernel (round 5): three groups, S1 | S2 | M
             const int prio = g_attn6_prio;
             auto launch6 = [&](auto ST, unsigned long long* d_st) -> hipError_t {
@@ -1731,6 +1748,7 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
                     (void)hipGetLastError();
                     return hipErrorNotSupported;
                 }
+                launch_count(LC_ATTN_GEN9);
                 hipLaunchKernelGGL(k, dim3(items), dim3(768), 4 * STAGE_B, s, p, d_st);
                 return hipGetLastError();
             };
@@ -1753,6 +1771,7 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
             return launch6(std::false_type{}, nullptr);
         }
         if (g_attn_ablate && gen == 2) {
+            launch_count(LC_ATTN_GEN2);
             switch (g_attn_ablate) {
 #define R3G_ABL2(m) case m: hipLaunchKernelGGL((attn2_kernel<true, false, 4, m>), dim3(items), dim3(256), 0, s, p); break;
                 R3G_ABL2(1) R3G_ABL2(4) R3G_ABL2(8) R3G_ABL2(12) R3G_ABL2(16) R3G_ABL2(48) R3G_ABL2(64) R3G_ABL2(128)
@@ -1762,6 +1781,7 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
             }
             return hipGetLastError();
         }
+        launch_count(!g_attn_glds ? LC_ATTN_GEN2 : gen == 3 ? LC_ATTN_GEN3 : gen == 4 ? LC_ATTN_GEN4 : gen == 5 ? LC_ATTN_GEN5 : gen == 6 ? LC_ATTN_GEN6 : LC_ATTN_GEN2);
         if (!g_attn_glds) hipLaunchKernelGGL((attn2_kernel<false, false, 4>), dim3(items), dim3(256), 0, s, p);
         else if (gen == 3) hipLaunchKernelGGL((attn2_kernel<true, true, 4>), dim3(items), dim3(256), 0, s, p);
         else if (gen == 4) hipLaunchKernelGGL((attn2_kernel<true, true, 8>), dim3(items), dim3(512), 0, s, p);
@@ -1785,6 +1805,8 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
     }
     if (p.q_prescaled) return hipErrorInvalidValue;   // the first-generation kernels scale the scores themselves
     dim3 grid(p.Lq_pad / 128, p.H, p.B);
+    launch_count(g_attn_pipelined ? LC_ATTN_PIPELINED : LC_ATTN_GEN1);
+    if (!g_attn_glds) launch_count(LC_ATTN_REGISTER_STAGED);
     if (g_attn_pipelined) {
         if (g_attn_glds) hipLaunchKernelGGL(attn_kernel_sp<true>, grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL(attn_kernel_sp<false>, grid, dim3(256), 0, s, p);

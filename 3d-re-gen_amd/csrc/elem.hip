@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "kernels.h"
 #include "prof.h"
@@ -666,6 +667,9 @@ inline int blocks_for(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
         /* the two combinations the path is made of, with their optional terms known at compile time (MODE) */            \
         const bool m_aff = g_ln_modes && p.w && p.b && !p.scale && !p.shift && !p.scale2 && !p.shift2 && !p.y8;            \
         const bool m_mod = g_ln_modes && !p.w && !p.b && p.scale && p.shift && !p.y8 && (p.seg2_row1 <= p.seg2_row0 || (p.scale2 && p.shift2)); \
+        launch_count(r4 ? LC_LN_ROWS4 : LC_LN_ROWS1);                                                                      \
+        if ((p.C == 1024 || p.C == 1536) && g_ln_fixed) launch_count(LC_LN_FIXED);                                         \
+        if (p.C == 1024 && g_ln_fixed && (m_mod || m_aff)) launch_count(LC_LN_MODE);                                       \
         if (p.C == 1024 && g_ln_fixed && m_mod) {                                                                          \
             if (r4) hipLaunchKernelGGL((layernorm_kernel<XB, 4, 4, 2>), g4, blk, 0, s, p);                                 \
             else hipLaunchKernelGGL((layernorm_kernel<XB, 4, 1, 2>), g1, blk, 0, s, p);                                    \
@@ -696,6 +700,14 @@ void ln_set_rows_per_wave(int rows) { g_ln_rows = rows == 1 || rows == 4 ? rows 
 // family 45.5 -> 46.8 ms per object, A/B twice on one box (profiles/r04_layernorm_rows.md) -- the option stays for the next try
 static int g_ln_rows4_min = 65536;
 void ln_set_rows4_min(int rows) { g_ln_rows4_min = rows > 0 ? rows : 65536; }
+bool ln_get_option(const char* name, int* value) {
+    if (!strcmp(name, "ln_rows")) *value = g_ln_rows;
+    else if (!strcmp(name, "ln_rows4_min")) *value = g_ln_rows4_min;
+    else if (!strcmp(name, "ln_fixed")) *value = g_ln_fixed ? 1 : 0;
+    else if (!strcmp(name, "ln_modes")) *value = g_ln_modes ? 1 : 0;
+    else return false;
+    return true;
+}
 static int ln_rows_per_wave(int rows) { return g_ln_rows ? g_ln_rows : (rows >= g_ln_rows4_min ? 4 : 1); }
 
 hipError_t layernorm_launch(const LnArgs& p, hipStream_t s) {
@@ -825,6 +837,8 @@ hipError_t fourier_points_launch(uint16_t* out, const int32_t* list, int count, 
 #define R3G_LNDOT_LAUNCH(XB)                                                                                               \
     {                                                                                                                      \
         const bool r4 = ln_rows_per_wave(rows) == 4;                                                                       \
+        launch_count(r4 ? LC_LN_ROWS4 : LC_LN_ROWS1);                                                                      \
+        if (C == 1024 && g_ln_fixed) launch_count(LC_LN_FIXED);                                                            \
         const dim3 g1((rows + 3) / 4), g4((rows + 15) / 16), blk(256);                                                     \
         if (C == 1024 && g_ln_fixed) {                                                                                     \
             if (r4) hipLaunchKernelGGL((ln_dot_kernel<XB, 4, 4>), g4, blk, 0, s, x, ldx, rows, C, do_ln, lnw, lnb, eps, w, b, out); \

@@ -19,6 +19,7 @@
 // Workgroup ids are remapped so that the 8 XCDs each own a contiguous run of tiles (L2 locality).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <map>
 #include <mutex>
@@ -2078,6 +2079,7 @@ hipError_t launch_gemm8p(const GemmArgs& p, const GemmArgs& p2, int num_cu, hipS
     }
     if (state < 0) { (void)hipGetLastError(); return hipErrorNotSupported; }
     const int walk = g_gemm_xcd_walk ? rounds : 0;
+    launch_count(EPI2 != EPI ? LC_GEMM_MIXED : LC_GEMM_PHASED_PERSISTENT);
     if (kSliceable && g_gemm_epi_slices && p.wide_epilogue) { hipLaunchKernelGGL(ks, dim3(grid), dim3(512), lds, s, p, p2, tiles, walk); }
     else { hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, p, p2, tiles, walk); }
     return hipGetLastError();
@@ -2094,6 +2096,7 @@ hipError_t launch_gemm8(const GemmArgs& p, const GemmArgs& p2, hipStream_t s) {
         done = true;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
+    launch_count(LC_GEMM_PHASED);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, s, p, p2, (float*)nullptr, (unsigned*)nullptr, 0u);
     return hipGetLastError();
 }
@@ -2135,6 +2138,7 @@ hipError_t launch_gemm8_split(const GemmArgs& p, const GemmArgs& p2, hipStream_t
         done = true;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
+    launch_count(LC_GEMM_SPLITK2);
     hipLaunchKernelGGL(k, dim3(2 * tiles), dim3(512), lds, s, p, p2, w.ws, w.flags, w.epoch);
     return hipGetLastError();
 }
@@ -2149,6 +2153,7 @@ hipError_t launch_deep(const GemmArgs& p, int batch, hipStream_t s) {
         done = true;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
+    launch_count(LC_GEMM_DEEP_RING);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, s, p);
     return hipGetLastError();
 }
@@ -2169,6 +2174,8 @@ hipError_t launch_cfg(const GemmArgs& p, const GemmArgs& p2, bool glds, hipStrea
             (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         }
     }
+    launch_count(BIG == 2 ? LC_GEMM_256X128 : BIG == 1 ? (NW == 16 ? LC_GEMM_W16_256 : LC_GEMM_TWO_STAGE_256) : (NW == 4 ? LC_GEMM_W4_128 : LC_GEMM_W8_128));
+    if (!glds) launch_count(LC_GEMM_REGISTER_STAGED);
     if (glds) {
         hipLaunchKernelGGL(kt, dim3(tiles), dim3(NW * 64), lds, s, p, p2);
     } else {
@@ -2241,6 +2248,7 @@ hipError_t launch_conv(const GemmArgs& p, hipStream_t s) {
         done = true;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
+    launch_count(LC_GEMM_CONV_IMPLICIT);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, s, p);
     return hipGetLastError();
 }
@@ -2327,8 +2335,19 @@ hipError_t launch_epi(const GemmArgs& p, const GemmArgs& p2, bool glds, hipStrea
 
 }  // namespace
 
+std::atomic<int64_t> g_launch_counters[LC_COUNT];
+const char* launch_counter_name(int which) {
+    static const char* const names[LC_COUNT] = {
+        "gemm_w4_128", "gemm_w8_128", "gemm_w16_256", "gemm_two_stage_256", "gemm_256x128", "gemm_phased", "gemm_phased_persistent",
+        "gemm_mixed", "gemm_splitk2", "gemm_splitk128", "gemm_deep_ring", "gemm_conv_implicit", "gemm_register_staged",
+        "attn_gen1", "attn_pipelined", "attn_gen2", "attn_gen3", "attn_gen4", "attn_gen5", "attn_gen6", "attn_gen9", "attn_register_staged",
+        "ln_rows1", "ln_rows4", "ln_fixed_count", "ln_mode_inst", "mc_rows4", "mc_rows8", "mc_rows16", "mc_rows32", "mc_deferred_rows"};
+    return which >= 0 && which < LC_COUNT ? names[which] : nullptr;
+}
+
 static bool g_gemm_glds = true;
 void gemm_set_glds(bool on) { g_gemm_glds = on; }
+bool gemm_glds() { return g_gemm_glds; }
 void gemm_set_raster(int group) { g_gemm_raster = group; }
 void gemm_set_auto_rule(int rule, int num_cu) {
     if (rule >= 0) g_gemm_auto_rule = rule;
@@ -2359,6 +2378,34 @@ void gemm_set_mixed(bool on) { g_gemm_mixed = on; }
 void gemm_set_persistent_qkv(bool on) { g_gemm_persistent_qkv = on; }
 void gemm_set_config(int waves) {
     if (waves == 0 || waves == 4 || waves == 8 || waves == 9 || waves == 10 || waves == 11 || waves == 12 || waves == 13 || waves == 16 || waves == 32) g_gemm_waves = waves;
+}
+
+bool gemm_get_option(const char* name, int* value) {
+    if (!strcmp(name, "gemm_waves")) *value = g_gemm_waves;
+    else if (!strcmp(name, "gemm_raster")) *value = g_gemm_raster;
+    else if (!strcmp(name, "gemm_auto_rule")) *value = g_gemm_auto_rule;
+    else if (!strcmp(name, "gemm_num_cu")) *value = g_num_cu;
+    else if (!strcmp(name, "gemm_wide_epilogue")) *value = g_gemm_wide_epilogue ? 1 : 0;
+    else if (!strcmp(name, "gemm_phased")) *value = g_gemm_phased ? 1 : 0;
+    else if (!strcmp(name, "gemm_persistent")) *value = g_gemm_persistent ? 1 : 0;
+    else if (!strcmp(name, "gemm_persistent_resid")) *value = g_gemm_persistent_resid;
+    else if (!strcmp(name, "gemm_splitk")) *value = g_gemm_splitk ? 1 : 0;
+    else if (!strcmp(name, "gemm_splitk128")) *value = g_gemm_splitk128 ? 1 : 0;
+    else if (!strcmp(name, "conv_implicit")) *value = g_conv_implicit ? 1 : 0;
+    else if (!strcmp(name, "gemm_xcd_walk")) *value = g_gemm_xcd_walk ? 1 : 0;
+    else if (!strcmp(name, "gemm_epi_slices")) *value = g_gemm_epi_slices ? 1 : 0;
+    else if (!strcmp(name, "gemm_mixed")) *value = g_gemm_mixed ? 1 : 0;
+    else if (!strcmp(name, "gemm_persistent_qkv")) *value = g_gemm_persistent_qkv ? 1 : 0;
+    else if (!strcmp(name, "gelu_pk")) *value = g_gemm_gelu_pk ? 1 : 0;
+    else return false;
+    return true;
+}
+
+// the checks of gemm_launch2's three folded branches that depend on the switches and the shape alone (one problem, batch 1)
+bool gemm_fold_supported(int epi, int M, int N, int K) {
+    if (epi != EPI_RESID_BF16_ST && epi != EPI_BF16_GELU_ERF_LNF && epi != EPI_RESID_BF16_LND) return false;
+    if (!g_gemm_glds || !g_gemm_wide_epilogue) return false;
+    return M > 0 && N > 0 && K % 128 == 0 && K >= 256 && N % 256 == 0;
 }
 
 static bool gemm_args_ok(const GemmArgs& p) {
@@ -2423,6 +2470,7 @@ hipError_t gemm_launch2(const GemmArgs& p_in, int batch, const GemmArgs* p2_in, 
         }
         if (S > 1) {
             g_last_splitk_slices = S;
+            launch_count(LC_GEMM_SPLITK128);
             GemmArgs q = p;
             q.K = p.K / S;
             q.batch = S;
@@ -2453,6 +2501,7 @@ hipError_t gemm_launch2(const GemmArgs& p_in, int batch, const GemmArgs* p2_in, 
         const int64_t MN = (int64_t)p.M * p.N;
         if (S > 1 && (int64_t)S * MN <= p.split_ws_elems) {
             g_last_splitk_slices = S;
+            launch_count(LC_GEMM_SPLITK128);
             GemmArgs q = p;
             q.K = p.K / S;
             q.batch = S;
@@ -2527,7 +2576,7 @@ hipError_t gemm_launch_qkv_mlp(const GemmArgs& pq_in, const GemmArgs& pm_in, hip
         const hipError_t e = gemm_launch(pm_in, 1, s);
         return e != hipSuccess ? e : gemm_launch(pq_in, 1, s);
     };
-    if (!g_gemm_mixed || !g_gemm_persistent || !g_gemm_phased || g_gemm_waves != 0 || !g_gemm_glds || !g_gemm_wide_epilogue ||
+    if (!g_gemm_mixed || !g_gemm_persistent || !g_gemm_persistent_qkv || !g_gemm_phased || g_gemm_waves != 0 || !g_gemm_glds || !g_gemm_wide_epilogue ||
         pq.epi != EPI_QKV || pm.epi != EPI_BF16_GELU_TANH || pq.conv.x || pm.conv.x || pq.M <= 0 || pm.M <= 0)
         return fallback();
     if (pq.K % 128 || pm.K % 128 || pq.K < 256 || pm.K < 256 || pq.N % 256 || pm.N % 256) return fallback();

@@ -3,8 +3,41 @@
 #define R3G_KERNELS_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 namespace r3g {
+
+// ------------------------------------------------------------------ launch counters (r3g_get_counter)
+// Which kernel form a launch actually took: bumped on the host where the launch is issued, so that a test can tell a switch that
+// was obeyed from one that was ignored (the forms are bit-identical more often than not).  Names: launch_counter_name().
+enum LaunchCounter {
+    LC_GEMM_W4_128 = 0,        // launch_cfg: 128 x 128 tile, 4 waves
+    LC_GEMM_W8_128,            // 128 x 128 tile, 8 waves
+    LC_GEMM_W16_256,           // 256 x 256 tile, 16 waves ("gemm_waves" 16)
+    LC_GEMM_TWO_STAGE_256,     // 256 x 256 tile, 8 waves, two LDS stages ("gemm_waves" 9)
+    LC_GEMM_256X128,           // 256 x 128 tile ("gemm_waves" 10)
+    LC_GEMM_PHASED,            // phased 256 x 256 kernel, one tile per workgroup (the folded geo epilogues included)
+    LC_GEMM_PHASED_PERSISTENT, // ... its persistent form
+    LC_GEMM_MIXED,             // one persistent launch over a single block's fused QKV and MLP-in problems
+    LC_GEMM_SPLITK2,           // phased kernel, split-K over two workgroups per tile
+    LC_GEMM_SPLITK128,         // K slices of the 128 x 128 kernel plus the reduce kernel
+    LC_GEMM_DEEP_RING,         // deep-ring 256 x 256 x 32 kernel ("gemm_waves" 32)
+    LC_GEMM_CONV_IMPLICIT,     // implicit-GEMM 3 x 3 convolution
+    LC_GEMM_REGISTER_STAGED,   // any of the launch_cfg forms with register staging instead of LDS-DMA
+    LC_ATTN_GEN1,              // first-round attention kernel
+    LC_ATTN_PIPELINED,         // ... its software-pipelined form ("attn_pipelined")
+    LC_ATTN_GEN2, LC_ATTN_GEN3, LC_ATTN_GEN4, LC_ATTN_GEN5, LC_ATTN_GEN6, LC_ATTN_GEN9,
+    LC_ATTN_REGISTER_STAGED,   // an attention launch with register staging
+    LC_LN_ROWS1, LC_LN_ROWS4,  // LayerNorm / ln_dot row-kernel launches with 1 | 4 rows per wave
+    LC_LN_FIXED,               // ... with a compile-time row length (C = 1024 / 1536, "ln_fixed")
+    LC_LN_MODE,                // ... with the affine-only / modulation-only instantiation ("ln_modes")
+    LC_MC_ROWS4, LC_MC_ROWS8, LC_MC_ROWS16, LC_MC_ROWS32,   // marching cubes: row-kernel classify launches by node rows per wave
+    LC_MC_DEFERRED,            // ... of them, with the deferred tiling selection ("mc_deferred")
+    LC_COUNT
+};
+extern std::atomic<int64_t> g_launch_counters[LC_COUNT];
+inline void launch_count(int which) { g_launch_counters[which].fetch_add(1, std::memory_order_relaxed); }
+const char* launch_counter_name(int which);
 
 // ------------------------------------------------------------------ GEMM (gemm.hip)
 enum GemmEpilogue {
@@ -112,7 +145,7 @@ hipError_t gemm_launch2(const GemmArgs& p, int batch, const GemmArgs* p2, int ba
 void gemm_set_glds(bool on);  // staging path: LDS-DMA (default) or register-staged
 void attn_set_glds(bool on);
 void attn_set_ablate(int mask);   // timing-only ablation builds of the attention kernel (tools/bench_attn.py)
-void attn_set_variant(int v);       // round 6: bit 0 re-stabilise test on the sum of the exponentials, bit 1 row sum on plain adds (generations 2 / 6 / 7)
+void attn_set_variant(int v);       // round 6: 1 (default) fast pass with the re-stabilise test on the sum of the exponentials | 0 rounds 2-5 (generations 2 / 6 / 7)
 void attn_set_interleave(int v);    // 1: the 64-query kernel's fast pass interleaves its softmax with its MFMAs (opt-in, measured slower) | 0 (default): clustered
 void attn_set_async_stage(int v);   // 1 (default): the variant-1 kernels issue their LDS-DMA from inline asm, unseen by the compiler's wait counts | 0: through the builtin
 void attn_set_pipelined(bool on);  // software-pipelined attention kernel (off by default: slower) vs the plain one
@@ -137,6 +170,12 @@ void gemm_set_persistent(bool on);   // phased kernel walks several tiles per wo
 void gemm_set_phased(bool on);   // 256x256 tiles: phased kernel (default) or the two-stage one
 void gemm_set_gelu_pk(bool on);   // GELU epilogues in packed fp16 (default on) | fp32 with v_exp_f32 / v_rcp_f32 (rounds 3-4)
 void gemm_set_wide_epilogue(bool on);  // 4|8 waves per 128x128 tile, 2|3 LDS stages
+bool gemm_glds();                      // the staging path gemm_set_glds selected
+// current value of a switch that lives in gemm.hip, by its r3g_set_option name; false: not one of them
+bool gemm_get_option(const char* name, int* value);
+// gemm_launch2 serves the folded geo-decoder epilogue `epi` (EPI_RESID_BF16_ST, EPI_BF16_GELU_ERF_LNF, EPI_RESID_BF16_LND) for one
+// problem of this shape under the current staging / epilogue switches: exactly its argument checks that do not depend on pointers
+bool gemm_fold_supported(int epi, int M, int N, int K);
 
 // ------------------------------------------------------------------ attention (attn.hip)
 constexpr int kAttnMaxEntries = 8;
@@ -170,6 +209,8 @@ struct AttnArgs {
 };
 
 hipError_t attention_launch(const AttnArgs& p, hipStream_t s);
+bool attn_glds();
+bool attn_get_option(const char* name, int* value);   // as gemm_get_option, for the switches of attn.hip
 // factor the producers of Q fold into it for the current attention kernel: scale * log2(e) (generation 2), or 1
 float attn_q_scale(float scale);
 void attn_set_wide_min(int items);     // generation 7: 256-query workgroups (generation 6) from this many work items on (default 2048)
@@ -180,6 +221,7 @@ void ln_set_rows4_min(int rows);     // automatic rule: launches of at least thi
 void ln_set_modes(bool on);         // LayerNorm: compile-time instantiations for the affine-only / modulation-only launches (default on)
 void ln_set_rows_per_wave(int rows);  // LayerNorm / ln_dot row kernels: 0 automatic | 1 | 4 rows per wave
 void ln_set_fixed_count(bool on);     // 1 (default): compile-time element counts for C = 1024 / 1536
+bool ln_get_option(const char* name, int* value);     // as gemm_get_option, for the "ln_*" switches (elem.hip)
 
 // ------------------------------------------------------------------ elementwise / norms (elem.hip)
 // y(bf16)[r][c] = ((x - mean) * rstd * (w ? w[c] : 1) + (b ? b[c] : 0)) * (1 + scale[batch][c]) + shift[batch][c]

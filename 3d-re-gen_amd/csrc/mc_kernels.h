@@ -17,6 +17,8 @@ struct McWorkspaceLayout {
 
 void mc_set_deferred(bool on);         // row kernel: tiling selection batched per wave (default) or per row
 void mc_set_rows_per_wave(int rows);  // node rows a wave marches through in the row kernel (4|8|16|32)
+bool mc_get_deferred();
+int mc_get_rows_per_wave();
 size_t mc_workspace_bytes(int n0, int n1, int n2, McWorkspaceLayout* lay);
 
 // K1 + K2.  After the stream drains: status word at ws+off_small, totals {nV, nF, nNZ} at +16.

@@ -33,6 +33,7 @@
 #define R3G_DEV static __device__ __forceinline__
 #define R3G_HOSTDEV static __host__ __device__ __forceinline__
 #define R3G_LUT_QUAL static __device__ const
+#include "kernels.h"
 #include "mc_cell.h"
 #include "mc_kernels.h"
 #include "prof.h"
@@ -640,6 +641,8 @@ static int g_rows_per_wave = 16;
 static bool g_deferred = true;   // row kernel with the tiling selection batched over all rows of a wave
 void mc_set_deferred(bool on) { g_deferred = on; }
 void mc_set_rows_per_wave(int rows) { g_rows_per_wave = rows == 4 || rows == 8 || rows == 32 ? rows : 16; }
+bool mc_get_deferred() { return g_deferred; }
+int mc_get_rows_per_wave() { return g_rows_per_wave; }
 
 size_t mc_workspace_bytes(int n0, int n1, int n2, McWorkspaceLayout* lay) {
     const uint64_t ncells = (uint64_t)(n0 - 1) * (n1 - 1) * (n2 - 1);
@@ -689,6 +692,8 @@ hipError_t mc_count_launch(const float* grid, int n0, int n1, int n2, double lev
             kern = rows == 4 ? mc_classify_rows2<4> : rows == 8 ? mc_classify_rows2<8> : rows == 32 ? mc_classify_rows2<32>
                                                                                                    : mc_classify_rows2<16>;
         }
+        launch_count(rows == 4 ? LC_MC_ROWS4 : rows == 8 ? LC_MC_ROWS8 : rows == 32 ? LC_MC_ROWS32 : LC_MC_ROWS16);
+        if (g_deferred) launch_count(LC_MC_DEFERRED);
         hipLaunchKernelGGL(kern, dim3((tasks + 3) / 4), dim3(kBlock), 0, stream, grid, nx, ny, cx, cy, cz,
                            lo, exact, level, classic, (uint2*)(ws + lay.off_act), (uint4*)(ws + lay.off_blk),
                            chunk_sums, chunk_nz, status);

@@ -573,6 +573,7 @@ static hipError_t compact_mesh(Arena& ar, float* verts, int64_t nv, int32_t* fac
 
 static bool g_floater_by_vertex = false;   // option "floater_by_vertex": rounds 1-2 joined components through shared vertices
 void mesh_set_floater_by_vertex(bool on) { g_floater_by_vertex = on; }
+bool mesh_get_floater_by_vertex() { return g_floater_by_vertex; }
 
 static int64_t edge_table_slots(int64_t nf) {
     int64_t cap = 64;

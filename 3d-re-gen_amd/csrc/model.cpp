@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -65,10 +66,10 @@ static bool g_geo_q_cache = true;   // keep the object-independent query side of
 static bool g_dit_f16_guard = true;    // option "dit_f16_guard": check the latents of an fp16-stream group, fall back to fp32 on overflow
 static bool g_geo_ln3_fold = true;    // option "geo_ln3_fold" (round 6): the geo decoder's ln_3 folded into c_proj's epilogue (statistics) and c_fc (W' = W gamma, rstd (acc - mean c1) + c2)
 static bool g_geo_lnd_fused = true;   // option "geo_lnd_fused" (round 6): ln_post + output_proj folded into the geo decoder's last residual GEMM
-static int64_t g_geo_q_cache_builds = 0;   // allocations of Model::GeoCache so far (r3g_get_counter "geo_q_cache_builds")
-static int64_t g_dit_groups = 0;         // launch groups r3g_flow_sample_batch has run (r3g_get_counter)
-static int64_t g_dit_evals = 0;          // DiT evaluations issued, one per launch group and step (r3g_get_counter "dit_evals")
-static int g_dit_f16_fallbacks = 0;    // how often that happened (r3g_set_option("dit_f16_fallbacks_reset", ...) / stderr line)
+static std::atomic<int64_t> g_geo_q_cache_builds{0};   // allocations of Model::GeoCache so far (r3g_get_counter "geo_q_cache_builds")
+static std::atomic<int64_t> g_dit_groups{0};       // launch groups r3g_flow_sample_batch has run (r3g_get_counter)
+static std::atomic<int64_t> g_dit_evals{0};        // DiT evaluations issued, one per launch group and step (r3g_get_counter "dit_evals")
+static std::atomic<int64_t> g_dit_f16_fallbacks{0};    // how often that happened (r3g_set_option("dit_f16_fallbacks_reset", ...) / stderr line)
 static bool g_dit_resid_f16 = true;   // the DiT's residual stream of the de-duplicated CFG path in fp16 (the reference's activation type) instead of fp32
 static bool g_skip_zero_step = true;   // skip the DiT evaluation of a step whose d_sigma is 0 (upstream's last step)
 // r3g_flow_sample runs steps [g_flow_first_step, g_flow_last_step) of its schedule (options "flow_first_step" / "flow_last_step";
@@ -78,11 +79,12 @@ static int g_flow_first_step = 0, g_flow_last_step = 1 << 30;
 // adaptive top-k selection of the geo decoder's cross-attention keys (options "geo_kv_topk" / "geo_kv_group" /
 // "geo_kv_stride"): 0 exact (default) | k > 0 keys kept per (group, head), clamped to num_latents | -1 upstream's rule
 static int g_geo_kv_topk = 0, g_geo_kv_group = 8192, g_geo_kv_stride = 64;
-static int64_t g_geo_kv_groups = 0;      // (group, head) selections made so far (r3g_get_counter "geo_kv_groups")
+static std::atomic<int64_t> g_geo_kv_groups{0};    // (group, head) selections made so far (r3g_get_counter "geo_kv_groups")
 // narrow geo decoder: option "geo_narrow_fused" -- everything behind the cross-attention of a decoder of width
 // 256 in one launch per pass (geo_narrow.hip) instead of the generic five
 static bool g_geo_narrow_fused = false;
-static int64_t g_geo_narrow_passes = 0;   // passes served by that kernel (r3g_get_counter "geo_narrow_passes")
+static std::atomic<int64_t> g_geo_narrow_passes{0};   // passes served by that kernel (r3g_get_counter "geo_narrow_passes")
+static std::atomic<int64_t> g_geo_lnf_passes{0}, g_geo_lnd_passes{0};   // passes that took the folded ln_3 / ln_post epilogues ("geo_lnf_passes" / "geo_lnd_passes")
 
 struct Model {
     r3g_model_config c{};
@@ -1053,12 +1055,15 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
                       lfc.K == W && lfp.N == W && lfp.K == lfc.N;
     // Round 6: ln_post + output_proj inside the last residual GEMM (EPI_RESID_BF16_LND): the final stream x2 is never written or
     // read again (2 x 268 MB per pass) and the ln_dot launch becomes a 33 MB merge of per-chunk statistics.  bf16 stream, bf16 MLP.
-    const bool lnd = g_geo_lnd_fused && xb && !f8m && c.vae_ln_post && W % 256 == 0 && W <= 4096 && lfc.N % 128 == 0 && lfc.N >= 256;
+    // (both folds only where gemm_launch2 serves their epilogues under the current staging / epilogue switches: otherwise round 5's sequence)
+    const bool lnd = g_geo_lnd_fused && xb && !f8m && c.vae_ln_post && W % 256 == 0 && W <= 4096 && lfc.N % 128 == 0 && lfc.N >= 256 &&
+                     gemm_fold_supported(EPI_RESID_BF16_LND, m.qc, W, lfc.N);
     // ... and ln_3 the same way, its weights being static: c_proj's epilogue also writes the row statistics of the stream it stores
     // (EPI_RESID_BF16_ST), a small kernel merges them into (mean, rstd), and c_fc runs on the RAW stream with W' = bf16(W gamma) and the
     // epilogue rstd (acc - mean c1) + c2 in front of its GELU (EPI_BF16_GELU_ERF_LNF) -- no LayerNorm launch, no normalised copy of the
     // stream (2 x 268 MB per pass).
-    const bool lnf = g_geo_ln3_fold && xb && !f8m && W % 256 == 0 && W <= 4096 && lfc.N % 256 == 0;
+    const bool lnf = g_geo_ln3_fold && xb && !f8m && W % 256 == 0 && W <= 4096 && lfc.N % 256 == 0 &&
+                     gemm_fold_supported(EPI_RESID_BF16_ST, m.qc, W, W) && gemm_fold_supported(EPI_BF16_GELU_ERF_LNF, m.qc, lfc.N, W);
     if ((lnd || lnf) && !tail && m.lnd_w < W) {
         if (m.lnd_part || m.lnd_gw) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(m.lnd_part); (void)hipFree(m.lnd_gw); m.lnd_part = m.lnd_gw = nullptr; }
         m.lnd_w = W;
@@ -1167,6 +1172,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
                 pf.lnf_stats = m.lnf_stats;
                 hipError_t e = gemm_launch(pf, 1, s);
                 if (e != hipSuccess) return hip_fail(e, "gemm_launch(geo ln_3 + mlp.c_fc)");
+                ++g_geo_lnf_passes;
             } else {
                 R3G_RC(layernorm(m.f32a, W, 0, m.xn, W, 0, n, 1, W, l3w, l3b, nullptr, nullptr, 0, 1e-6f, s, xb));
                 R3G_RC(gemm(m.xn, W, 0, lfc, 0, lfc.N, m.hid, lfc.N, 0, n, W, EPI_BF16_GELU_ERF, nullptr, 0, 1, s));
@@ -1178,6 +1184,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
                 hipError_t e = gemm_launch(pl, 1, s);
                 if (e != hipSuccess) return hip_fail(e, "gemm_launch(geo mlp.c_proj + ln_post + output_proj)");
                 R3G_TRY(lnd_finalize_launch(m.lnd_part, n, W / 64, 1e-5f, m.lnd_gw + W, grid + start + off, s));
+                ++g_geo_lnd_passes;
                 continue;
             }
             R3G_RC(gemm(m.hid, lfc.N, 0, lfp, 0, W, m.f32a, W, 0, n, lfc.N, epi_res, nullptr, 0, 1, s));
@@ -1499,9 +1506,15 @@ int r3g_get_counter(const char* name, int64_t* value) {
     else if (!strcmp(name, "geo_q_cache_builds")) *value = g_geo_q_cache_builds;
     else if (!strcmp(name, "geo_kv_groups")) *value = g_geo_kv_groups;
     else if (!strcmp(name, "geo_narrow_passes")) *value = g_geo_narrow_passes;
+    else if (!strcmp(name, "geo_lnf_passes")) *value = g_geo_lnf_passes;
+    else if (!strcmp(name, "geo_lnd_passes")) *value = g_geo_lnd_passes;
     else if (!strcmp(name, "meshdist_tests")) *value = meshdist_tests_total();
     else if (!strcmp(name, "meshinside_tests")) *value = meshinside_tests_total();
-    else return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
+    else {
+        for (int i = 0; i < LC_COUNT; ++i)
+            if (!strcmp(name, launch_counter_name(i))) { *value = g_launch_counters[i].load(std::memory_order_relaxed); return R3G_OK; }
+        return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
+    }
     return R3G_OK;
 }
 
@@ -1652,9 +1665,10 @@ int r3g_op_gemm(const uint16_t* d_a, int64_t lda, const uint16_t* d_w, int64_t l
     GemmArgs p{};
     p.A = d_a; p.lda = lda; p.W = d_w; p.ldw = ldw; p.bias = d_bias; p.C = d_c; p.ldc = ldc; p.gate = d_gate;
     p.M = m_; p.N = n_; p.K = k_; p.epi = epilogue;
+    const bool staging = gemm_glds();      // the process-wide mode (r3g_set_staging) comes back after this launch
     gemm_set_glds(use_lds_dma != 0);
     hipError_t e = gemm_launch(p, 1, (hipStream_t)stream);
-    gemm_set_glds(true);
+    gemm_set_glds(staging);
     if (e != hipSuccess) return hip_fail(e, "r3g_op_gemm");
     return R3G_OK;
 }
@@ -1700,9 +1714,10 @@ int r3g_op_attention(const uint16_t* d_q, const uint16_t* d_k, const uint16_t* d
     p.Q = d_q; p.K = d_k; p.Vt = d_vt; p.O = d_o; p.ldo = (int64_t)heads * 64; p.strideO = (int64_t)lq * heads * 64;
     p.B = batch; p.H = heads; p.Lq = lq; p.Lq_pad = lq_pad; p.Lk = lk; p.Lk_pad = lk_pad;
     p.kv_batch_stride_zero = shared_kv; p.scale = 0.125f;
+    const bool staging = attn_glds();
     attn_set_glds(use_lds_dma != 0);
     hipError_t e = attention_launch(p, (hipStream_t)stream);
-    attn_set_glds(true);
+    attn_set_glds(staging);
     if (e != hipSuccess) return hip_fail(e, "r3g_op_attention");
     return R3G_OK;
 }
@@ -1878,6 +1893,37 @@ int r3g_set_option(const char* name, int value) {
     else if (!strcmp(name, "mc_deferred")) mc_set_deferred(value != 0);
     else if (!strcmp(name, "lds_dma")) { gemm_set_glds(value != 0); attn_set_glds(value != 0); }
     else return fail(R3G_ERR_INVALID, "r3g_set_option: unknown option '%s'", name);
+    return R3G_OK;
+}
+
+int r3g_get_option(const char* name, int* value) {
+    if (!name || !value) return fail(R3G_ERR_INVALID, "r3g_get_option: null argument");
+    if (!strcmp(name, "geo_kv_topk")) *value = g_geo_kv_topk;
+    else if (!strcmp(name, "geo_kv_group")) *value = g_geo_kv_group;
+    else if (!strcmp(name, "geo_kv_stride")) *value = g_geo_kv_stride;
+    else if (!strcmp(name, "geo_narrow_fused")) *value = g_geo_narrow_fused ? 1 : 0;
+    else if (!strcmp(name, "fuse_qkv")) *value = g_fuse_qkv ? 1 : 0;
+    else if (!strcmp(name, "batch_mods")) *value = g_batch_mods ? 1 : 0;
+    else if (!strcmp(name, "cfg_dedup")) *value = g_cfg_dedup ? 1 : 0;
+    else if (!strcmp(name, "skip_zero_step")) *value = g_skip_zero_step ? 1 : 0;
+    else if (!strcmp(name, "geo_q_cache")) *value = g_geo_q_cache ? 1 : 0;
+    else if (!strcmp(name, "geo_q_cache_gb")) *value = g_geo_q_cache_bytes < 0 ? -1 : (int)(g_geo_q_cache_bytes >> 30);
+    else if (!strcmp(name, "geo_resid_bf16")) *value = g_geo_resid_bf16 ? 1 : 0;
+    else if (!strcmp(name, "dit_resid_f16")) *value = g_dit_resid_f16 ? 1 : 0;
+    else if (!strcmp(name, "dit_f16_guard")) *value = g_dit_f16_guard ? 1 : 0;
+    else if (!strcmp(name, "geo_fp8")) *value = g_geo_fp8;
+    else if (!strcmp(name, "group_streams")) *value = g_group_streams ? 1 : 0;
+    else if (!strcmp(name, "overlap_mlp")) *value = g_overlap_mlp ? 1 : 0;
+    else if (!strcmp(name, "geo_lnd_fused")) *value = g_geo_lnd_fused ? 1 : 0;
+    else if (!strcmp(name, "geo_ln3_fold")) *value = g_geo_ln3_fold ? 1 : 0;
+    else if (!strcmp(name, "flow_first_step")) *value = g_flow_first_step;
+    else if (!strcmp(name, "flow_last_step")) *value = g_flow_last_step >= (1 << 30) ? -1 : g_flow_last_step;
+    else if (!strcmp(name, "floater_by_vertex")) *value = mesh_get_floater_by_vertex() ? 1 : 0;
+    else if (!strcmp(name, "mc_rows")) *value = mc_get_rows_per_wave();
+    else if (!strcmp(name, "mc_deferred")) *value = mc_get_deferred() ? 1 : 0;
+    else if (!strcmp(name, "lds_dma")) *value = gemm_glds() && attn_glds() ? 1 : 0;
+    else if (gemm_get_option(name, value) || attn_get_option(name, value) || ln_get_option(name, value)) return R3G_OK;
+    else return fail(R3G_ERR_INVALID, "r3g_get_option: unknown option '%s'", name);
     return R3G_OK;
 }
 

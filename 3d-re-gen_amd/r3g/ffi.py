@@ -100,6 +100,7 @@ SYMBOLS = {
     "r3g_op_geo_tail": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, _P, _P]),
     "r3g_set_staging": (_I, [_I]),
     "r3g_set_option": (_I, [ctypes.c_char_p, _I]),
+    "r3g_get_option": (_I, [ctypes.c_char_p, _P]),
     "r3g_get_counter": (_I, [ctypes.c_char_p, _P]),
     "r3g_prof_enable": (_I, [_I]),
     "r3g_prof_read": (_I, [_P, _P, _P, _I]),
@@ -163,9 +164,16 @@ def check(rc):
     raise R3GError(rc, msg)
 
 
+def option(name):
+    """r3g_get_option: the current value of a process-wide switch, as r3g_set_option would take it back"""
+    v = ctypes.c_int(0)
+    check(lib().r3g_get_option(name.encode(), ctypes.byref(v)))
+    return int(v.value)
+
+
 def counter(name):
     """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "dit_evals", "geo_q_cache_builds",
-    "geo_kv_groups", "geo_narrow_passes", "meshdist_tests", "meshinside_tests")"""
+    "geo_kv_groups", "geo_narrow_passes", "meshdist_tests", "meshinside_tests", ...: the list is in include/r3g.h)"""
     v = ctypes.c_int64(0)
     check(lib().r3g_get_counter(name.encode(), ctypes.byref(v)))
     return int(v.value)

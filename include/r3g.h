@@ -585,20 +585,29 @@ int r3g_prof_read_bytes(double* bytes, int n);
  * q-norm of every grid point -- stays resident in HBM after its first evaluation, 2 x 34.8 GB at 257^3, and is read instead of
  * recomputed; bit-identical; skipped by itself when the memory is not there), "skip_zero_step" (the DiT evaluation of a step with d_sigma = 0 --
  * upstream's last step -- is skipped: x += 0 * v), "overlap_mlp" (0 default | 1: MLP half of a single block's linear1
- * on a second stream beside the attention kernel), "gemm_wide_epilogue" (stores through the LDS transpose).
+ * on a second stream beside the attention kernel), "gemm_wide_epilogue" (stores through the LDS transpose).  "lds_dma" 0 and "gemm_wide_epilogue" 0 keep every bit except (a) in
+ * the geo decoder, whose folded epilogues ("geo_ln3_fold", "geo_lnd_fused") exist for LDS-DMA staging and the wide epilogue only:
+ * without either it runs rounds 1-5's launches, as under "geo_ln3_fold" 0 + "geo_lnd_fused" 0; (b) "lds_dma" 0: the register-staged
+ * attention kernel is the "attn_variant" 0 body, with that switch's corner; (c) "gemm_wide_epilogue" 0: the narrow fp32
+ * read-modify-write epilogue forms old + gate (acc + bias) with one fused multiply-add where the wide one rounds the product first --
+ * whatever runs on an fp32 residual stream (conditioner, VAE, the DiT's plain-batch forward) moves by an fp32 rounding per residual
+ * GEMM, and stays at its tolerance against the fp32 oracle (tests/test_switches_gpu.py::test_switch[gemm_wide_epilogue=0]).
  * Tuning: "gemm_waves" (0 auto | 4 | 8 | 9 = 256x256 two-stage | 10 = 256x128 | 11 = 256x256 phased | 12 = phased,
- * persistent grid | 13 = phased, deterministic split-K over two workgroups per tile | 16 | 32 = deep ring), "gemm_raster" (-1 auto | tile columns per rasterisation group), "gemm_phased"
+ * persistent grid | 13 = phased, deterministic split-K over two workgroups per tile (another order of the fp32 additions, like "gemm_splitk") | 16 | 32 = deep ring), "gemm_raster" (-1 auto | tile columns per rasterisation group), "gemm_phased"
  * (1: 256x256 tiles on the phased counted-vmcnt kernel), "gemm_persistent" (1: its persistent form for bf16 outputs
  * with more tiles than CUs), "gemm_xcd_walk" (1 default: in the persistent form an XCD's workgroups walk ONE contiguous range of the
  * rasterised tile order (consecutive steps touch neighbouring A rows) -- geo c_fc 1 109 -> 1 045 us, L2 <-> fabric bytes unchanged; bit-identical | 0: rounds 2-4's walk), "gemm_persistent_resid" (0 | bit 0: the fp32, bit 1: the bf16 read-modify-write epilogue on the persistent form as well), "gemm_num_cu" (CUs the tile rules assume, default 256), "gemm_auto_rule" (2: the current
  * tile-choice rule | 1: round 2's | 0: round 1's first version), "attn_generation" (7 default: 6 where its
  * 256-query workgroups make four rounds of the device, otherwise 2 | 2 = four waves of 32 queries | 6 = four waves of 64
  * queries, bit-identical to 2 | 1 = the first-round kernel | 3, 4, 5 = pipelined / 8-wave variants), "attn_wide_min" (2048: work items of 256 queries from which attn_generation 7 takes generation 6), "ln_rows" (0 automatic | 1 | 4 rows per wave in the
- * LayerNorm / ln_dot row kernels), "ln_rows4_min" (65536: launches of at least this many rows take 4 rows per wave under the automatic rule), "ln_fixed" (1: their instantiations with a compile-time row length for C = 1024 / 1536), "ln_modes" (1, round 6: for C = 1024 the affine-only and the modulation-only launches take instantiations with that decided at compile time -- bit-identical | 0: the generic kernel), "attn_pipelined" (0), "attn_ablate"
+ * LayerNorm / ln_dot row kernels), "ln_rows4_min" (65536: launches of at least this many rows take 4 rows per wave under the automatic rule), "ln_fixed" (1: their instantiations with a compile-time row length for C = 1024 / 1536), "ln_modes" (1, round 6: for C = 1024 the affine-only and the modulation-only launches take instantiations with that decided at compile time -- bit-identical | 0: the generic kernel), "attn_pipelined" (0 default | 1: the software-pipelined form of the first-round kernel, other rounding points inside the softmax like
+ * attn_generation 1), "attn_ablate"
  * (timing-only masks, results are garbage), "floater_by_vertex" (0), "mc_rows" (4 | 8 | 16 | 32 node rows per wave in the marching-cubes row
  * kernel), "mc_deferred" (1: tiling selection batched per wave | 0: round 1's per-row kernel), "geo_resid_bf16" (1:
- * 16-bit residual stream in the geo decoder block), "geo_fp8" (0 default | 1: the geo decoder's c_q and MLP GEMMs on e4m3
- * operands | 2: MLP only | 3: c_q only -- a different precision, NOT result-preserving), "gemm_splitk" (0), "conv_implicit" (1 default: the 3 x 3 convolutions of the texture models run as implicit GEMMs -- the 128 x 128
+ * 16-bit residual stream in the geo decoder block | 0: round 1's fp32 stream, without the query-side cache and the folded epilogues --
+ * another precision of the stream, NOT bit-preserving), "geo_fp8" (0 default | 1: the geo decoder's c_q and MLP GEMMs on e4m3
+ * operands | 2: MLP only | 3: c_q only -- a different precision, NOT result-preserving), "gemm_splitk" (0 default | 1: an under-filled deep-K fp32-residual GEMM splits K over two workgroups per 256x256 tile -- another order of
+ * the fp32 additions, not bit-preserving; deterministic), "conv_implicit" (1 default: the 3 x 3 convolutions of the texture models run as implicit GEMMs -- the 128 x 128
  * kernel gathers the nine shifted rows of its A operand from the activation rows itself, bit-identical to the GEMM over the im2col
  * matrix | 0: im2col + GEMM, rounds 3-4), "gemm_splitk128" (1 default: the 3 x 3 convolutions of the texture models split a deep k over
  * several workgroups where their grid would fill less than half of the chip, r3g_op_gemm_splitk | 0: one workgroup per tile walks all of k, rounds 2-4 -- another
@@ -627,15 +636,18 @@ int r3g_prof_read_bytes(double* bytes, int n);
  * "geo_ln3_fold" (1 default, round 6 | 0: the geo decoder's ln_3 as its own launch writing a normalised bf16 copy of the stream, rounds
  * 1-5; folded, c_proj's epilogue also writes the rows' chunk statistics, and c_fc runs on the raw stream with W' = bf16(W gamma) and
  * rstd (acc - mean c1) + c2 in front of its GELU -- the same function without the bf16 rounding of the normalised operand: logits move
- * by ~1e-3 of their scale, inside the 1e-2 tolerance against the fp32 oracle),
+ * by 4-6e-3 of their scale (recorded in tests/test_model_gpu.py), inside the 1e-2 tolerance against the fp32 oracle; taken only where the GEMM
+ * launcher serves the folded epilogues -- LDS-DMA staging and "gemm_wide_epilogue" on -- otherwise rounds 1-5's launches run),
  * "geo_lnd_fused" (1 default, round 6 | 0: the geo decoder's ln_post + output_proj as their own launch over the stored residual
  * stream, rounds 1-5; fused, the last residual GEMM's epilogue writes per-row statistics of its 64-column chunks instead of the
- * stream and a small kernel merges them -- same function, another summation order: logits equal to ~1e-6 of their scale),
+ * stream and a small kernel merges them -- same function, another summation order: logits equal to ~1e-6 of their scale; under the
+ * same condition as "geo_ln3_fold"),
  * "gemm_epi_slices" (1 default, round 6 | 0: the persistent phased kernel's bf16 / fused-QKV epilogues in 32-row passes through 4 KiB of
  * extra scratch per wave instead of 64-row passes through the wave's own staging slices of the idle k-tile buffer), "gemm_mixed" (1
  * default, round 6 | 0: a DiT single block's fused QKV projection and MLP-in + GELU projection as two launches instead of one
  * persistent launch over both problems' tiles), "gemm_persistent_qkv" (1 default since round 6 | 0: fused QKV launches with more 256x256 tiles than CUs -- the double
- * blocks' img + txt pair -- one tile per workgroup instead of the persistent phased kernel; with round 4's 32-row epilogue passes the
+ * blocks' img + txt pair, and the single blocks' QKV half, which then leaves the "gemm_mixed" launch -- one tile per workgroup instead of the
+ * persistent phased kernel; with round 4's 32-row epilogue passes the
  * persistent form was 17 ms per object slower, with "gemm_epi_slices" it is 4 ms faster, profiles/r06_ab.md), "flow_first_step" / "flow_last_step" (0 / -1: r3g_flow_sample runs steps [first, last) of its schedule; consecutive
  * segments continuing on each other's latents are the same launches as one call -- how tests read the latents after 10, 20, ...
  * of 50 steps), "geo_kv_topk" / "geo_kv_group" / "geo_kv_stride" (0 / 8192 / 64: adaptive top-k KV selection in the geo decoder,
@@ -643,9 +655,16 @@ int r3g_prof_read_bytes(double* bytes, int n);
  * narrow geo decoder of width 256 with hidden 256 | 512 | 1024 on the bf16 stream is affected -- 1: everything behind its
  * cross-attention, c_proj to output_proj, is one launch per pass (r3g_op_geo_tail's kernel) | 0: the generic launches; the same
  * function with other rounding points; profiles/turbo_vae.md has the timing).  None of them changes a
- * result bit, except fuse_qkv / batch_mods / cfg_dedup (different summation order, same function) and attn_generation
- * (different rounding points inside the softmax). */
+ * result bit, except fuse_qkv / batch_mods / cfg_dedup (different summation order, same function), attn_generation and
+ * attn_pipelined (different rounding points inside the softmax), and those whose description above says so: geo_fp8, geo_resid_bf16,
+ * dit_resid_f16, gelu_pk, gemm_splitk, gemm_waves 13, gemm_splitk128, geo_ln3_fold, geo_lnd_fused, geo_narrow_fused, attn_variant in its stated
+ * corner, and lds_dma / gemm_wide_epilogue where their description says so.  r3g_get_option reads every one of them back. */
 int r3g_set_option(const char* name, int value);
+/* The current value of every name r3g_set_option accepts (the "geo_kv_*" names and "geo_narrow_fused" included), as r3g_set_option
+ * would take it back: "geo_q_cache_gb" reports -1 for the automatic budget, "flow_last_step" -1 for "to the end", "lds_dma" 1 only
+ * while both the GEMM and the attention kernels stage through LDS-DMA.  A value that r3g_set_option clamped or refused reads back as
+ * what is in force.  Host state only (no GPU needed).  Unknown name: R3G_ERR_INVALID. */
+int r3g_get_option(const char* name, int* value);
 /* Process-wide event counters (round 6).  "dit_f16_fallbacks": launch groups of r3g_flow_sample_batch whose fp16 residual stream
  * produced non-finite latents and that therefore ran a second time on the fp32 stream ("dit_f16_guard"; such a group costs twice its
  * time -- bench.py and the stage report carry the count so that a slow run says why).  "dit_groups": launch groups run so far.
@@ -657,6 +676,20 @@ int r3g_set_option(const char* name, int value);
  * "geo_narrow_passes": grid passes served by the fused tail of a narrow geo decoder ("geo_narrow_fused") so far.
  * "meshdist_tests": point-triangle tests made by r3g_meshdist_query so far.
  * "meshinside_tests": point-face tests made by r3g_meshinside_query so far.
+ * "geo_lnf_passes" / "geo_lnd_passes": geo decoder passes that took the folded ln_3 ("geo_ln3_fold") / ln_post + output_proj
+ * ("geo_lnd_fused") epilogues.
+ * Kernel-choice counters, one per form a launch can end in, bumped on the host where the launch is issued (tests read them to see
+ * that a switch was obeyed, the forms being bit-identical more often than not).  GEMM: "gemm_w4_128", "gemm_w8_128" (128 x 128 tiles,
+ * 4 | 8 waves), "gemm_w16_256" (256 x 256, 16 waves), "gemm_two_stage_256" ("gemm_waves" 9), "gemm_256x128" (10), "gemm_phased" (one
+ * tile per workgroup; the folded geo epilogues included), "gemm_phased_persistent", "gemm_mixed" (a single block's fused QKV + MLP-in
+ * as one persistent launch), "gemm_splitk2" (split-K over two workgroups per tile), "gemm_splitk128" (the slices of the 128 x 128
+ * kernel plus their reduce; the slice launch counts under its own form as well), "gemm_deep_ring", "gemm_conv_implicit",
+ * "gemm_register_staged" (a tile-kernel launch without LDS-DMA; the phased kernels have no such form).  Attention: "attn_gen1",
+ * "attn_pipelined", "attn_gen2", "attn_gen3", "attn_gen4", "attn_gen5", "attn_gen6", "attn_gen9" (the generation launched, after "attn_generation" 7's rule), and
+ * "attn_register_staged".  Row kernels: "ln_rows1" / "ln_rows4" (LayerNorm and ln_dot launches with 1 | 4 rows per wave), "ln_fixed_count"
+ * (with a compile-time row length), "ln_mode_inst" (with the affine-only / modulation-only instantiation); "mc_rows4", "mc_rows8",
+ * "mc_rows16", "mc_rows32" (marching-cubes row-kernel classify launches by node rows per wave) and "mc_deferred_rows" (those with the
+ * deferred tiling selection).  All counters are atomic: two contexts on two threads may bump them concurrently.
  * r3g_flow_sample_batch is SYNCHRONOUS while the guard is on (one 4-byte read-back per group) and must not be captured into a
  * hipGraph then; with "dit_f16_guard" 0 or "dit_resid_f16" 0 it only enqueues work.  Unknown name: R3G_ERR_INVALID. */
 int r3g_get_counter(const char* name, int64_t* value);

@@ -116,9 +116,8 @@ def test_every_option_is_documented_and_settable():
     from r3g import ffi
     L = ffi.lib()
     assert L.r3g_set_option(b"no_such_option", 1) != 0
-    defaults = {"attn_generation": 7, "ln_rows": 0, "ln_fixed": 1, "overlap_mlp": 0, "gemm_waves": 0, "gemm_raster": -1,
-                "gemm_num_cu": 256, "gemm_auto_rule": 1, "mc_rows": 16, "geo_fp8": 0, "gemm_splitk": 0, "attn_pipelined": 0,
-                "attn_ablate": 0}
+    import switch_table as T
     for n in names:
-        v = defaults.get(n, 1)
-        assert L.r3g_set_option(n.encode(), v) == 0, n       # (re)sets the default: the other tests share this process
+        assert L.r3g_set_option(n.encode(), T.ROWS[n]["default"]) == 0, n       # (re)sets the default: the other tests share this process
+    T.restore_defaults(L, ffi)                                   # (the "geo_kv_*" names, which kv_set_option parses, included)
+    assert T.not_at_default(L, ffi) == {}, "options left off their defaults (current, default)"

@@ -293,15 +293,29 @@ def test_linear1_as_one_persistent_launch_and_sliced_epilogues_are_bit_identical
     from r3g import ffi
     L = ffi.lib()
     lat, cond = _batch_inputs(wide, 4, 300)
+    names = ("gemm_mixed", "gemm_phased_persistent", "gemm_phased")
+    c0 = {n: ffi.counter(n) for n in names}
     want = wide.gpu.flow_sample_batch(lat.clone(), cond, 2, 5.0).clone()
+    c1 = {n: ffi.counter(n) for n in names}
+    # the bits are the same either way, so the launch counters say which form ran: by default the single block's linear1 is the mixed
+    # launch and the double block's QKV pair a persistent one
+    assert c1["gemm_mixed"] > c0["gemm_mixed"] and c1["gemm_phased_persistent"] > c0["gemm_phased_persistent"]
+    base_phased = c1["gemm_phased"] - c0["gemm_phased"]
     try:
         for mixed, slices, pqkv in ((0, 1, 1), (1, 0, 1), (0, 0, 1), (1, 1, 0), (0, 0, 0)):
             ffi.check(L.r3g_set_option(b"gemm_mixed", mixed))
             ffi.check(L.r3g_set_option(b"gemm_epi_slices", slices))
             ffi.check(L.r3g_set_option(b"gemm_persistent_qkv", pqkv))       # the double blocks' QKV pair on the persistent kernel
+            c0 = {n: ffi.counter(n) for n in names}
             got = wide.gpu.flow_sample_batch(lat.clone(), cond, 2, 5.0)
+            c1 = {n: ffi.counter(n) for n in names}
             assert torch.equal(got, want), "gemm_mixed=%d gemm_epi_slices=%d gemm_persistent_qkv=%d: max |d| %.3e" % (
                 mixed, slices, pqkv, float((got - want).abs().max()))
+            # the mixed launch needs both switches (its QKV half IS a persistent fused-QKV launch) ...
+            assert (c1["gemm_mixed"] > c0["gemm_mixed"]) == bool(mixed and pqkv), (mixed, slices, pqkv)
+            # ... and without gemm_persistent_qkv every fused-QKV launch leaves the persistent kernel for the one-tile-per-workgroup form
+            if not pqkv:
+                assert c1["gemm_phased"] - c0["gemm_phased"] > base_phased, (mixed, slices, pqkv)
     finally:
         ffi.check(L.r3g_set_option(b"gemm_mixed", 1))
         ffi.check(L.r3g_set_option(b"gemm_epi_slices", 1))
