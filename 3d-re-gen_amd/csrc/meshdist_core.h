@@ -114,6 +114,59 @@ R3G_MD_HD float tri_dist2(float px, float py, float pz, const Tri& t) {
     return best;
 }
 
+// tri_dist2 with the point that attains it: the same candidates in the same order -- edges ab, bc, ac,
+// then the refined interior point -- with the same arithmetic, so the value returned is tri_dist2's bit for bit; a later
+// candidate replaces the point only when it is strictly nearer.  The point is base + t * edge (edges) or
+// a + v * ab + w * ac (interior), one float32 operation each, left to right.
+R3G_MD_HD float seg_closest(float apx, float apy, float apz, float abx, float aby, float abz, float* t_out) {
+    const float den = abx * abx + aby * aby + abz * abz;
+    const float num = apx * abx + apy * aby + apz * abz;
+    float t = den > 0.0f ? num / den : 0.0f;
+    t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+    const float qx = apx - t * abx, qy = apy - t * aby, qz = apz - t * abz;
+    *t_out = t;
+    return qx * qx + qy * qy + qz * qz;
+}
+
+R3G_MD_HD float tri_closest(float px, float py, float pz, const Tri& t, float* cx, float* cy, float* cz) {
+    const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az;
+    const float acx = t.cx - t.ax, acy = t.cy - t.ay, acz = t.cz - t.az;
+    const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
+    const float apx = px - t.ax, apy = py - t.ay, apz = pz - t.az;
+    const float bpx = px - t.bx, bpy = py - t.by, bpz = pz - t.bz;
+    const float cpx = px - t.cx, cpy = py - t.cy, cpz = pz - t.cz;
+    float s;
+    float best = seg_closest(apx, apy, apz, abx, aby, abz, &s);
+    float rx = t.ax + s * abx, ry = t.ay + s * aby, rz = t.az + s * abz;
+    float d = seg_closest(bpx, bpy, bpz, bcx, bcy, bcz, &s);
+    if (d < best) best = d, rx = t.bx + s * bcx, ry = t.by + s * bcy, rz = t.bz + s * bcz;
+    d = seg_closest(apx, apy, apz, acx, acy, acz, &s);
+    if (d < best) best = d, rx = t.ax + s * acx, ry = t.ay + s * acy, rz = t.az + s * acz;
+    const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
+    const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
+    const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    if (va > 0.0f && vb > 0.0f && vc > 0.0f) {
+        const float den = va + vb + vc;
+        float v = vb / den, w = vc / den;
+        float qx = apx - v * abx - w * acx, qy = apy - v * aby - w * acy, qz = apz - v * abz - w * acz;
+        const float g11 = abx * abx + aby * aby + abz * abz, g12 = abx * acx + aby * acy + abz * acz;
+        const float g22 = acx * acx + acy * acy + acz * acz, det = g11 * g22 - g12 * g12;
+        if (det > 0.0f) {
+            const float e1 = abx * qx + aby * qy + abz * qz, e2 = acx * qx + acy * qy + acz * qz;
+            const float v2 = v + (g22 * e1 - g12 * e2) / det, w2 = w + (g11 * e2 - g12 * e1) / det;
+            if (v2 >= 0.0f && w2 >= 0.0f && v2 + w2 <= 1.0f) {
+                qx = apx - v2 * abx - w2 * acx, qy = apy - v2 * aby - w2 * acy, qz = apz - v2 * abz - w2 * acz;
+                v = v2, w = w2;
+            }
+        }
+        d = qx * qx + qy * qy + qz * qz;
+        if (d < best) best = d, rx = t.ax + v * abx + w * acx, ry = t.ay + v * aby + w * acy, rz = t.az + v * abz + w * acz;
+    }
+    *cx = rx, *cy = ry, *cz = rz;
+    return best;
+}
+
 // (dist2, face) in lexicographic order: the order in which candidates arrive does not matter
 R3G_MD_HD void take(float d, int32_t f, float& best, int32_t& bface) {
     if (d < best || (d == best && f < bface)) {
@@ -275,6 +328,129 @@ R3G_MD_HD void nearest(const Grid& g, const Tri* tris, const uint32_t* starts, c
     *dist2_out = best;
     *face_out = bface == kNoFace ? -1 : bface;
     if (ntests_out) *ntests_out = ntests;
+}
+
+// ---- registration: what one point adds to the sums of a fit step --------------------------------
+// All of it float64 on float32 inputs, one operation per product and sum, left to right, no contraction: the host twin
+// (tests/emu/meshfit_emu.cpp) and the kernels (meshfit_kernels.hip) add the same bits in the same order.
+constexpr int kFitPoint = 0, kFitPlane = 1;
+constexpr int kFitPointTerms = 18;      // W, sum w p [3], sum w q [3], sum w p q^T [9, row = p], sum w |p|^2, sum w d^2
+constexpr int kFitPlaneTerms = 37;      // upper triangle of sum g j j^T [28, row-major], sum g j r [7], W, sum w d^2
+constexpr int kFitMaxTerms = 37;
+constexpr int kFitRecord = 40;          // 8-byte slots of a partial record: the terms, then [38] = used, [39] = tests (uint64)
+constexpr int kFitBlock = 256;          // lanes per block: four waves
+constexpr int kFitMaxBlocks = 4096;     // blocks of a step; beyond 2^20 points a lane takes several, in index order
+
+R3G_MD_HD int fit_terms(int mode) { return mode == kFitPlane ? kFitPlaneTerms : kFitPointTerms; }
+R3G_MD_HD int64_t fit_blocks(int64_t n) {
+    const int64_t b = (n + kFitBlock - 1) / kFitBlock;
+    return b < 1 ? 1 : (b > kFitMaxBlocks ? kFitMaxBlocks : b);
+}
+
+// similarity p -> s R p + t (R row-major)
+struct Sim {
+    double s;
+    double r[9];
+    double t[3];
+};
+
+// the moved point, rounded to float32: the grid walk and every sum see this value
+R3G_MD_HD void sim_apply(const Sim& x, float px, float py, float pz, float* ox, float* oy, float* oz) {
+    const double X = (double)px, Y = (double)py, Z = (double)pz;
+    const double rx = x.r[0] * X + x.r[1] * Y + x.r[2] * Z;
+    const double ry = x.r[3] * X + x.r[4] * Y + x.r[5] * Z;
+    const double rz = x.r[6] * X + x.r[7] * Y + x.r[8] * Z;
+    *ox = (float)(x.s * rx + x.t[0]);
+    *oy = (float)(x.s * ry + x.t[1]);
+    *oz = (float)(x.s * rz + x.t[2]);
+}
+
+// centre of the grid's box: the sums are taken about it, so that their products stay small
+R3G_MD_HD void fit_centre(const Grid& g, double c[3]) {
+    for (int a = 0; a < 3; ++a) c[a] = 0.5 * ((double)g.lo[a] + (double)g.hi[a]);
+}
+
+// One source point (px, py, pz) with weight w under the similarity x against the grid: acc[0 .. fit_terms(MODE)) += its
+// terms, *used += 1, when the moved point is finite and dist2 <= md2 (float32; +inf: every finite point).
+// MODE plane works with the UNNORMALISED float64 normal N = (b - a) x (c - a) of the winning face and the factor
+// g = w / (N . N): g (J J^T) and g (J R) with J = [p x N, N, p . N], R = N . (q - p) are what the unit normal gives, without
+// a square root.  N . N == 0 (a face without area): N = p - q; still 0 (the point lies on it): the point adds W and d^2 only.
+template <int MODE>
+R3G_MD_HD void fit_point(const Grid& g, const Tri* tris, const uint32_t* starts, const int32_t* pairs, const Sim& x, float px,
+                         float py, float pz, float w32, float md2, double* acc, uint32_t* used, uint32_t* ntests) {
+    float mx, my, mz, d2;
+    int32_t face;
+    uint32_t nt = 0;
+    sim_apply(x, px, py, pz, &mx, &my, &mz);
+    nearest(g, tris, starts, pairs, mx, my, mz, &d2, &face, &nt);
+    *ntests += nt;
+    if (face < 0 || !(d2 <= md2)) return;
+    const Tri t = tris[face];
+    float qx, qy, qz;
+    tri_closest(mx, my, mz, t, &qx, &qy, &qz);
+    double c[3];
+    fit_centre(g, c);
+    const double w = (double)w32;
+    const double p[3] = {(double)mx - c[0], (double)my - c[1], (double)mz - c[2]};
+    const double q[3] = {(double)qx - c[0], (double)qy - c[1], (double)qz - c[2]};
+    *used += 1u;
+    if (MODE == kFitPoint) {
+        const double wp[3] = {w * p[0], w * p[1], w * p[2]};
+        acc[0] += w;
+_Pragma("unroll")
+        for (int a = 0; a < 3; ++a) acc[1 + a] += wp[a];
+_Pragma("unroll")
+        for (int a = 0; a < 3; ++a) acc[4 + a] += w * q[a];
+_Pragma("unroll")
+        for (int a = 0; a < 3; ++a)
+_Pragma("unroll")
+            for (int b = 0; b < 3; ++b) acc[7 + 3 * a + b] += wp[a] * q[b];
+        acc[16] += wp[0] * p[0] + wp[1] * p[1] + wp[2] * p[2];
+        acc[17] += w * (double)d2;
+    } else {
+        const double e1[3] = {(double)t.bx - (double)t.ax, (double)t.by - (double)t.ay, (double)t.bz - (double)t.az};
+        const double e2[3] = {(double)t.cx - (double)t.ax, (double)t.cy - (double)t.ay, (double)t.cz - (double)t.az};
+        double N[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        double nn = N[0] * N[0] + N[1] * N[1] + N[2] * N[2];
+        if (!(nn > 0.0)) {
+_Pragma("unroll")
+            for (int a = 0; a < 3; ++a) N[a] = p[a] - q[a];
+            nn = N[0] * N[0] + N[1] * N[1] + N[2] * N[2];
+        }
+        if (nn > 0.0) {
+            const double gw = w / nn;
+            const double J[7] = {p[1] * N[2] - p[2] * N[1], p[2] * N[0] - p[0] * N[2], p[0] * N[1] - p[1] * N[0], N[0], N[1], N[2],
+                                 p[0] * N[0] + p[1] * N[1] + p[2] * N[2]};
+            const double R = N[0] * (q[0] - p[0]) + N[1] * (q[1] - p[1]) + N[2] * (q[2] - p[2]);
+            int k = 0;
+_Pragma("unroll")
+            for (int a = 0; a < 7; ++a) {
+                const double gj = gw * J[a];
+_Pragma("unroll")
+                for (int b = a; b < 7; ++b) acc[k++] += gj * J[b];
+                acc[28 + a] += gj * R;
+            }
+        }
+        acc[35] += w;
+        acc[36] += w * (double)d2;
+    }
+}
+
+// The reduction order, stated on the host (the kernels do the same with shuffles and LDS): lane l of a wave holds v[l];
+// the butterfly v[l] += v[l ^ d] for d = 32, 16, 8, 4, 2, 1 leaves the wave's sum in every lane (a + b is commutative, so
+// all lanes hold the same bits); the four waves of a block are then added in index order, ((s0 + s1) + s2) + s3.
+R3G_MD_HD double fit_tree256(const double* v) {
+    double s[4];
+    for (int wv = 0; wv < 4; ++wv) {
+        double a[64], b[64];
+        for (int l = 0; l < 64; ++l) a[l] = v[64 * wv + l];
+        for (int d = 32; d >= 1; d >>= 1) {
+            for (int l = 0; l < 64; ++l) b[l] = a[l] + a[l ^ d];
+            for (int l = 0; l < 64; ++l) a[l] = b[l];
+        }
+        s[wv] = a[0];
+    }
+    return ((s[0] + s[1]) + s[2]) + s[3];
 }
 
 }  // namespace r3g_md

@@ -9,6 +9,7 @@
 #include "../../include/r3g.h"
 #include "r3g_ctx.h"
 #include "mesh_kernels.h"
+#include "meshfit_core.h"
 #include "tex_kernels.h"
 
 namespace r3g {
@@ -138,6 +139,8 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->mesh_ws) (void)hipFree(c->mesh_ws);
     if (c->meshdist_ws) (void)hipFree(c->meshdist_ws);
     if (c->meshdist_pairs) (void)hipFree(c->meshdist_pairs);
+    if (c->meshfit_ws) (void)hipFree(c->meshfit_ws);
+    if (c->h_fit) (void)hipHostFree(c->h_fit);
     if (c->meshinside_ws) (void)hipFree(c->meshinside_ws);
     if (c->meshinside_pairs) (void)hipFree(c->meshinside_pairs);
     if (c->tex_ws) (void)hipFree(c->tex_ws);
@@ -402,6 +405,122 @@ int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, fl
     int rc = meshdist_small(c, s, &sm);
     if (rc) return rc;
     meshdist_add_tests((int64_t)sm.tests);
+    return R3G_OK;
+}
+
+// ---- mesh registration ------------------------------------------------------------------------
+int r3g_meshdist_closest(r3g_ctx* ctx, const float* d_points, int64_t n_points, float* d_dist2, int32_t* d_face, float* d_closest,
+                         void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->meshdist_built) return fail(R3G_ERR_STATE, "r3g_meshdist_closest: no successful r3g_meshdist_build on this context");
+    if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: n_points out of range");
+    if (n_points == 0) return R3G_OK;
+    if (!d_points || !d_dist2 || !d_face || !d_closest) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: null buffer");
+    hipError_t e = meshfit_closest(c->meshdist_ws, c->meshdist_lay, c->meshdist_grid, (const int32_t*)c->meshdist_pairs, d_points,
+                                   n_points, d_dist2, d_face, d_closest, (hipStream_t)stream);
+    return e == hipSuccess ? R3G_OK : hip_fail(e, "meshfit_closest");
+}
+
+// one accumulation under x -> the record in c->h_fit
+static int meshfit_accumulate(Ctx* c, const float* d_points, int64_t n, const float* d_weights, const r3g_md::Sim& x, int mode,
+                              double max_dist, hipStream_t s, MeshfitRecord* out) {
+    int rc = c->reserve(&c->meshfit_ws, &c->meshfit_ws_bytes, meshfit_workspace_bytes(), "hipMalloc(meshfit workspace)");
+    if (rc) return rc;
+    if (!c->h_fit) {
+        hipError_t e = hipHostMalloc((void**)&c->h_fit, sizeof(MeshfitRecord), hipHostMallocDefault);
+        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(meshfit)");
+    }
+    const float md2 = (float)(max_dist * max_dist);
+    hipError_t e = meshfit_step(c->meshfit_ws, c->meshdist_ws, c->meshdist_lay, c->meshdist_grid, (const int32_t*)c->meshdist_pairs,
+                                d_points, n, d_weights, x, mode, md2, s);
+    if (e != hipSuccess) return hip_fail(e, "meshfit_step");
+    e = hipMemcpyAsync(c->h_fit, c->meshfit_ws, sizeof(MeshfitRecord), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshfit)");
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshfit)");
+    memcpy(out, c->h_fit, sizeof(MeshfitRecord));
+    meshfit_add_steps(1);
+    meshdist_add_tests((int64_t)out->tests);
+    return R3G_OK;
+}
+
+static int meshfit_check(const char* who, Ctx* c, const float* d_points, int64_t n, int mode, double max_dist) {
+    if (!c->meshdist_built) return fail(R3G_ERR_STATE, "%s: no successful r3g_meshdist_build on this context", who);
+    if (n < 0 || n >= (1ll << 31)) return fail(R3G_ERR_INVALID, "%s: n_points out of range", who);
+    if (mode != r3g_md::kFitPoint && mode != r3g_md::kFitPlane) return fail(R3G_ERR_INVALID, "%s: mode must be 0 (point) or 1 (plane)", who);
+    if (!(max_dist >= 0.0)) return fail(R3G_ERR_INVALID, "%s: max_dist must be >= 0 (+inf: no limit)", who);
+    if (n && !d_points) return fail(R3G_ERR_INVALID, "%s: null buffer", who);
+    return R3G_OK;
+}
+
+int r3g_meshfit_step(r3g_ctx* ctx, const float* d_points, int64_t n_points, const float* d_weights, const double* xform, int mode,
+                     double max_dist, double* sums_out, int64_t* used_out, void* stream) {
+    if (!ctx || !xform || !sums_out || !used_out) return fail(R3G_ERR_INVALID, "r3g_meshfit_step: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    int rc = meshfit_check("r3g_meshfit_step", c, d_points, n_points, mode, max_dist);
+    if (rc) return rc;
+    for (int i = 0; i < r3g_md::kFitMaxTerms; ++i) sums_out[i] = 0.0;
+    *used_out = 0;
+    if (n_points == 0) return R3G_OK;
+    r3g_md::Sim x;
+    x.s = xform[0];
+    for (int i = 0; i < 9; ++i) x.r[i] = xform[1 + i];
+    for (int i = 0; i < 3; ++i) x.t[i] = xform[10 + i];
+    MeshfitRecord rec;
+    if ((rc = meshfit_accumulate(c, d_points, n_points, d_weights, x, mode, max_dist, (hipStream_t)stream, &rec))) return rc;
+    for (int i = 0; i < r3g_md::fit_terms(mode); ++i) sums_out[i] = rec.sums[i];
+    *used_out = (int64_t)rec.used;
+    return R3G_OK;
+}
+
+int r3g_meshfit(r3g_ctx* ctx, const float* d_points, int64_t n_points, const float* d_weights, const double* init, int mode,
+                int with_scale, int max_iterations, double tolerance, double max_dist, double* matrix_out, double* info_out,
+                void* stream) {
+    if (!ctx || !matrix_out || !info_out) return fail(R3G_ERR_INVALID, "r3g_meshfit: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    int rc = meshfit_check("r3g_meshfit", c, d_points, n_points, mode, max_dist);
+    if (rc) return rc;
+    if (max_iterations < 0) return fail(R3G_ERR_INVALID, "r3g_meshfit: max_iterations must be >= 0");
+    if (!(tolerance == tolerance)) return fail(R3G_ERR_INVALID, "r3g_meshfit: tolerance is NaN");
+    r3g_md::Sim cur = r3g_mf::identity();
+    if (init && !r3g_mf::from_matrix(init, &cur))
+        return fail(R3G_ERR_INVALID, "r3g_meshfit: init is not a similarity [s R | t; 0 0 0 1] with s > 0 and det R = +1");
+    double rms = 0.0, rms_prev = 0.0;
+    int64_t used = 0;
+    int updates = 0, converged = 0;
+    if (n_points > 0) {
+        double centre[3];
+        r3g_md::fit_centre(c->meshdist_grid, centre);
+        const int iw = mode == r3g_md::kFitPlane ? 35 : 0, id = mode == r3g_md::kFitPlane ? 36 : 17;
+        for (int it = 0;; ++it) {
+            MeshfitRecord rec;
+            if ((rc = meshfit_accumulate(c, d_points, n_points, d_weights, cur, mode, max_dist, (hipStream_t)stream, &rec))) return rc;
+            if (rec.used < 3 || !(rec.sums[iw] > 0.0))
+                return fail(R3G_ERR_INVALID, "r3g_meshfit: too few points: %lld of %lld within max_dist in iteration %d (3 needed, with positive weight)",
+                            (long long)rec.used, (long long)n_points, it);
+            used = (int64_t)rec.used;
+            rms = sqrt(rec.sums[id] / rec.sums[iw]);
+            if (it > 0 && fabs(rms_prev - rms) < tolerance) {
+                converged = 1;
+                break;
+            }
+            if (it >= max_iterations) break;
+            r3g_md::Sim delta;
+            const bool ok = mode == r3g_md::kFitPlane ? r3g_mf::solve_plane(rec.sums, with_scale != 0, centre, &delta)
+                                                      : r3g_mf::solve_point(rec.sums, with_scale != 0, centre, &delta);
+            if (!ok) return fail(R3G_ERR_INVALID, "r3g_meshfit: non-finite sums in iteration %d (a non-finite weight?)", it);
+            cur = r3g_mf::compose(delta, cur);
+            ++updates;
+            rms_prev = rms;
+        }
+    }
+    r3g_mf::to_matrix(cur, matrix_out);
+    info_out[0] = (double)updates;
+    info_out[1] = (double)converged;
+    info_out[2] = rms;
+    info_out[3] = (double)used;
+    info_out[4] = cur.s;
     return R3G_OK;
 }
 

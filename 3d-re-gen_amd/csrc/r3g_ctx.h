@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "mc_kernels.h"
 #include "meshdist_kernels.h"
+#include "meshfit_kernels.h"
 #include "meshinside_kernels.h"
 
 namespace r3g {
@@ -48,6 +49,11 @@ struct Ctx {
     MeshdistLayout meshdist_lay{};
     r3g_md::Grid meshdist_grid{};
     bool meshdist_built = false;
+    // mesh registration: the partial records of a fit step, and the pinned buffer its result is read back through (the sums
+    // do not fit h_small); both made on first use
+    char* meshfit_ws = nullptr;
+    size_t meshfit_ws_bytes = 0;
+    char* h_fit = nullptr;
     // point in mesh: the columns of the last r3g_meshinside_build (separate from the distance grid: both may be held at once)
     char* meshinside_ws = nullptr;
     size_t meshinside_ws_bytes = 0;

@@ -3,7 +3,7 @@
 `trimesh` is what the reference stage holds between shapegen, the cleaners and `mesh.export(path)`
 (src/2d_to_3d_models/run.py:84-102); it is not installed in this image, so this class provides the
 attributes that script touches: .vertices, .faces, .is_empty, .export(path), update_vertices,
-update_faces, remove_unreferenced_vertices, nondegenerate_faces, process.  The GLB carries POSITION
+update_faces, remove_unreferenced_vertices, nondegenerate_faces, process, plus apply_transform, closest_point and register.  The GLB carries POSITION
 (float32) + uint32 indices (+ optional per-vertex COLOR_0, + optional TEXCOORD_0 with a PNG baseColorTexture), which is
 what the downstream consumer loads with load_textures=True (src/scene_reconstruction/source/pose_matching_planar.py:882-906).
 """
@@ -145,6 +145,48 @@ class Mesh:
         if self.is_empty or other.is_empty:
             raise ValueError("Mesh.distance_to: an empty mesh has no distance")
         return meshdist.compare(self.device_buffers(), other.device_buffers(), **kw)
+
+    def apply_transform(self, matrix):
+        """trimesh.Trimesh.apply_transform: move the vertices by a 4 x 4 homogeneous matrix, in place -> self.  A matrix with
+        negative determinant mirrors the mesh, so the faces' winding is flipped to keep the normals pointing outward."""
+        m = np.asarray(matrix, np.float64)
+        if m.shape != (4, 4) or not np.isfinite(m).all():
+            raise ValueError("Mesh.apply_transform: expected a finite 4 x 4 matrix")
+        flip = np.linalg.det(m[:3, :3]) < 0.0
+        if self._v is None:
+            import torch
+            mt = torch.from_numpy(m).to(self._dv.device)
+            self._dv = (self._dv.to(torch.float64) @ mt[:3, :3].T + mt[:3, 3]).to(torch.float32)
+            if flip:
+                self._df = self._df[:, [0, 2, 1]].contiguous()
+        else:
+            f = self.faces
+            self.vertices = self.vertices @ m[:3, :3].T + m[:3, 3]
+            if flip:
+                self.faces = f[:, ::-1]
+        return self
+
+    def closest_point(self, points):
+        """trimesh.proximity.closest_point(mesh, points): (closest [N,3], distance [N], face id [N]) of points [N,3] on this
+        mesh, by r3g.meshdist.closest_point on the device buffers.  numpy in, numpy out; a torch tensor gives CUDA tensors."""
+        from . import meshdist
+        if self.is_empty:
+            raise ValueError("Mesh.closest_point: an empty mesh has no closest point")
+        v, f = self.device_buffers()
+        p, host = self._query_points(points, "closest_point")
+        q, d, face = meshdist.closest_point(p, v, f)
+        return (q.cpu().numpy(), d.cpu().numpy(), face.cpu().numpy()) if host else (q, d, face)
+
+    def register(self, other, **kw):
+        """trimesh.Trimesh.register: align this mesh onto `other` -> (matrix float64 [4,4], cost).  r3g.meshfit.align of this
+        mesh's area-weighted surface samples onto `other` (keywords: method, with_scale, init, inits, max_iterations,
+        tolerance, max_dist, samples, seed); cost = the weighted rms distance after the fit.  The mesh itself is not moved:
+        apply_transform(matrix) does that."""
+        from . import meshfit
+        if self.is_empty or other.is_empty:
+            raise ValueError("Mesh.register: an empty mesh cannot be registered")
+        matrix, info = meshfit.align(self.device_buffers(), other.device_buffers(), **kw)
+        return matrix, info["rms"]
 
     def _query_points(self, points, what):
         """points as a CUDA float32 tensor on the mesh's device, and whether they came as a host array"""

@@ -82,6 +82,38 @@ def nearest(points, verts, faces, resolution=None):
     return d2.sqrt(), face
 
 
+def closest(points):
+    """r3g_meshdist_closest against the last build on the points' device
+    -> (dist2 float32 [N], face int32 [N], closest float32 [N,3]); dist2 and face are `query`'s"""
+    if not (torch.is_tensor(points) and points.is_cuda):
+        raise ValueError("query points must live on the GPU (there is no CPU path)")
+    p = points.detach().to(torch.float32).contiguous()
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("expected points [N,3]")
+    dev = p.device.index or 0
+    d2 = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
+    face = torch.empty(p.shape[0], dtype=torch.int32, device=p.device)
+    q = torch.empty((p.shape[0], 3), dtype=torch.float32, device=p.device)
+    with ffi.device_lock(dev), torch.cuda.device(p.device):
+        ffi.check(ffi.lib().r3g_meshdist_closest(ffi.context(dev), ctypes.c_void_p(p.data_ptr()), p.shape[0],
+                                                 ctypes.c_void_p(d2.data_ptr()), ctypes.c_void_p(face.data_ptr()),
+                                                 ctypes.c_void_p(q.data_ptr()), _stream_ptr()))
+    return d2, face, q
+
+
+def closest_point(points, verts, faces, resolution=None):
+    """trimesh.proximity.closest_point: for every point the closest point of the mesh, its distance and the face that holds
+    it -> (closest float32 [N,3], dist float32 [N], face int32 [N]).  dist and face are `nearest`'s; closest is tri_closest of
+    csrc/meshdist_core.h on that face.  A point with a non-finite coordinate gets (NaN, NaN, -1).  CUDA tensors only."""
+    if not (torch.is_tensor(points) and points.is_cuda):
+        raise ValueError("query points must live on the GPU (there is no CPU path)")
+    dev = points.device.index or 0
+    with ffi.device_lock(dev):
+        build(verts, faces, resolution)
+        d2, face, q = closest(points)
+    return q, d2.sqrt(), face
+
+
 def face_areas(verts, faces):
     """float64 [F]; a face with a non-finite vertex has area 0"""
     t = verts.to(torch.float64)[faces.long()]

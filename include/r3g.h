@@ -180,6 +180,46 @@ int r3g_meshinside_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, co
                          int axis, int resolution, int* resolution_out, int64_t* pairs_out, int64_t* skipped_out, void* stream);
 int r3g_meshinside_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, int32_t* d_count, void* stream);
 
+/* ---- mesh registration ----------------------------------------------------------------
+ * Closest points and iterative closest point (ICP) of a point set onto a mesh, the alignment that the distances above
+ * presuppose (r3g/meshfit.py).  All three calls work against the grid of the last successful r3g_meshdist_build on the
+ * context (none: R3G_ERR_STATE) and leave it as it is.
+ *
+ * r3g_meshdist_closest: r3g_meshdist_query plus the point that attains the distance: d_closest float32 [n_points][3] =
+ *   tri_closest(p_i, face) (csrc/meshdist_core.h: candidates in the order edge ab, bc, ac, interior; a later one wins only
+ *   when strictly nearer), d_dist2 and d_face exactly as r3g_meshdist_query gives them.  A point with a non-finite coordinate
+ *   gets NaN, -1 and NaN.  n_points == 0 is a no-op.  Enqueues on `stream` and does not synchronise.
+ * r3g_meshfit_step: ONE accumulation of the registration, no solve.  xform = 13 doubles: s, R (row-major, 9), t.  Each source
+ *   point d_points[i] (float32) is moved to p' = s R p + t in float64 and rounded to float32; q = the closest point of the mesh
+ *   to p', d2 its squared distance.  The point takes part iff p' is finite and d2 <= (float)(max_dist^2) (max_dist = +inf: every
+ *   finite point), with weight w_i = d_weights[i] (float32, finite, >= 0; NULL: 1).  mode 0 (point): sums_out[0..18) =
+ *   W, sum w p', sum w q, sum w p' q^T (row = p'), sum w |p'|^2, sum w d2.  mode 1 (plane): sums_out[0..37) = the upper triangle
+ *   of sum w j j^T (28, row-major), sum w j r (7), W, sum w d2, with j = [p' x n, n, p' . n], r = n . (q - p'), n the unit normal
+ *   of the winning face ((p' - q) / |p' - q| for a face without area; a point with neither adds W and d2 only), evaluated
+ *   without a square root as (w / N.N) J J^T and (w / N.N) J R on the unnormalised normal N.  p' and q are taken relative to
+ *   the centre of the grid's box, c = (lo + hi) / 2 in float64.  sums_out must hold 37 doubles (host memory); *used_out = the points
+ *   that took part.  The sums are added in float64 in a fixed order (wave butterfly, the block's four waves in
+ *   index order, the blocks' records in index order by the same tree; no floating-point atomics), so they are a pure function
+ *   of the mesh, the points, the weights and xform, independent of the grid's resolution; tests/emu/meshfit_emu.cpp reproduces
+ *   them bit for bit on the host.  n_points == 0 gives zeros.  Synchronises `stream`.
+ * r3g_meshfit: the loop accumulate -> solve -> compose on the host.  init = row-major 4 x 4 similarity (NULL: identity; not
+ *   a similarity with positive determinant: R3G_ERR_INVALID).  mode 1 = point-to-plane (one Gauss-Newton step per iteration:
+ *   Cholesky of the 6 x 6 normal equations, 7 x 7 with_scale; an unconstrained degree of freedom stays 0), mode 0 = the closed
+ *   form on closest points (Horn / Umeyama).  Each iteration accumulates under the current transform and stops, before solving,
+ *   when |rms_prev - rms| < tolerance or when max_iterations updates have been made; so matrix_out (row-major 4 x 4, maps
+ *   source onto target) is the transform the last accumulation ran under.  info_out = 5 doubles: updates made, converged (0 | 1),
+ *   rms = sqrt(sum w d2 / W) of the last accumulation, points used in it, scale of matrix_out.  Errors: mode outside 0..1,
+ *   max_dist < 0 or NaN, max_iterations < 0, tolerance NaN: R3G_ERR_INVALID; an accumulation with fewer than 3 points used or
+ *   W <= 0: R3G_ERR_INVALID ("too few points"), matrix_out untouched.  n_points == 0: matrix_out = init, used 0, rms 0.
+ *   Synchronises `stream` once per accumulation (one 320-byte read-back through a pinned buffer of the context). */
+int r3g_meshdist_closest(r3g_ctx* ctx, const float* d_points, int64_t n_points, float* d_dist2, int32_t* d_face, float* d_closest,
+                         void* stream);
+int r3g_meshfit_step(r3g_ctx* ctx, const float* d_points, int64_t n_points, const float* d_weights, const double* xform, int mode,
+                     double max_dist, double* sums_out, int64_t* used_out, void* stream);
+int r3g_meshfit(r3g_ctx* ctx, const float* d_points, int64_t n_points, const float* d_weights, const double* init, int mode,
+                int with_scale, int max_iterations, double tolerance, double max_dist, double* matrix_out, double* info_out,
+                void* stream);
+
 /* ---- texture stage: native pieces ------------------------------------------------------------
  * SURVEY.md 8(f) rank 3.  Upstream's Hunyuan3DPaintPipeline (reference call site src/2d_to_3d_models/run.py:97, built at
  * :126-128) uses two native extensions, `custom_rasterizer` (CUDA) and `mesh_processor.cpp`, and bakes the generated views
@@ -674,8 +714,9 @@ int r3g_get_option(const char* name, int* value);
  * again; r3g_grid_query_points and the coarse levels of r3g_grid_query_hier never do).
  * "geo_kv_groups": (group, head) selections of top-k KV selection so far.
  * "geo_narrow_passes": grid passes served by the fused tail of a narrow geo decoder ("geo_narrow_fused") so far.
- * "meshdist_tests": point-triangle tests made by r3g_meshdist_query so far.
+ * "meshdist_tests": point-triangle tests made by r3g_meshdist_query, and by the walks of r3g_meshfit_step / r3g_meshfit, so far.
  * "meshinside_tests": point-face tests made by r3g_meshinside_query so far.
+ * "meshfit_steps": accumulation launches of the mesh registration (r3g_meshfit_step, and each one r3g_meshfit makes) so far.
  * "geo_lnf_passes" / "geo_lnd_passes": geo decoder passes that took the folded ln_3 ("geo_ln3_fold") / ln_post + output_proj
  * ("geo_lnd_fused") epilogues.
  * Kernel-choice counters, one per form a launch can end in, bumped on the host where the launch is issued (tests read them to see
