@@ -6,5 +6,16 @@ The reference stage imports trimesh only for `isinstance(mesh, trimesh.Trimesh)`
 trimesh is installed."""
 from r3g.mesh import Mesh as Trimesh, load_glb as load  # noqa: F401
 
+import sys as _sys
+
+if __name__ in _sys.modules:      # `import trimesh.repair`: fix_winding, fix_normals, fix_inversion, broken_faces on the GPU
+    from . import repair  # noqa: F401
+else:       # executed from its file under a name that is not in sys.modules: there is no package to import from
+    import importlib.util as _util
+    import os as _os
+    _spec = _util.spec_from_file_location(__name__ + ".repair", _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "repair.py"))
+    repair = _util.module_from_spec(_spec)
+    _spec.loader.exec_module(repair)
+
 __r3g_compat__ = True
 __version__ = "0+r3g.compat"

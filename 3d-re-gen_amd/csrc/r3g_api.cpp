@@ -143,6 +143,8 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->h_fit) (void)hipHostFree(c->h_fit);
     if (c->meshinside_ws) (void)hipFree(c->meshinside_ws);
     if (c->meshinside_pairs) (void)hipFree(c->meshinside_pairs);
+    if (c->meshtopo_ws) (void)hipFree(c->meshtopo_ws);
+    if (c->h_topo) (void)hipHostFree(c->h_topo);
     if (c->tex_ws) (void)hipFree(c->tex_ws);
     if (c->hier_ws) (void)hipFree(c->hier_ws);
     if (c->h_small) (void)hipHostFree(c->h_small);
@@ -604,6 +606,145 @@ int r3g_meshinside_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, 
     int rc = meshinside_small(c, s, &sm);
     if (rc) return rc;
     meshinside_add_tests((int64_t)sm.tests);
+    return R3G_OK;
+}
+
+// ---- mesh topology ------------------------------------------------------------------------------------------------
+static int meshtopo_small(Ctx* c, hipStream_t s, r3g_mt::Small* out) {
+    hipError_t e = hipMemcpyAsync(c->h_topo, c->meshtopo_ws + c->meshtopo_lay.off_small, sizeof(r3g_mt::Small), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshtopo)");
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshtopo)");
+    memcpy(out, c->h_topo, sizeof(r3g_mt::Small));
+    return R3G_OK;
+}
+
+// the build behind r3g_meshtopo_build and r3g_meshtopo_orient (arguments checked by the caller)
+static int meshtopo_build(Ctx* c, const char* who, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces,
+                          hipStream_t s) {
+    c->meshtopo_built = false;
+    int rc;
+    if (!c->h_topo) {
+        hipError_t e = hipHostMalloc((void**)&c->h_topo, 256, hipHostMallocDefault);
+        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(meshtopo)");
+    }
+    MeshtopoLayout lay;
+    rc = c->reserve(&c->meshtopo_ws, &c->meshtopo_ws_bytes, meshtopo_workspace_bytes(n_verts, n_faces, &lay), "hipMalloc(meshtopo workspace)");
+    if (rc) return rc;
+    c->meshtopo_lay = lay;
+    hipError_t e = meshtopo_check(c->meshtopo_ws, lay, d_verts, n_verts, d_faces, n_faces, s);
+    if (e != hipSuccess) return hip_fail(e, "meshtopo_check");
+    r3g_mt::Small sm;
+    if ((rc = meshtopo_small(c, s, &sm))) return rc;
+    // (-2 by the contract of include/r3g.h: found on the device, before anything is read through the index)
+    if (sm.bad_index) return fail(-2, "%s: a face index lies outside [0, %lld)", who, (long long)n_verts);
+    e = meshtopo_edges(c->meshtopo_ws, lay, d_faces, n_faces, s);
+    if (e != hipSuccess) return hip_fail(e, "meshtopo_edges");
+    int rounds = 0;
+    for (;;) {
+        if (rounds == r3g_mt::kMaxRounds) {
+            meshtopo_add_counters(0, rounds);
+            return fail(R3G_ERR_INVALID, "%s: the body labels still move after %d rounds; no labelling is returned", who, rounds);
+        }
+        e = meshtopo_round(c->meshtopo_ws, lay, n_faces, s);
+        if (e != hipSuccess) return hip_fail(e, "meshtopo_round");
+        ++rounds;
+        if ((rc = meshtopo_small(c, s, &sm))) return rc;
+        if (!sm.changed) break;
+    }
+    e = meshtopo_finish(c->meshtopo_ws, lay, d_verts, d_faces, n_faces, s);
+    if (e != hipSuccess) return hip_fail(e, "meshtopo_finish");
+    if ((rc = meshtopo_small(c, s, &sm))) return rc;      // (also: the caller may free its buffers, a fault would surface here)
+    meshtopo_add_counters(1, rounds);
+    int64_t* r = c->meshtopo_report;
+    r[0] = (int64_t)sm.usable, r[1] = (int64_t)sm.skipped, r[2] = (int64_t)sm.vref, r[3] = (int64_t)sm.edges;
+    r[4] = (int64_t)sm.boundary, r[5] = (int64_t)sm.clash, r[6] = (int64_t)sm.nonmanifold;
+    r[7] = (int64_t)sm.bodies, r[8] = (int64_t)sm.unorientable;
+    r[9] = r[2] - r[3] + r[0];
+    r[10] = (int64_t)sm.nonfinite;
+    r[11] = sm.six_volume_q, r[12] = r3g_mt::vol_scale(sm.max_bits);
+    r[13] = sm.two_area_q, r[14] = r3g_mt::area_scale(sm.max_bits);
+    r[15] = d_verts ? 1 : 0;
+    c->meshtopo_nf = n_faces;
+    c->meshtopo_built = true;
+    return R3G_OK;
+}
+
+static int meshtopo_args(const char* who, const float* d_verts, int64_t n_verts, const void* d_faces, int64_t n_faces) {
+    if (n_verts < 0 || n_verts >= (1ll << 31) || n_faces < 0 || n_faces > r3g_mt::kMaxFaces)
+        return fail(R3G_ERR_INVALID, "%s: mesh size out of range (at most 2^29 faces)", who);
+    if (n_faces == 0) return fail(R3G_ERR_INVALID, "%s: the mesh has no face", who);
+    if (!d_faces) return fail(R3G_ERR_INVALID, "%s: null buffer", who);
+    (void)d_verts;
+    return R3G_OK;
+}
+
+int r3g_meshtopo_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces, int64_t* report,
+                       void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshtopo_build: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    c->meshtopo_built = false;
+    int rc = meshtopo_args("r3g_meshtopo_build", d_verts, n_verts, d_faces, n_faces);
+    if (rc) return rc;
+    if ((rc = meshtopo_build(c, "r3g_meshtopo_build", d_verts, n_verts, d_faces, n_faces, (hipStream_t)stream))) return rc;
+    if (report) memcpy(report, c->meshtopo_report, sizeof c->meshtopo_report);
+    return R3G_OK;
+}
+
+int r3g_meshtopo_report(r3g_ctx* ctx, int64_t* report) {
+    if (!ctx || !report) return fail(R3G_ERR_INVALID, "r3g_meshtopo_report: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->meshtopo_built) return fail(R3G_ERR_STATE, "r3g_meshtopo_report: no successful r3g_meshtopo_build on this context");
+    memcpy(report, c->meshtopo_report, sizeof c->meshtopo_report);
+    return R3G_OK;
+}
+
+int r3g_meshtopo_mates(r3g_ctx* ctx, int32_t* d_mate, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshtopo_mates: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->meshtopo_built) return fail(R3G_ERR_STATE, "r3g_meshtopo_mates: no successful r3g_meshtopo_build on this context");
+    if (!d_mate) return fail(R3G_ERR_INVALID, "r3g_meshtopo_mates: null buffer");
+    hipError_t e = hipMemcpyAsync(d_mate, c->meshtopo_ws + c->meshtopo_lay.off_mate, 12 * (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice,
+                                  (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshtopo mates)");
+    return R3G_OK;
+}
+
+int r3g_meshtopo_bodies(r3g_ctx* ctx, int32_t* d_body, uint8_t* d_flip, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshtopo_bodies: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->meshtopo_built) return fail(R3G_ERR_STATE, "r3g_meshtopo_bodies: no successful r3g_meshtopo_build on this context");
+    hipError_t e = hipSuccess;
+    if (d_body) e = hipMemcpyAsync(d_body, c->meshtopo_ws + c->meshtopo_lay.off_body, 4 * (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess && d_flip)
+        e = hipMemcpyAsync(d_flip, c->meshtopo_ws + c->meshtopo_lay.off_flip, (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshtopo bodies)");
+    return R3G_OK;
+}
+
+int r3g_meshtopo_orient(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, int32_t* d_faces, int64_t n_faces, int outward,
+                        int64_t* faces_reversed, int64_t* bodies_reversed, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshtopo_orient: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    c->meshtopo_built = false;
+    int rc = meshtopo_args("r3g_meshtopo_orient", d_verts, n_verts, d_faces, n_faces);
+    if (rc) return rc;
+    if (outward < 0 || outward > 2) return fail(R3G_ERR_INVALID, "r3g_meshtopo_orient: outward must be 0, 1 or 2");
+    if (outward && !d_verts) return fail(R3G_ERR_INVALID, "r3g_meshtopo_orient: outward != 0 needs the vertices");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = meshtopo_build(c, "r3g_meshtopo_orient", d_verts, n_verts, d_faces, n_faces, s))) return rc;
+    c->meshtopo_built = false;                    // until the state describes the faces as this call leaves them
+    hipError_t e = meshtopo_apply(c->meshtopo_ws, c->meshtopo_lay, d_faces, n_faces, outward, s);
+    if (e != hipSuccess) return hip_fail(e, "meshtopo_apply");
+    r3g_mt::Small sm;
+    if ((rc = meshtopo_small(c, s, &sm))) return rc;
+    if (sm.faces_reversed) {
+        if ((rc = meshtopo_build(c, "r3g_meshtopo_orient", d_verts, n_verts, d_faces, n_faces, s))) return rc;
+    } else {
+        c->meshtopo_built = true;
+    }
+    if (faces_reversed) *faces_reversed = (int64_t)sm.faces_reversed;
+    if (bodies_reversed) *bodies_reversed = (int64_t)sm.bodies_reversed;
     return R3G_OK;
 }
 

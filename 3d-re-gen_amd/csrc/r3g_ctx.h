@@ -12,6 +12,7 @@
 #include "meshdist_kernels.h"
 #include "meshfit_kernels.h"
 #include "meshinside_kernels.h"
+#include "meshtopo_kernels.h"
 
 namespace r3g {
 
@@ -63,6 +64,16 @@ struct Ctx {
     r3g_mi::Grid2 meshinside_grid{};
     int meshinside_axis = 0;
     bool meshinside_built = false;
+    // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
+    // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
+    // fit h_small), made on first use
+    char* meshtopo_ws = nullptr;
+    size_t meshtopo_ws_bytes = 0;
+    char* h_topo = nullptr;
+    MeshtopoLayout meshtopo_lay{};
+    int64_t meshtopo_nf = 0;
+    int64_t meshtopo_report[16] = {0};
+    bool meshtopo_built = false;
     // texture stage (z-buffer / inpainting workspace)
     char* tex_ws = nullptr;
     size_t tex_ws_bytes = 0;

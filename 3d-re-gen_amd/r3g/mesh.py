@@ -224,6 +224,87 @@ class Mesh:
             raise ValueError("Mesh.volume_iou: an empty mesh has no volume")
         return meshinside.volume_iou(self.device_buffers(), other.device_buffers(), **kw)
 
+    # -- topology (r3g.meshtopo on the device buffers; an empty mesh answers False / 0 without a launch) ---------
+    def _topology(self):
+        """r3g.meshtopo.build's report of this mesh, or None for an empty mesh"""
+        if self.is_empty:
+            return None
+        from . import meshtopo
+        return meshtopo.build(*self.device_buffers())
+
+    @property
+    def is_watertight(self):
+        """trimesh.Trimesh.is_watertight: every edge is shared by exactly two faces"""
+        r = self._topology()
+        return bool(r and r["watertight"])
+
+    @property
+    def is_winding_consistent(self):
+        """trimesh.Trimesh.is_winding_consistent: no edge is run through twice in the same direction"""
+        r = self._topology()
+        return bool(r and r["winding_consistent"])
+
+    @property
+    def is_volume(self):
+        """trimesh.Trimesh.is_volume: watertight, consistently wound and of positive volume"""
+        r = self._topology()
+        return bool(r and r["watertight"] and r["winding_consistent"] and r["six_volume_q"] > 0)
+
+    @property
+    def euler_number(self):
+        """referenced vertices - edges + usable faces"""
+        r = self._topology()
+        return r["euler"] if r else 0
+
+    @property
+    def body_count(self):
+        """the number of bodies: sets of faces joined through edges that exactly two faces share"""
+        r = self._topology()
+        return r["bodies"] if r else 0
+
+    @property
+    def volume(self):
+        """trimesh.Trimesh.volume: the signed volume, sum of det[a, b, c] / 6 over the faces (negative: wound inward)"""
+        r = self._topology()
+        return r["volume"] if r else 0.0
+
+    @property
+    def area(self):
+        r = self._topology()
+        return r["area"] if r else 0.0
+
+    @property
+    def face_adjacency(self):
+        """trimesh.Trimesh.face_adjacency: int64 [M,2] face pairs that share an edge no third face has"""
+        if self.is_empty:
+            return np.zeros((0, 2), np.int64)
+        from . import meshtopo
+        return meshtopo.face_adjacency(*self.device_buffers()).cpu().numpy()
+
+    def _orient(self, outward):
+        from . import meshtopo
+        if self.is_empty:
+            return 0
+        v, f = self.device_buffers()
+        f, info = meshtopo._orient(v, f.clone(), outward)
+        if info["faces_reversed"]:
+            self._df = f
+            self._f = None if self._v is None else f.cpu().numpy().astype(np.int64)
+        return info["faces_reversed"]
+
+    def fix_normals(self, multibody=False):
+        """trimesh.Trimesh.fix_normals: consistent winding, normals outward (r3g.meshtopo.fix_normals), in place -> self"""
+        self._orient(1 if multibody else 2)
+        return self
+
+    def invert(self):
+        """trimesh.Trimesh.invert: reverse every face, (v0, v1, v2) -> (v2, v1, v0), in place -> self"""
+        if self._df is not None:
+            self._df = self._df.flip(1).contiguous()
+        if self._f is not None:
+            self._f = np.ascontiguousarray(self._f[:, ::-1])
+        return self
+
     def process(self, validate=False):
         """merge bit-identical vertices (trimesh.Trimesh.process default), drop degenerate faces if validate"""
         if len(self.vertices):

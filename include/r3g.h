@@ -220,6 +220,54 @@ int r3g_meshfit(r3g_ctx* ctx, const float* d_points, int64_t n_points, const flo
                 int with_scale, int max_iterations, double tolerance, double max_dist, double* matrix_out, double* info_out,
                 void* stream);
 
+/* ---- mesh topology --------------------------------------------------------------------
+ * Is the mesh a valid surface -- closed, manifold, consistently wound -- and the in-place repair of its winding
+ * (r3g/meshtopo.py; trimesh's face_adjacency, is_watertight, is_winding_consistent, euler_number, volume, area,
+ * repair.fix_winding, repair.fix_normals, repair.broken_faces).  Everything is a pure function of d_faces and n_verts, and
+ * for volume and area of d_verts (csrc/meshtopo_core.h; tests/emu/meshtopo_emu.cpp reproduces it exactly on the host): integer
+ * atomics only, and the order in which they land decides nothing.
+ *
+ * r3g_meshtopo_build: take the mesh (d_verts float32 [n_verts][3] or NULL, d_faces int32 [n_faces][3]) and leave on the context
+ *   mate int32 [n_faces][3], body int32 [n_faces], flip uint8 [n_faces] and the report.  A face is USABLE when its three indices are
+ *   pairwise different; the others are counted in `skipped` and take part in nothing.  Half-edge h = 3 f + k of usable face f runs
+ *   from v_k to v_(k+1)%3; an undirected edge has deg half-edges, n_fwd of them running from its lower to its higher vertex.
+ *       mate[h] = the other half-edge (deg = 2) | -1 boundary (deg = 1) | -2 non-manifold (deg >= 3) | -3 skipped face
+ *   A deg = 2 edge whose two half-edges run in the same direction is a CLASH.  Faces joined through deg = 2 edges form a body;
+ *   body[f] = the lowest face index of the body (-1: skipped).  A body is orientable iff bits flip[f] exist with
+ *   flip[f] ^ flip[g] = (the edge between f and g is a clash) over all its deg = 2 edges; flip is the one such assignment with
+ *   flip[body[f]] = 0, and 0 on every face of an unorientable body.
+ *   report (int64 [16], may be NULL): 0 usable faces, 1 skipped, 2 referenced vertices, 3 distinct edges, 4 boundary edges,
+ *   5 clashes, 6 non-manifold edges, 7 bodies, 8 unorientable bodies, 9 euler = [2] - [3] + [0], 10 nonfinite (usable faces with
+ *   a non-finite vertex), 11 six_volume_q, 12 its scale exponent s_vol, 13 two_area_q, 14 its scale exponent s_area, 15 whether
+ *   d_verts was given ([10] - [14] are 0 without).  six_volume_q = sum of llrint(det[a, b, c] * 2^s_vol) and two_area_q = sum of
+ *   llrint(|ab x ac| * 2^s_area) over the usable faces without a non-finite vertex (float64 arithmetic on the float32 inputs);
+ *   with e such that the largest finite |coordinate| of a referenced vertex is below 2^e, s_vol = 30 - 3 e and s_area = 29 - 2 e,
+ *   so 2^29 faces cannot overflow and |sum / 2^s - exact sum| <= faces * 2^-(s + 1).  watertight = ([0] > 0 and [4] == 0 and
+ *   [6] == 0); winding consistent = ([5] == 0).
+ *   A face index outside [0, n_verts): error -2, found on the device before anything is read through the index.  n_faces == 0 or
+ *   above 2^29: R3G_ERR_INVALID.  The body labels are found in rounds (counter "meshtopo_rounds") until one changes nothing; 1024
+ *   rounds without that: R3G_ERR_INVALID, and no partial labelling is kept.  A failed build leaves the context without a state.
+ *   Synchronises `stream` (one 136-byte read-back per round through a pinned buffer of the context).
+ * r3g_meshtopo_report / _mates / _bodies: the report, mate (d_mate int32 [n_faces][3]) and body / flip (either may be NULL) of the
+ *   last successful build or orient on this context (none: R3G_ERR_STATE).  The copies are enqueued on `stream`.
+ * r3g_meshtopo_orient: build, then rewrite d_faces in place -- a reversed face (v0, v1, v2) becomes (v2, v1, v0) -- so that every
+ *   orientable body is consistently wound (the faces with flip = 1 are reversed), and with outward = 1 (trimesh's multibody = True)
+ *   every orientable body whose quantised volume is then negative is reversed as a whole, with outward = 2 (trimesh's default)
+ *   every orientable body if the sum of the orientable bodies' volumes is then negative (the unorientable bodies, which are
+ *   never reversed, are left out of that sum: reversing what may be reversed negates it exactly, so the result is stable).
+ *   outward = 0 looks at no volume; 1 and 2 need d_verts.  A zero sum
+ *   changes nothing, unorientable bodies are never touched, and a face that both steps would reverse is not written at all.
+ *   *faces_reversed = the faces rewritten, *bodies_reversed = the bodies the outward step reversed (either may be NULL).  The state
+ *   left on the context describes the faces as this call leaves them (a second build when anything was reversed); a second call on
+ *   its own output reverses nothing.  Errors as r3g_meshtopo_build; outward outside 0..2: R3G_ERR_INVALID. */
+int r3g_meshtopo_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces, int64_t* report,
+                       void* stream);
+int r3g_meshtopo_report(r3g_ctx* ctx, int64_t* report);
+int r3g_meshtopo_mates(r3g_ctx* ctx, int32_t* d_mate, void* stream);
+int r3g_meshtopo_bodies(r3g_ctx* ctx, int32_t* d_body, uint8_t* d_flip, void* stream);
+int r3g_meshtopo_orient(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, int32_t* d_faces, int64_t n_faces, int outward,
+                        int64_t* faces_reversed, int64_t* bodies_reversed, void* stream);
+
 /* ---- texture stage: native pieces ------------------------------------------------------------
  * SURVEY.md 8(f) rank 3.  Upstream's Hunyuan3DPaintPipeline (reference call site src/2d_to_3d_models/run.py:97, built at
  * :126-128) uses two native extensions, `custom_rasterizer` (CUDA) and `mesh_processor.cpp`, and bakes the generated views
@@ -717,6 +765,8 @@ int r3g_get_option(const char* name, int* value);
  * "meshdist_tests": point-triangle tests made by r3g_meshdist_query, and by the walks of r3g_meshfit_step / r3g_meshfit, so far.
  * "meshinside_tests": point-face tests made by r3g_meshinside_query so far.
  * "meshfit_steps": accumulation launches of the mesh registration (r3g_meshfit_step, and each one r3g_meshfit makes) so far.
+ * "meshtopo_builds": successful builds of the mesh topology (r3g_meshtopo_build, and the one or two r3g_meshtopo_orient makes) so far.
+ * "meshtopo_rounds": label rounds those builds launched so far.
  * "geo_lnf_passes" / "geo_lnd_passes": geo decoder passes that took the folded ln_3 ("geo_ln3_fold") / ln_post + output_proj
  * ("geo_lnd_fused") epilogues.
  * Kernel-choice counters, one per form a launch can end in, bumped on the host where the launch is issued (tests read them to see
