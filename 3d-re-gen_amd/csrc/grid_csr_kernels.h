@@ -1,0 +1,57 @@
+// grid_csr_kernels.h -- host-side interface of the device build of a grid in CSR form (grid_csr.h; internal to libr3g.so):
+// what a build leaves behind, and the exclusive scan of grid_csr_kernels.hip.  The kernels that depend on the record type
+// are templates (grid_csr_device.h), instantiated by meshdist_kernels.hip and meshinside_kernels.hip.
+#ifndef R3G_GRID_CSR_KERNELS_H
+#define R3G_GRID_CSR_KERNELS_H
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "grid_csr.h"
+
+namespace r3g {
+
+// what the build leaves on the device for the query (all inside the user's workspace except the pair list)
+struct GridCsrLayout {
+    size_t off_small;     // GridCsrSmall
+    size_t off_recs;      // the user's 48-byte record [nf]
+    size_t off_counts;    // uint32 [cells + 1]: per-cell counts, then the fill cursors
+    size_t off_starts;    // uint32 [cells + 1]: CSR row starts
+    size_t off_sums;      // uint32 [scan tiles]
+    size_t total;
+};
+
+// the bytes read back through the context's 64-byte pinned buffer
+struct GridCsrSmall {
+    uint32_t bad_index;             // != 0: a face index outside [0, V)
+    uint32_t pad;
+    unsigned long long skipped;     // faces with a non-finite vertex
+    uint32_t box[6];                // enc_float of lo[D], hi[D] on the grid axes; the first 2 * D entries in use
+    unsigned long long pairs;       // (record, cell) pairs at the resolution last counted
+    unsigned long long tests;       // point-record tests of the last query
+};
+static_assert(sizeof(GridCsrSmall) == 56, "GridCsrSmall travels through the 64-byte pinned buffer");
+
+// what a user keeps in the context between its build and its queries
+template <int D>
+struct GridCsrState {
+    char* ws = nullptr;
+    size_t ws_bytes = 0;
+    char* pairs = nullptr;          // int32 [GridCsrSmall::pairs]: a buffer of its own
+    size_t pairs_bytes = 0;
+    GridCsrLayout lay{};
+    r3g_grid::GridN<D> grid{};
+    bool built = false;
+};
+
+constexpr int kCsrScanTile = 2048;                                    // elements per block of the scan
+constexpr int64_t kCsrScanMax = (int64_t)256 * 40 * kCsrScanTile;     // one block scans the tile sums: 10240 tiles at the most
+
+size_t grid_csr_workspace_bytes(int64_t nf, size_t record_bytes, int64_t cells, GridCsrLayout* lay);
+
+// starts[i] = counts[0] + ... + counts[i - 1] for i in [0, n1); sums: uint32 [ceil(n1 / kCsrScanTile)] of scratch.
+// hipErrorInvalidValue when n1 > kCsrScanMax.
+hipError_t csr_exclusive_scan(const unsigned* counts, unsigned* starts, int64_t n1, unsigned* sums, hipStream_t s);
+
+}  // namespace r3g
+#endif

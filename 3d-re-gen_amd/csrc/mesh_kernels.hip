@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "mesh_kernels.h"
+#include "mesh_launch.h"
 #include "prof.h"
 
 #pragma clang fp contract(off)
@@ -32,11 +33,8 @@
 namespace r3g {
 namespace {
 
-constexpr int kT = 256;
 constexpr int kItems = 8;                 // per thread in the scan kernels
 constexpr int kTile = kT * kItems;        // 2048 elements per block
-
-inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // ------------------------------------------------------------------ exclusive scan of 32-bit counts (flags)
 __device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* total) {
@@ -482,12 +480,6 @@ struct Arena {
         return p;
     }
 };
-
-#define R3G_HIP(x)                         \
-    do {                                   \
-        hipError_t e_ = (x);               \
-        if (e_ != hipSuccess) return e_;   \
-    } while (0)
 
 // out[i] = sum of in[0..i), *d_total = sum of all; scratch: block sums
 hipError_t exclusive_scan(const unsigned* in, int64_t n, unsigned* out, unsigned* bsum, unsigned* d_total,

@@ -9,15 +9,26 @@
 #define R3G_MESHDIST_CORE_H
 #include <stdint.h>
 
+#include "grid_csr.h"
+
 #ifndef R3G_MD_HD
 #define R3G_MD_HD static inline
 #endif
 
 namespace r3g_md {
 
+using r3g_grid::clamp;
+using r3g_grid::coord;
+using r3g_grid::dec_float;
+using r3g_grid::enc_float;
+using r3g_grid::finite;
+using r3g_grid::fmax2;
+using r3g_grid::fmin2;
+using r3g_grid::kPairMult;
+using r3g_grid::make_grid;
+using Grid = r3g_grid::GridN<3>;      // cells (section 4f)
+
 constexpr int kMaxRes = 256;                          // cap: 256^3 = 2^24 cells
-constexpr int kPairMult = 8;                          // automatic resolution: halve while pairs > kPairMult * F
-constexpr float kBinMargin = 1.0f / 256.0f;           // cells; widens a triangle's cell range (rounding can only add cells)
 constexpr float kSlackRel = 1.0f / 262144.0f;         // 2^-18 of the squared ring bound
 constexpr float kSlackAbs = 1.0f / 262144.0f;         // 2^-18 of the squared distance to the farthest corner of the box
 constexpr float kInf = __builtin_huge_valf();
@@ -33,30 +44,7 @@ struct alignas(16) Tri {
     int32_t pad2;
 };
 
-struct Grid {
-    float lo[3];
-    float hi[3];
-    float h[3];          // cell size per axis
-    float inv[3];        // 1 / h: defines the cell coordinate t = (x - lo) * inv
-    int res;             // cells per axis
-};
-
-R3G_MD_HD bool finite(float x) { return (x - x) == 0.0f; }
-R3G_MD_HD float fmin2(float a, float b) { return b < a ? b : a; }
-R3G_MD_HD float fmax2(float a, float b) { return b > a ? b : a; }
 R3G_MD_HD float fabs1(float a) { return a < 0.0f ? -a : a; }
-
-// order-preserving float -> uint32 (bounding box by integer atomicMin / atomicMax) and back
-R3G_MD_HD uint32_t enc_float(float x) {
-    union { float f; uint32_t u; } c;
-    c.f = x;
-    return (c.u & 0x80000000u) ? ~c.u : (c.u | 0x80000000u);
-}
-R3G_MD_HD float dec_float(uint32_t u) {
-    union { float f; uint32_t u; } c;
-    c.u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return c.f;
-}
 
 // the NaN a non-finite query point gets: one bit pattern on host and device (inf - inf has the sign bit set on x86 only)
 R3G_MD_HD float quiet_nan() {
@@ -66,13 +54,15 @@ R3G_MD_HD float quiet_nan() {
 }
 
 // squared distance from the point with offset (apx, apy, apz) = p - a to the segment a + t * ab, t in [0, 1];
-// a == b gives the point distance
-R3G_MD_HD float seg_dist2(float apx, float apy, float apz, float abx, float aby, float abz) {
+// a == b gives the point distance.  POINT: *t_out = the parameter of the closest point.
+template <bool POINT>
+R3G_MD_HD float seg_nearest(float apx, float apy, float apz, float abx, float aby, float abz, float* t_out) {
     const float den = abx * abx + aby * aby + abz * abz;
     const float num = apx * abx + apy * aby + apz * abz;
     float t = den > 0.0f ? num / den : 0.0f;
     t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
     const float qx = apx - t * abx, qy = apy - t * aby, qz = apz - t * abz;
+    if constexpr (POINT) *t_out = t;
     return qx * qx + qy * qy + qz * qz;
 }
 
@@ -80,23 +70,38 @@ R3G_MD_HD float seg_dist2(float apx, float apy, float apz, float abx, float aby,
 // vertex and edge regions, and are all there is of a degenerate triangle) and, where p projects strictly inside, the
 // interior point of Ericson's barycentric form (Real-Time Collision Detection 5.1.5).  Every candidate is the distance to
 // a point OF the triangle, so the value never undershoots the true distance by more than its own rounding.
-R3G_MD_HD float tri_dist2(float px, float py, float pz, const Tri& t) {
+// POINT: also the point that attains it, through r[3].  The candidates come in the order edges ab,
+// bc, ac, then the refined interior point; a later one replaces the point only when it is strictly nearer.  The point is
+// base + t * edge (edges) or a + v * ab + w * ac (interior), one float32 operation each, left to right.  One body: the
+// value is the same bits with and without the point, and without it nothing but the distance is computed.
+template <bool POINT>
+R3G_MD_HD float tri_nearest(float px, float py, float pz, const Tri& t, float* r) {
     const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az;
     const float acx = t.cx - t.ax, acy = t.cy - t.ay, acz = t.cz - t.az;
     const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
     const float apx = px - t.ax, apy = py - t.ay, apz = pz - t.az;
     const float bpx = px - t.bx, bpy = py - t.by, bpz = pz - t.bz;
     const float cpx = px - t.cx, cpy = py - t.cy, cpz = pz - t.cz;
-    float best = seg_dist2(apx, apy, apz, abx, aby, abz);
-    best = fmin2(best, seg_dist2(bpx, bpy, bpz, bcx, bcy, bcz));
-    best = fmin2(best, seg_dist2(apx, apy, apz, acx, acy, acz));
+    float s = 0.0f;
+    float best = seg_nearest<POINT>(apx, apy, apz, abx, aby, abz, &s);
+    if constexpr (POINT) r[0] = t.ax + s * abx, r[1] = t.ay + s * aby, r[2] = t.az + s * abz;
+    float d = seg_nearest<POINT>(bpx, bpy, bpz, bcx, bcy, bcz, &s);
+    if (d < best) {
+        best = d;
+        if constexpr (POINT) r[0] = t.bx + s * bcx, r[1] = t.by + s * bcy, r[2] = t.bz + s * bcz;
+    }
+    d = seg_nearest<POINT>(apx, apy, apz, acx, acy, acz, &s);
+    if (d < best) {
+        best = d;
+        if constexpr (POINT) r[0] = t.ax + s * acx, r[1] = t.ay + s * acy, r[2] = t.az + s * acz;
+    }
     const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
     const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
     const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
     const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
     if (va > 0.0f && vb > 0.0f && vc > 0.0f) {
         const float den = va + vb + vc;                      // > 0 here
-        const float v = vb / den, w = vc / den;              // v, w > 0 and v + w < 1: a point of the triangle
+        float v = vb / den, w = vc / den;                    // v, w > 0 and v + w < 1: a point of the triangle
         float qx = apx - v * abx - w * acx, qy = apy - v * aby - w * acy, qz = apz - v * abz - w * acz;
         // One step of iterative refinement.  The barycentrics above come from products of dot products and lose a factor
         // 1 / sin^2 of the smallest angle (marching cubes is full of slivers); the residual q is small, so solving the
@@ -106,65 +111,27 @@ R3G_MD_HD float tri_dist2(float px, float py, float pz, const Tri& t) {
         if (det > 0.0f) {
             const float e1 = abx * qx + aby * qy + abz * qz, e2 = acx * qx + acy * qy + acz * qz;
             const float v2 = v + (g22 * e1 - g12 * e2) / det, w2 = w + (g11 * e2 - g12 * e1) / det;
-            if (v2 >= 0.0f && w2 >= 0.0f && v2 + w2 <= 1.0f)
-                qx = apx - v2 * abx - w2 * acx, qy = apy - v2 * aby - w2 * acy, qz = apz - v2 * abz - w2 * acz;
-        }
-        best = fmin2(best, qx * qx + qy * qy + qz * qz);
-    }
-    return best;
-}
-
-// tri_dist2 with the point that attains it: the same candidates in the same order -- edges ab, bc, ac,
-// then the refined interior point -- with the same arithmetic, so the value returned is tri_dist2's bit for bit; a later
-// candidate replaces the point only when it is strictly nearer.  The point is base + t * edge (edges) or
-// a + v * ab + w * ac (interior), one float32 operation each, left to right.
-R3G_MD_HD float seg_closest(float apx, float apy, float apz, float abx, float aby, float abz, float* t_out) {
-    const float den = abx * abx + aby * aby + abz * abz;
-    const float num = apx * abx + apy * aby + apz * abz;
-    float t = den > 0.0f ? num / den : 0.0f;
-    t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-    const float qx = apx - t * abx, qy = apy - t * aby, qz = apz - t * abz;
-    *t_out = t;
-    return qx * qx + qy * qy + qz * qz;
-}
-
-R3G_MD_HD float tri_closest(float px, float py, float pz, const Tri& t, float* cx, float* cy, float* cz) {
-    const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az;
-    const float acx = t.cx - t.ax, acy = t.cy - t.ay, acz = t.cz - t.az;
-    const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
-    const float apx = px - t.ax, apy = py - t.ay, apz = pz - t.az;
-    const float bpx = px - t.bx, bpy = py - t.by, bpz = pz - t.bz;
-    const float cpx = px - t.cx, cpy = py - t.cy, cpz = pz - t.cz;
-    float s;
-    float best = seg_closest(apx, apy, apz, abx, aby, abz, &s);
-    float rx = t.ax + s * abx, ry = t.ay + s * aby, rz = t.az + s * abz;
-    float d = seg_closest(bpx, bpy, bpz, bcx, bcy, bcz, &s);
-    if (d < best) best = d, rx = t.bx + s * bcx, ry = t.by + s * bcy, rz = t.bz + s * bcz;
-    d = seg_closest(apx, apy, apz, acx, acy, acz, &s);
-    if (d < best) best = d, rx = t.ax + s * acx, ry = t.ay + s * acy, rz = t.az + s * acz;
-    const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
-    const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
-    const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
-    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    if (va > 0.0f && vb > 0.0f && vc > 0.0f) {
-        const float den = va + vb + vc;
-        float v = vb / den, w = vc / den;
-        float qx = apx - v * abx - w * acx, qy = apy - v * aby - w * acy, qz = apz - v * abz - w * acz;
-        const float g11 = abx * abx + aby * aby + abz * abz, g12 = abx * acx + aby * acy + abz * acz;
-        const float g22 = acx * acx + acy * acy + acz * acz, det = g11 * g22 - g12 * g12;
-        if (det > 0.0f) {
-            const float e1 = abx * qx + aby * qy + abz * qz, e2 = acx * qx + acy * qy + acz * qz;
-            const float v2 = v + (g22 * e1 - g12 * e2) / det, w2 = w + (g11 * e2 - g12 * e1) / det;
             if (v2 >= 0.0f && w2 >= 0.0f && v2 + w2 <= 1.0f) {
                 qx = apx - v2 * abx - w2 * acx, qy = apy - v2 * aby - w2 * acy, qz = apz - v2 * abz - w2 * acz;
-                v = v2, w = w2;
+                if constexpr (POINT) v = v2, w = w2;
             }
         }
         d = qx * qx + qy * qy + qz * qz;
-        if (d < best) best = d, rx = t.ax + v * abx + w * acx, ry = t.ay + v * aby + w * acy, rz = t.az + v * abz + w * acz;
+        if (d < best) {
+            best = d;
+            if constexpr (POINT) r[0] = t.ax + v * abx + w * acx, r[1] = t.ay + v * aby + w * acy, r[2] = t.az + v * abz + w * acz;
+        }
     }
-    *cx = rx, *cy = ry, *cz = rz;
     return best;
+}
+
+R3G_MD_HD float tri_dist2(float px, float py, float pz, const Tri& t) { return tri_nearest<false>(px, py, pz, t, nullptr); }
+
+R3G_MD_HD float tri_closest(float px, float py, float pz, const Tri& t, float* cx, float* cy, float* cz) {
+    float r[3];
+    const float d = tri_nearest<true>(px, py, pz, t, r);
+    *cx = r[0], *cy = r[1], *cz = r[2];
+    return d;
 }
 
 // (dist2, face) in lexicographic order: the order in which candidates arrive does not matter
@@ -188,52 +155,20 @@ R3G_MD_HD int initial_resolution(int64_t nf) {
     return r;
 }
 
-R3G_MD_HD Grid make_grid(const float lo[3], const float hi[3], int res) {
-    Grid g;
-    g.res = res;
-    float ext[3], maxext = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = lo[a];
-        g.hi[a] = hi[a];
-        ext[a] = hi[a] - lo[a];
-        maxext = fmax2(maxext, ext[a]);
-    }
-    for (int a = 0; a < 3; ++a) {
-        float h = ext[a] / (float)res;
-        if (!(h >= 1e-30f && h <= 1e30f)) h = maxext / (float)res;     // a flat axis: every face lands in its cell 0
-        if (!(h >= 1e-30f && h <= 1e30f)) h = 1.0f;
-        g.h[a] = h;
-        g.inv[a] = 1.0f / h;
-    }
-    return g;
+// what the grid builder asks of a record (grid_csr.h): does it take part, and its axis-aligned box
+R3G_MD_HD bool grid_member(const Tri& t) { return t.valid != 0; }
+R3G_MD_HD void grid_box(const Tri& t, float mn[3], float mx[3]) {
+    mn[0] = fmin2(t.ax, fmin2(t.bx, t.cx)), mn[1] = fmin2(t.ay, fmin2(t.by, t.cy)), mn[2] = fmin2(t.az, fmin2(t.bz, t.cz));
+    mx[0] = fmax2(t.ax, fmax2(t.bx, t.cx)), mx[1] = fmax2(t.ay, fmax2(t.by, t.cy)), mx[2] = fmax2(t.az, fmax2(t.bz, t.cz));
 }
 
-R3G_MD_HD float cell_coord(const Grid& g, int a, float x) { return (x - g.lo[a]) * g.inv[a]; }
-
-// floor(t) clamped to [0, res - 1]; NaN -> 0
-R3G_MD_HD int cell_clamp(float t, int res) {
-    if (!(t > 0.0f)) return 0;
-    if (t >= (float)res) return res - 1;
-    return (int)t;
+// the grid helpers under the names of this header's interface: a triangle's cell range, its pair count, a cell's index
+R3G_MD_HD void tri_range(const Grid& g, const Tri& t, int lo[3], int hi[3]) { r3g_grid::range(g, t, lo, hi); }
+R3G_MD_HD int64_t tri_pairs(const Grid& g, const Tri& t) { return r3g_grid::pairs(g, t); }
+R3G_MD_HD int cell_index(const Grid& g, int x, int y, int z) {
+    const int c[3] = {x, y, z};
+    return r3g_grid::index(g, c);
 }
-
-// the cells a triangle's axis-aligned box overlaps, widened by kBinMargin on both sides
-R3G_MD_HD void tri_range(const Grid& g, const Tri& t, int lo[3], int hi[3]) {
-    const float mn[3] = {fmin2(t.ax, fmin2(t.bx, t.cx)), fmin2(t.ay, fmin2(t.by, t.cy)), fmin2(t.az, fmin2(t.bz, t.cz))};
-    const float mx[3] = {fmax2(t.ax, fmax2(t.bx, t.cx)), fmax2(t.ay, fmax2(t.by, t.cy)), fmax2(t.az, fmax2(t.bz, t.cz))};
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = cell_clamp(cell_coord(g, a, mn[a]) - kBinMargin, g.res);
-        hi[a] = cell_clamp(cell_coord(g, a, mx[a]) + kBinMargin, g.res);
-    }
-}
-
-R3G_MD_HD int64_t tri_pairs(const Grid& g, const Tri& t) {
-    int lo[3], hi[3];
-    tri_range(g, t, lo, hi);
-    return (int64_t)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1);
-}
-
-R3G_MD_HD int cell_index(const Grid& g, int x, int y, int z) { return (z * g.res + y) * g.res + x; }
 
 R3G_MD_HD void visit_cell(const Tri* tris, const uint32_t* starts, const int32_t* pairs, int cell, float px, float py,
                           float pz, float& best, int32_t& bface, uint32_t& ntests) {
@@ -274,8 +209,8 @@ R3G_MD_HD void nearest(const Grid& g, const Tri* tris, const uint32_t* starts, c
     float tp[3], out2[3], far2 = 0.0f;
     int c[3], rmax = 0;
     for (int a = 0; a < 3; ++a) {
-        tp[a] = cell_coord(g, a, p[a]);
-        c[a] = cell_clamp(tp[a], R);
+        tp[a] = coord(g, a, p[a]);
+        c[a] = clamp(tp[a], R);
         const int m = c[a] > R - 1 - c[a] ? c[a] : R - 1 - c[a];
         rmax = m > rmax ? m : rmax;
         const float f = fmax2(fabs1(p[a] - g.lo[a]), fabs1(p[a] - g.hi[a]));

@@ -21,11 +21,11 @@ struct MeshfitRecord {
 // one MeshfitRecord for the result, then one per block
 inline size_t meshfit_workspace_bytes() { return sizeof(MeshfitRecord) * (size_t)(1 + r3g_md::kFitMaxBlocks); }
 
-// dist2 [n], face [n], closest [n][3] (MeshdistSmall::tests of the distance workspace receives the test count)
-hipError_t meshfit_closest(char* md_ws, const MeshdistLayout& lay, const r3g_md::Grid& g, const int32_t* pairs, const float* points,
+// dist2 [n], face [n], closest [n][3] (GridCsrSmall::tests of the distance workspace receives the test count)
+hipError_t meshfit_closest(char* md_ws, const GridCsrLayout& lay, const r3g_md::Grid& g, const int32_t* pairs, const float* points,
                            int64_t n, float* dist2, int32_t* face, float* closest, hipStream_t s);
 // one accumulation: fit_blocks(n) partial records, then their sum into the first record of `ws`
-hipError_t meshfit_step(char* ws, const char* md_ws, const MeshdistLayout& lay, const r3g_md::Grid& g, const int32_t* pairs,
+hipError_t meshfit_step(char* ws, const char* md_ws, const GridCsrLayout& lay, const r3g_md::Grid& g, const int32_t* pairs,
                         const float* points, int64_t n, const float* weights, const r3g_md::Sim& x, int mode, float md2, hipStream_t s);
 
 void meshfit_add_steps(int64_t n);      // r3g_get_counter("meshfit_steps")

@@ -13,7 +13,9 @@
 
 #pragma clang fp contract(off)
 
+#define R3G_GRID_HD static __host__ __device__ __forceinline__
 #define R3G_MD_HD static __host__ __device__ __forceinline__
+#include "mesh_launch.h"
 #include "meshfit_kernels.h"
 
 namespace r3g {
@@ -23,14 +25,8 @@ using r3g_md::Grid;
 using r3g_md::Sim;
 using r3g_md::Tri;
 
-constexpr int kT = r3g_md::kFitBlock;
-
 __device__ __forceinline__ double wave_sum_f64(double v) {
     for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
 }
 
@@ -116,20 +112,20 @@ std::atomic<int64_t> g_steps{0};
 }  // namespace
 
 static_assert(sizeof(MeshfitRecord) == 8 * r3g_md::kFitRecord, "a partial record is kFitRecord 8-byte slots");
-static_assert(r3g_md::kFitMaxTerms <= 38 && r3g_md::kFitBlock == 256, "the sums fit the record; the tree is four waves");
+static_assert(r3g_md::kFitMaxTerms <= 38 && r3g_md::kFitBlock == kT, "the sums fit the record; the tree is four waves");
 
-hipError_t meshfit_closest(char* md_ws, const MeshdistLayout& lay, const Grid& g, const int32_t* pairs, const float* points, int64_t n,
+hipError_t meshfit_closest(char* md_ws, const GridCsrLayout& lay, const Grid& g, const int32_t* pairs, const float* points, int64_t n,
                            float* dist2, int32_t* face, float* closest, hipStream_t s) {
-    hipLaunchKernelGGL(mf_closest, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, s, g, (const Tri*)(md_ws + lay.off_tris),
+    hipLaunchKernelGGL(mf_closest, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, s, g, (const Tri*)(md_ws + lay.off_recs),
                        (const unsigned*)(md_ws + lay.off_starts), pairs, points, n, dist2, face, closest);
     return hipGetLastError();
 }
 
-hipError_t meshfit_step(char* ws, const char* md_ws, const MeshdistLayout& lay, const Grid& g, const int32_t* pairs, const float* points,
+hipError_t meshfit_step(char* ws, const char* md_ws, const GridCsrLayout& lay, const Grid& g, const int32_t* pairs, const float* points,
                         int64_t n, const float* weights, const Sim& x, int mode, float md2, hipStream_t s) {
     MeshfitRecord* rec = (MeshfitRecord*)ws;
     const unsigned nb = (unsigned)r3g_md::fit_blocks(n);
-    const Tri* tris = (const Tri*)(md_ws + lay.off_tris);
+    const Tri* tris = (const Tri*)(md_ws + lay.off_recs);
     const unsigned* starts = (const unsigned*)(md_ws + lay.off_starts);
     if (mode == r3g_md::kFitPlane)
         hipLaunchKernelGGL(mf_step<r3g_md::kFitPlane>, dim3(nb), dim3(kT), 0, s, g, tris, starts, pairs, points, n, weights, x, md2, rec + 1);

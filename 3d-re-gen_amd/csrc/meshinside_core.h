@@ -10,15 +10,26 @@
 #define R3G_MESHINSIDE_CORE_H
 #include <stdint.h>
 
+#include "grid_csr.h"
+
 #ifndef R3G_MI_HD
 #define R3G_MI_HD static inline
 #endif
 
 namespace r3g_mi {
 
+using r3g_grid::clamp;
+using r3g_grid::coord;
+using r3g_grid::dec_float;
+using r3g_grid::enc_float;
+using r3g_grid::finite;
+using r3g_grid::fmax2;
+using r3g_grid::fmin2;
+using r3g_grid::kPairMult;
+using r3g_grid::make_grid;
+using Grid2 = r3g_grid::GridN<2>;      // columns (section 4g): the grid of grid_csr.h over the two projected axes
+
 constexpr int kMaxRes = 1024;                         // cap: 1024^2 = 2^20 columns
-constexpr int kPairMult = 8;                          // automatic resolution: halve while pairs > kPairMult * F
-constexpr float kBinMargin = 1.0f / 256.0f;           // columns; widens a face's column range (rounding can only add columns)
 constexpr float kInf = __builtin_huge_valf();
 
 // one face in projected coordinates (u, v) = (x[(axis+1)%3], x[(axis+2)%3]), depth w = x[axis], with its vertex indices
@@ -31,30 +42,6 @@ struct alignas(16) Rec {
     float cu, cv, cw;
     int32_t ic;
 };
-
-struct Grid2 {
-    float lo[2];
-    float hi[2];
-    float h[2];          // column size per projected axis
-    float inv[2];        // 1 / h: defines the column coordinate t = (x - lo) * inv
-    int res;             // columns per projected axis
-};
-
-R3G_MI_HD bool finite(float x) { return (x - x) == 0.0f; }
-R3G_MI_HD float fmin2(float a, float b) { return b < a ? b : a; }
-R3G_MI_HD float fmax2(float a, float b) { return b > a ? b : a; }
-
-// order-preserving float -> uint32 (bounding box by integer atomicMin / atomicMax) and back
-R3G_MI_HD uint32_t enc_float(float x) {
-    union { float f; uint32_t u; } c;
-    c.f = x;
-    return (c.u & 0x80000000u) ? ~c.u : (c.u | 0x80000000u);
-}
-R3G_MI_HD float dec_float(uint32_t u) {
-    union { float f; uint32_t u; } c;
-    c.u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return c.f;
-}
 
 R3G_MI_HD Rec make_rec(const float a[3], int32_t ia, const float b[3], int32_t ib, const float c[3], int32_t ic, int axis) {
     const int iu = (axis + 1) % 3, iv = (axis + 2) % 3;
@@ -140,56 +127,23 @@ R3G_MI_HD int initial_resolution(int64_t nf) {
     return r;
 }
 
-R3G_MI_HD Grid2 make_grid(const float lo[2], const float hi[2], int res) {
-    Grid2 g;
-    g.res = res;
-    float ext[2], maxext = 0.0f;
-    for (int a = 0; a < 2; ++a) {
-        g.lo[a] = lo[a];
-        g.hi[a] = hi[a];
-        ext[a] = hi[a] - lo[a];
-        maxext = fmax2(maxext, ext[a]);
-    }
-    for (int a = 0; a < 2; ++a) {
-        float h = ext[a] / (float)res;
-        if (!(h >= 1e-30f && h <= 1e30f)) h = maxext / (float)res;     // a flat axis: every face lands in its column 0
-        if (!(h >= 1e-30f && h <= 1e30f)) h = 1.0f;
-        g.h[a] = h;
-        g.inv[a] = 1.0f / h;
-    }
-    return g;
+// what the grid builder asks of a record (grid_csr.h): does it take part, and its projected box
+R3G_MI_HD bool grid_member(const Rec& r) { return r.ia >= 0; }
+R3G_MI_HD void grid_box(const Rec& r, float mn[2], float mx[2]) {
+    mn[0] = fmin2(r.au, fmin2(r.bu, r.cu)), mn[1] = fmin2(r.av, fmin2(r.bv, r.cv));
+    mx[0] = fmax2(r.au, fmax2(r.bu, r.cu)), mx[1] = fmax2(r.av, fmax2(r.bv, r.cv));
 }
 
-// monotone in x: subtraction of a constant and multiplication by a positive constant round monotonically
-R3G_MI_HD float col_coord(const Grid2& g, int a, float x) { return (x - g.lo[a]) * g.inv[a]; }
-
-// floor(t) clamped to [0, res - 1]; NaN -> 0
-R3G_MI_HD int col_clamp(float t, int res) {
-    if (!(t > 0.0f)) return 0;
-    if (t >= (float)res) return res - 1;
-    return (int)t;
+// the grid helpers under the names of this header's interface: a face's column range, its pair count, a column's index
+R3G_MI_HD void rec_range(const Grid2& g, const Rec& r, int lo[2], int hi[2]) { r3g_grid::range(g, r, lo, hi); }
+R3G_MI_HD int64_t rec_pairs(const Grid2& g, const Rec& r) { return r3g_grid::pairs(g, r); }
+R3G_MI_HD int col_index(const Grid2& g, int x, int y) {
+    const int c[2] = {x, y};
+    return r3g_grid::index(g, c);
 }
-
-// the columns a face's projected box overlaps, widened by kBinMargin on both sides
-R3G_MI_HD void rec_range(const Grid2& g, const Rec& r, int lo[2], int hi[2]) {
-    const float mn[2] = {fmin2(r.au, fmin2(r.bu, r.cu)), fmin2(r.av, fmin2(r.bv, r.cv))};
-    const float mx[2] = {fmax2(r.au, fmax2(r.bu, r.cu)), fmax2(r.av, fmax2(r.bv, r.cv))};
-    for (int a = 0; a < 2; ++a) {
-        lo[a] = col_clamp(col_coord(g, a, mn[a]) - kBinMargin, g.res);
-        hi[a] = col_clamp(col_coord(g, a, mx[a]) + kBinMargin, g.res);
-    }
-}
-
-R3G_MI_HD int64_t rec_pairs(const Grid2& g, const Rec& r) {
-    int lo[2], hi[2];
-    rec_range(g, r, lo, hi);
-    return (int64_t)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1);
-}
-
-R3G_MI_HD int col_index(const Grid2& g, int x, int y) { return y * g.res + x; }
 
 // The query of one point given in mesh coordinates: project, find the column, sum the crossings of the faces listed there.
-// A face that p is covered by holds p inside its projected box, so (col_coord is monotone) p's column lies inside the
+// A face that p is covered by holds p inside its projected box, so (the grid's coord is monotone) p's column lies inside the
 // face's column range: every face that can be crossed is listed in p's column.
 R3G_MI_HD int32_t count_crossings(const Grid2& g, int axis, const Rec* recs, const uint32_t* starts, const int32_t* pairs, float px,
                                   float py, float pz, uint32_t* ntests_out) {
@@ -197,7 +151,7 @@ R3G_MI_HD int32_t count_crossings(const Grid2& g, int axis, const Rec* recs, con
     const float p[3] = {px, py, pz};
     const float pu = p[(axis + 1) % 3], pv = p[(axis + 2) % 3], pw = p[axis];
     if (pu < g.lo[0] || pu > g.hi[0] || pv < g.lo[1] || pv > g.hi[1]) return 0;     // outside the projected box: no lookup
-    const int col = col_index(g, col_clamp(col_coord(g, 0, pu), g.res), col_clamp(col_coord(g, 1, pv), g.res));
+    const int col = col_index(g, clamp(coord(g, 0, pu), g.res), clamp(coord(g, 1, pv), g.res));
     const uint32_t e = starts[col + 1];
     int32_t n = 0;
     uint32_t ntests = 0;

@@ -13,6 +13,7 @@
 #pragma clang fp contract(off)
 
 #define R3G_MT_HD static __host__ __device__ __forceinline__
+#include "mesh_launch.h"
 #include "meshtopo_kernels.h"
 #include "wave_sum.h"
 
@@ -20,13 +21,6 @@ namespace r3g {
 namespace {
 
 using r3g_mt::Small;
-
-constexpr int kT = 256;
-
-inline unsigned grid_for(int64_t n) {
-    const int64_t b = (n + kT - 1) / kT;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
 
 // A lane's count in the kernels below is at most ceil(3 * 2^29 / (4096 * 256)) = 1536, a wave's at most 98304: exact in float.
 __device__ __forceinline__ unsigned long long wave_count(unsigned n) { return (unsigned long long)wave_sum((float)n); }
@@ -293,12 +287,6 @@ __global__ __launch_bounds__(kT) void mt_apply(int32_t* __restrict__ faces, int6
     add_count(&sm->faces_reversed, nfaces);
     add_count(&sm->bodies_reversed, nbodies);
 }
-
-#define R3G_HIP(x)                         \
-    do {                                   \
-        hipError_t e_ = (x);               \
-        if (e_ != hipSuccess) return e_;   \
-    } while (0)
 
 std::atomic<int64_t> g_builds{0}, g_rounds{0};
 

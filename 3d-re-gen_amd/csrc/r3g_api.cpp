@@ -90,6 +90,102 @@ int hier_unsafe_cells(Ctx* c, const float* d_fine, double level, int64_t* count,
     *count = (int64_t) * (const unsigned long long*)c->h_small;
     return R3G_OK;
 }
+
+// ---- grids in CSR form: the mesh distance's cells and the point-in-mesh columns ----------------------
+// "meshdist_fill", "hipMalloc(meshinside pairs)": a step's name for the error text, with the user's name in it
+struct Named {
+    char s[64];
+    Named(const char* fmt, const char* who) { snprintf(s, sizeof s, fmt, who); }
+    operator const char*() const { return s; }
+};
+
+static int grid_small(Ctx* c, const char* ws, const GridCsrLayout& lay, const char* who, hipStream_t s, GridCsrSmall* out) {
+    hipError_t e = hipMemcpyAsync(c->h_small, ws + lay.off_small, sizeof(GridCsrSmall), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, Named("hipMemcpyAsync(%s)", who));
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, Named("hipStreamSynchronize(%s)", who));
+    memcpy(out, c->h_small, sizeof(GridCsrSmall));
+    return R3G_OK;
+}
+
+// what the build driver needs to know of its user; `records` launches the user's records kernel
+struct MeshdistBuild {
+    static constexpr int D = 3, kMaxRes = r3g_md::kMaxRes;
+    static constexpr size_t record_bytes = sizeof(r3g_md::Tri);
+    static constexpr const char *who = "meshdist", *no_face = "the target mesh has no face", *cell = "cell";
+    static int initial_resolution(int64_t nf) { return r3g_md::initial_resolution(nf); }
+    const char* check() const { return nullptr; }
+    hipError_t records(char* ws, const GridCsrLayout& lay, const float* v, int64_t nv, const int32_t* f, int64_t nf, hipStream_t s) const {
+        return meshdist_records(ws, lay, v, nv, f, nf, s);
+    }
+};
+
+struct MeshinsideBuild {
+    static constexpr int D = 2, kMaxRes = r3g_mi::kMaxRes;
+    static constexpr size_t record_bytes = sizeof(r3g_mi::Rec);
+    static constexpr const char *who = "meshinside", *no_face = "the mesh has no face", *cell = "column";
+    static int initial_resolution(int64_t nf) { return r3g_mi::initial_resolution(nf); }
+    int axis;
+    const char* check() const { return axis < 0 || axis > 2 ? "axis outside 0..2" : nullptr; }
+    hipError_t records(char* ws, const GridCsrLayout& lay, const float* v, int64_t nv, const int32_t* f, int64_t nf, hipStream_t s) const {
+        return meshinside_records(ws, lay, v, nv, f, nf, axis, s);
+    }
+};
+
+// validate, reserve, records, read-back and checks, box, resolution, pairs reserve, fill, sync
+template <class U>
+static int grid_csr_build(Ctx* c, GridCsrState<U::D>* st, const U& user, const float* d_verts, int64_t n_verts, const int32_t* d_faces,
+                          int64_t n_faces, int resolution, int* resolution_out, int64_t* pairs_out, int64_t* skipped_out, hipStream_t s) {
+    constexpr int D = U::D;
+    const char* who = U::who;
+    st->built = false;
+    if (n_verts < 0 || n_verts >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 30))
+        return fail(R3G_ERR_INVALID, "r3g_%s_build: mesh size out of range", who);
+    if (n_faces == 0) return fail(R3G_ERR_INVALID, "r3g_%s_build: %s", who, U::no_face);
+    if (!d_faces || (n_verts && !d_verts)) return fail(R3G_ERR_INVALID, "r3g_%s_build: null buffer", who);
+    if (const char* bad = user.check()) return fail(R3G_ERR_INVALID, "r3g_%s_build: %s", who, bad);
+    if (resolution < 0 || resolution > U::kMaxRes)
+        return fail(R3G_ERR_INVALID, "r3g_%s_build: resolution outside [0, %d] (0 = automatic)", who, U::kMaxRes);
+    const int initial = U::initial_resolution(n_faces);
+    GridCsrLayout lay;
+    const size_t need = grid_csr_workspace_bytes(n_faces, U::record_bytes, r3g_grid::cells<D>(resolution ? resolution : initial), &lay);
+    int rc = c->reserve(&st->ws, &st->ws_bytes, need, Named("hipMalloc(%s workspace)", who));
+    if (rc) return rc;
+    st->lay = lay;
+    hipError_t e = user.records(st->ws, lay, d_verts, n_verts, d_faces, n_faces, s);
+    if (e != hipSuccess) return hip_fail(e, Named("%s_records", who));
+    GridCsrSmall sm;
+    if ((rc = grid_small(c, st->ws, lay, who, s, &sm))) return rc;
+    // (-2 by the contract of include/r3g.h: found on the device, before anything is read through the index)
+    if (sm.bad_index) return fail(-2, "r3g_%s_build: a face index lies outside [0, %lld)", who, (long long)n_verts);
+    if ((int64_t)sm.skipped >= n_faces)
+        return fail(R3G_ERR_INVALID, "r3g_%s_build: every face has a non-finite vertex (%lld skipped)", who, (long long)sm.skipped);
+    float lo[D], hi[D];
+    for (int a = 0; a < D; ++a) lo[a] = r3g_grid::dec_float(sm.box[a]), hi[a] = r3g_grid::dec_float(sm.box[D + a]);
+    r3g_grid::GridN<D> g;
+    int64_t pairs = 0;
+    rc = r3g_grid::choose_resolution(lo, hi, resolution, initial, n_faces, [&](const r3g_grid::GridN<D>& cand, int64_t* n) {
+        e = grid_csr_count_pairs(st->ws, lay, n_faces, cand, s);
+        if (e != hipSuccess) return hip_fail(e, Named("%s_count_pairs", who));
+        const int r = grid_small(c, st->ws, lay, who, s, &sm);
+        *n = (int64_t)sm.pairs;
+        return r;
+    }, &g, &pairs);
+    if (rc) return rc;
+    if (pairs >= (1ll << 31))
+        return fail(R3G_ERR_INVALID, "r3g_%s_build: %lld (face, %s) pairs at resolution %d; force a lower one", who, (long long)pairs, U::cell, g.res);
+    if ((rc = c->reserve(&st->pairs, &st->pairs_bytes, 4 * (size_t)pairs, Named("hipMalloc(%s pairs)", who)))) return rc;
+    e = grid_csr_fill(st->ws, lay, n_faces, g, (int32_t*)st->pairs, s);
+    if (e != hipSuccess) return hip_fail(e, Named("%s_fill", who));
+    e = hipStreamSynchronize(s);      // the caller may free its mesh buffers, and a fault would surface here
+    if (e != hipSuccess) return hip_fail(e, Named("hipStreamSynchronize(%s_fill)", who));
+    st->grid = g;
+    st->built = true;
+    if (resolution_out) *resolution_out = g.res;
+    if (pairs_out) *pairs_out = pairs;
+    if (skipped_out) *skipped_out = (int64_t)sm.skipped;
+    return R3G_OK;
+}
 }  // namespace r3g
 
 using namespace r3g;
@@ -137,12 +233,12 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->mc_ws) (void)hipFree(c->mc_ws);
     if (c->dmc_ws) (void)hipFree(c->dmc_ws);
     if (c->mesh_ws) (void)hipFree(c->mesh_ws);
-    if (c->meshdist_ws) (void)hipFree(c->meshdist_ws);
-    if (c->meshdist_pairs) (void)hipFree(c->meshdist_pairs);
+    if (c->meshdist.ws) (void)hipFree(c->meshdist.ws);
+    if (c->meshdist.pairs) (void)hipFree(c->meshdist.pairs);
     if (c->meshfit_ws) (void)hipFree(c->meshfit_ws);
     if (c->h_fit) (void)hipHostFree(c->h_fit);
-    if (c->meshinside_ws) (void)hipFree(c->meshinside_ws);
-    if (c->meshinside_pairs) (void)hipFree(c->meshinside_pairs);
+    if (c->meshinside.ws) (void)hipFree(c->meshinside.ws);
+    if (c->meshinside.pairs) (void)hipFree(c->meshinside.pairs);
     if (c->meshtopo_ws) (void)hipFree(c->meshtopo_ws);
     if (c->h_topo) (void)hipHostFree(c->h_topo);
     if (c->tex_ws) (void)hipFree(c->tex_ws);
@@ -330,81 +426,27 @@ int r3g_mesh_cluster_faces(r3g_ctx* ctx, float* d_verts, int64_t* n_verts, int32
 }
 
 // ---- mesh distance ------------------------------------------------------------------------------------------------
-static int meshdist_small(Ctx* c, hipStream_t s, MeshdistSmall* out) {
-    hipError_t e = hipMemcpyAsync(c->h_small, c->meshdist_ws + c->meshdist_lay.off_small, sizeof(MeshdistSmall), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshdist)");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshdist)");
-    memcpy(out, c->h_small, sizeof(MeshdistSmall));
-    return R3G_OK;
-}
-
 int r3g_meshdist_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces,
                        int resolution, int* resolution_out, int64_t* pairs_out, int64_t* skipped_out, void* stream) {
     if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshdist_build: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    c->meshdist_built = false;
-    if (n_verts < 0 || n_verts >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 30))
-        return fail(R3G_ERR_INVALID, "r3g_meshdist_build: mesh size out of range");
-    if (n_faces == 0) return fail(R3G_ERR_INVALID, "r3g_meshdist_build: the target mesh has no face");
-    if (!d_faces || (n_verts && !d_verts)) return fail(R3G_ERR_INVALID, "r3g_meshdist_build: null buffer");
-    if (resolution < 0 || resolution > r3g_md::kMaxRes)
-        return fail(R3G_ERR_INVALID, "r3g_meshdist_build: resolution outside [0, %d] (0 = automatic)", r3g_md::kMaxRes);
-    hipStream_t s = (hipStream_t)stream;
-    int res = resolution ? resolution : r3g_md::initial_resolution(n_faces);
-    MeshdistLayout lay;
-    int rc = c->reserve(&c->meshdist_ws, &c->meshdist_ws_bytes, meshdist_workspace_bytes(n_faces, res, &lay), "hipMalloc(meshdist workspace)");
-    if (rc) return rc;
-    c->meshdist_lay = lay;
-    hipError_t e = meshdist_records(c->meshdist_ws, lay, d_verts, n_verts, d_faces, n_faces, s);
-    if (e != hipSuccess) return hip_fail(e, "meshdist_records");
-    MeshdistSmall sm;
-    if ((rc = meshdist_small(c, s, &sm))) return rc;
-    // (-2 by the contract of include/r3g.h: found on the device, before anything is read through the index)
-    if (sm.bad_index) return fail(-2, "r3g_meshdist_build: a face index lies outside [0, %lld)", (long long)n_verts);
-    if ((int64_t)sm.skipped >= n_faces)
-        return fail(R3G_ERR_INVALID, "r3g_meshdist_build: every face has a non-finite vertex (%lld skipped)", (long long)sm.skipped);
-    float lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) lo[a] = r3g_md::dec_float(sm.box[a]), hi[a] = r3g_md::dec_float(sm.box[3 + a]);
-    r3g_md::Grid g;
-    int64_t pairs = 0;
-    for (;;) {
-        g = r3g_md::make_grid(lo, hi, res);
-        e = meshdist_count_pairs(c->meshdist_ws, lay, n_faces, g, s);
-        if (e != hipSuccess) return hip_fail(e, "meshdist_count_pairs");
-        if ((rc = meshdist_small(c, s, &sm))) return rc;
-        pairs = (int64_t)sm.pairs;
-        if (resolution || res == 1 || pairs <= r3g_md::kPairMult * n_faces) break;
-        res /= 2;       // e.g. one triangle that spans the box: R^3 pairs of its own
-    }
-    if (pairs >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshdist_build: %lld (face, cell) pairs at resolution %d; force a lower one", (long long)pairs, res);
-    rc = c->reserve(&c->meshdist_pairs, &c->meshdist_pairs_bytes, 4 * (size_t)pairs, "hipMalloc(meshdist pairs)");
-    if (rc) return rc;
-    e = meshdist_fill(c->meshdist_ws, lay, n_faces, g, (int32_t*)c->meshdist_pairs, s);
-    if (e != hipSuccess) return hip_fail(e, "meshdist_fill");
-    e = hipStreamSynchronize(s);      // the caller may free its mesh buffers, and a fault would surface here
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshdist_fill)");
-    c->meshdist_grid = g;
-    c->meshdist_built = true;
-    if (resolution_out) *resolution_out = res;
-    if (pairs_out) *pairs_out = pairs;
-    if (skipped_out) *skipped_out = (int64_t)sm.skipped;
-    return R3G_OK;
+    return grid_csr_build(c, &c->meshdist, MeshdistBuild{}, d_verts, n_verts, d_faces, n_faces, resolution, resolution_out, pairs_out,
+                          skipped_out, (hipStream_t)stream);
 }
 
 int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, float* d_dist2, int32_t* d_face, void* stream) {
     if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshdist_query: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c->meshdist_built) return fail(R3G_ERR_STATE, "r3g_meshdist_query: no successful r3g_meshdist_build on this context");
+    if (!c->meshdist.built) return fail(R3G_ERR_STATE, "r3g_meshdist_query: no successful r3g_meshdist_build on this context");
     if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshdist_query: n_points out of range");
     if (n_points == 0) return R3G_OK;
     if (!d_points || !d_dist2 || !d_face) return fail(R3G_ERR_INVALID, "r3g_meshdist_query: null buffer");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = meshdist_query(c->meshdist_ws, c->meshdist_lay, c->meshdist_grid, (const int32_t*)c->meshdist_pairs, d_points,
+    hipError_t e = meshdist_query(c->meshdist.ws, c->meshdist.lay, c->meshdist.grid, (const int32_t*)c->meshdist.pairs, d_points,
                                   n_points, d_dist2, d_face, s);
     if (e != hipSuccess) return hip_fail(e, "meshdist_query");
-    MeshdistSmall sm;
-    int rc = meshdist_small(c, s, &sm);
+    GridCsrSmall sm;
+    int rc = grid_small(c, c->meshdist.ws, c->meshdist.lay, "meshdist", s, &sm);
     if (rc) return rc;
     meshdist_add_tests((int64_t)sm.tests);
     return R3G_OK;
@@ -415,11 +457,11 @@ int r3g_meshdist_closest(r3g_ctx* ctx, const float* d_points, int64_t n_points, 
                          void* stream) {
     if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c->meshdist_built) return fail(R3G_ERR_STATE, "r3g_meshdist_closest: no successful r3g_meshdist_build on this context");
+    if (!c->meshdist.built) return fail(R3G_ERR_STATE, "r3g_meshdist_closest: no successful r3g_meshdist_build on this context");
     if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: n_points out of range");
     if (n_points == 0) return R3G_OK;
     if (!d_points || !d_dist2 || !d_face || !d_closest) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: null buffer");
-    hipError_t e = meshfit_closest(c->meshdist_ws, c->meshdist_lay, c->meshdist_grid, (const int32_t*)c->meshdist_pairs, d_points,
+    hipError_t e = meshfit_closest(c->meshdist.ws, c->meshdist.lay, c->meshdist.grid, (const int32_t*)c->meshdist.pairs, d_points,
                                    n_points, d_dist2, d_face, d_closest, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "meshfit_closest");
 }
@@ -434,7 +476,7 @@ static int meshfit_accumulate(Ctx* c, const float* d_points, int64_t n, const fl
         if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(meshfit)");
     }
     const float md2 = (float)(max_dist * max_dist);
-    hipError_t e = meshfit_step(c->meshfit_ws, c->meshdist_ws, c->meshdist_lay, c->meshdist_grid, (const int32_t*)c->meshdist_pairs,
+    hipError_t e = meshfit_step(c->meshfit_ws, c->meshdist.ws, c->meshdist.lay, c->meshdist.grid, (const int32_t*)c->meshdist.pairs,
                                 d_points, n, d_weights, x, mode, md2, s);
     if (e != hipSuccess) return hip_fail(e, "meshfit_step");
     e = hipMemcpyAsync(c->h_fit, c->meshfit_ws, sizeof(MeshfitRecord), hipMemcpyDeviceToHost, s);
@@ -448,7 +490,7 @@ static int meshfit_accumulate(Ctx* c, const float* d_points, int64_t n, const fl
 }
 
 static int meshfit_check(const char* who, Ctx* c, const float* d_points, int64_t n, int mode, double max_dist) {
-    if (!c->meshdist_built) return fail(R3G_ERR_STATE, "%s: no successful r3g_meshdist_build on this context", who);
+    if (!c->meshdist.built) return fail(R3G_ERR_STATE, "%s: no successful r3g_meshdist_build on this context", who);
     if (n < 0 || n >= (1ll << 31)) return fail(R3G_ERR_INVALID, "%s: n_points out of range", who);
     if (mode != r3g_md::kFitPoint && mode != r3g_md::kFitPlane) return fail(R3G_ERR_INVALID, "%s: mode must be 0 (point) or 1 (plane)", who);
     if (!(max_dist >= 0.0)) return fail(R3G_ERR_INVALID, "%s: max_dist must be >= 0 (+inf: no limit)", who);
@@ -493,7 +535,7 @@ int r3g_meshfit(r3g_ctx* ctx, const float* d_points, int64_t n_points, const flo
     int updates = 0, converged = 0;
     if (n_points > 0) {
         double centre[3];
-        r3g_md::fit_centre(c->meshdist_grid, centre);
+        r3g_md::fit_centre(c->meshdist.grid, centre);
         const int iw = mode == r3g_md::kFitPlane ? 35 : 0, id = mode == r3g_md::kFitPlane ? 36 : 17;
         for (int it = 0;; ++it) {
             MeshfitRecord rec;
@@ -527,83 +569,29 @@ int r3g_meshfit(r3g_ctx* ctx, const float* d_points, int64_t n_points, const flo
 }
 
 // ---- point in mesh ------------------------------------------------------------------------------------------------
-static int meshinside_small(Ctx* c, hipStream_t s, MeshinsideSmall* out) {
-    hipError_t e = hipMemcpyAsync(c->h_small, c->meshinside_ws + c->meshinside_lay.off_small, sizeof(MeshinsideSmall), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshinside)");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshinside)");
-    memcpy(out, c->h_small, sizeof(MeshinsideSmall));
-    return R3G_OK;
-}
-
 int r3g_meshinside_build(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces, int axis,
                          int resolution, int* resolution_out, int64_t* pairs_out, int64_t* skipped_out, void* stream) {
     if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    c->meshinside_built = false;
-    if (n_verts < 0 || n_verts >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 30))
-        return fail(R3G_ERR_INVALID, "r3g_meshinside_build: mesh size out of range");
-    if (n_faces == 0) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: the mesh has no face");
-    if (!d_faces || (n_verts && !d_verts)) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: null buffer");
-    if (axis < 0 || axis > 2) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: axis outside 0..2");
-    if (resolution < 0 || resolution > r3g_mi::kMaxRes)
-        return fail(R3G_ERR_INVALID, "r3g_meshinside_build: resolution outside [0, %d] (0 = automatic)", r3g_mi::kMaxRes);
-    hipStream_t s = (hipStream_t)stream;
-    int res = resolution ? resolution : r3g_mi::initial_resolution(n_faces);
-    MeshinsideLayout lay;
-    int rc = c->reserve(&c->meshinside_ws, &c->meshinside_ws_bytes, meshinside_workspace_bytes(n_faces, res, &lay), "hipMalloc(meshinside workspace)");
-    if (rc) return rc;
-    c->meshinside_lay = lay;
-    hipError_t e = meshinside_records(c->meshinside_ws, lay, d_verts, n_verts, d_faces, n_faces, axis, s);
-    if (e != hipSuccess) return hip_fail(e, "meshinside_records");
-    MeshinsideSmall sm;
-    if ((rc = meshinside_small(c, s, &sm))) return rc;
-    // (-2 by the contract of include/r3g.h: found on the device, before anything is read through the index)
-    if (sm.bad_index) return fail(-2, "r3g_meshinside_build: a face index lies outside [0, %lld)", (long long)n_verts);
-    if ((int64_t)sm.skipped >= n_faces)
-        return fail(R3G_ERR_INVALID, "r3g_meshinside_build: every face has a non-finite vertex (%lld skipped)", (long long)sm.skipped);
-    float lo[2], hi[2];
-    for (int a = 0; a < 2; ++a) lo[a] = r3g_mi::dec_float(sm.box[a]), hi[a] = r3g_mi::dec_float(sm.box[2 + a]);
-    r3g_mi::Grid2 g;
-    int64_t pairs = 0;
-    for (;;) {
-        g = r3g_mi::make_grid(lo, hi, res);
-        e = meshinside_count_pairs(c->meshinside_ws, lay, n_faces, g, s);
-        if (e != hipSuccess) return hip_fail(e, "meshinside_count_pairs");
-        if ((rc = meshinside_small(c, s, &sm))) return rc;
-        pairs = (int64_t)sm.pairs;
-        if (resolution || res == 1 || pairs <= r3g_mi::kPairMult * n_faces) break;
-        res /= 2;       // e.g. one face that spans the box: R^2 pairs of its own
-    }
-    if (pairs >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshinside_build: %lld (face, column) pairs at resolution %d; force a lower one", (long long)pairs, res);
-    rc = c->reserve(&c->meshinside_pairs, &c->meshinside_pairs_bytes, 4 * (size_t)pairs, "hipMalloc(meshinside pairs)");
-    if (rc) return rc;
-    e = meshinside_fill(c->meshinside_ws, lay, n_faces, g, (int32_t*)c->meshinside_pairs, s);
-    if (e != hipSuccess) return hip_fail(e, "meshinside_fill");
-    e = hipStreamSynchronize(s);      // the caller may free its mesh buffers, and a fault would surface here
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshinside_fill)");
-    c->meshinside_grid = g;
-    c->meshinside_axis = axis;
-    c->meshinside_built = true;
-    if (resolution_out) *resolution_out = res;
-    if (pairs_out) *pairs_out = pairs;
-    if (skipped_out) *skipped_out = (int64_t)sm.skipped;
-    return R3G_OK;
+    const int rc = grid_csr_build(c, &c->meshinside, MeshinsideBuild{axis}, d_verts, n_verts, d_faces, n_faces, resolution, resolution_out,
+                                  pairs_out, skipped_out, (hipStream_t)stream);
+    if (rc == R3G_OK) c->meshinside_axis = axis;
+    return rc;
 }
 
 int r3g_meshinside_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, int32_t* d_count, void* stream) {
     if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshinside_query: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c->meshinside_built) return fail(R3G_ERR_STATE, "r3g_meshinside_query: no successful r3g_meshinside_build on this context");
+    if (!c->meshinside.built) return fail(R3G_ERR_STATE, "r3g_meshinside_query: no successful r3g_meshinside_build on this context");
     if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshinside_query: n_points out of range");
     if (n_points == 0) return R3G_OK;
     if (!d_points || !d_count) return fail(R3G_ERR_INVALID, "r3g_meshinside_query: null buffer");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = meshinside_query(c->meshinside_ws, c->meshinside_lay, c->meshinside_grid, c->meshinside_axis,
-                                    (const int32_t*)c->meshinside_pairs, d_points, n_points, d_count, s);
+    hipError_t e = meshinside_query(c->meshinside.ws, c->meshinside.lay, c->meshinside.grid, c->meshinside_axis,
+                                    (const int32_t*)c->meshinside.pairs, d_points, n_points, d_count, s);
     if (e != hipSuccess) return hip_fail(e, "meshinside_query");
-    MeshinsideSmall sm;
-    int rc = meshinside_small(c, s, &sm);
+    GridCsrSmall sm;
+    int rc = grid_small(c, c->meshinside.ws, c->meshinside.lay, "meshinside", s, &sm);
     if (rc) return rc;
     meshinside_add_tests((int64_t)sm.tests);
     return R3G_OK;

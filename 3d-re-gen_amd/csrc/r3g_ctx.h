@@ -43,27 +43,15 @@ struct Ctx {
     char* mesh_ws = nullptr;
     size_t mesh_ws_bytes = 0;
     // mesh distance: the grid of the last r3g_meshdist_build (records, CSR starts; the pair list has its own buffer)
-    char* meshdist_ws = nullptr;
-    size_t meshdist_ws_bytes = 0;
-    char* meshdist_pairs = nullptr;
-    size_t meshdist_pairs_bytes = 0;
-    MeshdistLayout meshdist_lay{};
-    r3g_md::Grid meshdist_grid{};
-    bool meshdist_built = false;
+    GridCsrState<3> meshdist;
     // mesh registration: the partial records of a fit step, and the pinned buffer its result is read back through (the sums
     // do not fit h_small); both made on first use
     char* meshfit_ws = nullptr;
     size_t meshfit_ws_bytes = 0;
     char* h_fit = nullptr;
     // point in mesh: the columns of the last r3g_meshinside_build (separate from the distance grid: both may be held at once)
-    char* meshinside_ws = nullptr;
-    size_t meshinside_ws_bytes = 0;
-    char* meshinside_pairs = nullptr;
-    size_t meshinside_pairs_bytes = 0;
-    MeshinsideLayout meshinside_lay{};
-    r3g_mi::Grid2 meshinside_grid{};
+    GridCsrState<2> meshinside;
     int meshinside_axis = 0;
-    bool meshinside_built = false;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
     // fit h_small), made on first use

@@ -8,77 +8,20 @@
 
 #include <vector>
 
+#include "meshdist_host.h"
 #include "meshfit_core.h"
 
 using namespace r3g_md;
 
 namespace {
 
-struct Target {
-    std::vector<Tri> tris;
-    std::vector<uint32_t> starts;
-    std::vector<int32_t> list;
-    Grid g;
-};
-
 // the grid build of meshdist_emu.cpp; -> 0, -2 for an index outside [0, nv), -1 for a mesh without a usable face
 int make_target(const float* v, int64_t nv, const int32_t* f, int64_t nf, int resolution, Target& T) {
-    uint32_t elo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, ehi[3] = {0, 0, 0};
-    int64_t skipped = 0;
-    T.tris.resize(nf);
-    for (int64_t i = 0; i < nf; ++i) {
-        Tri t{};
-        const int32_t i0 = f[3 * i], i1 = f[3 * i + 1], i2 = f[3 * i + 2];
-        if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return -2;
-        t.ax = v[3 * i0], t.ay = v[3 * i0 + 1], t.az = v[3 * i0 + 2];
-        t.bx = v[3 * i1], t.by = v[3 * i1 + 1], t.bz = v[3 * i1 + 2];
-        t.cx = v[3 * i2], t.cy = v[3 * i2 + 1], t.cz = v[3 * i2 + 2];
-        if (tri_finite(t)) {
-            t.valid = 1;
-            const float c[9] = {t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz};
-            for (int k = 0; k < 9; ++k) {
-                const uint32_t e = enc_float(c[k]);
-                if (e < elo[k % 3]) elo[k % 3] = e;
-                if (e > ehi[k % 3]) ehi[k % 3] = e;
-            }
-        } else {
-            ++skipped;
-        }
-        T.tris[i] = t;
-    }
-    if (nf == 0 || skipped >= nf || resolution < 0 || resolution > kMaxRes) return -1;
     float lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) lo[a] = dec_float(elo[a]), hi[a] = dec_float(ehi[a]);
-    int res = resolution ? resolution : initial_resolution(nf);
-    int64_t pairs = 0;
-    for (;;) {
-        T.g = make_grid(lo, hi, res);
-        pairs = 0;
-        for (int64_t k = 0; k < nf; ++k)
-            if (T.tris[k].valid) pairs += tri_pairs(T.g, T.tris[k]);
-        if (resolution || res == 1 || pairs <= kPairMult * nf) break;
-        res /= 2;
-    }
-    const int64_t cells = (int64_t)res * res * res;
-    T.starts.assign(cells + 1, 0);
-    std::vector<uint32_t> cursor(cells, 0);
-    T.list.resize(pairs);
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int64_t k = 0; k < nf; ++k) {
-            if (!T.tris[k].valid) continue;
-            int l[3], h[3];
-            tri_range(T.g, T.tris[k], l, h);
-            for (int z = l[2]; z <= h[2]; ++z)
-                for (int y = l[1]; y <= h[1]; ++y)
-                    for (int x = l[0]; x <= h[0]; ++x) {
-                        const int cell = cell_index(T.g, x, y, z);
-                        if (pass == 0) ++T.starts[cell + 1];
-                        else T.list[T.starts[cell] + cursor[cell]++] = (int32_t)k;
-                    }
-        }
-        if (pass == 0)
-            for (int64_t c = 0; c < cells; ++c) T.starts[c + 1] += T.starts[c];
-    }
+    const int64_t skipped = make_records(v, nv, f, nf, T.recs, lo, hi);
+    if (skipped < 0) return (int)skipped;
+    if (nf == 0 || skipped >= nf || resolution < 0 || resolution > kMaxRes) return -1;
+    T.build(lo, hi, resolution, initial_resolution(nf), false);
     return 0;
 }
 
@@ -94,7 +37,7 @@ void accumulate(const Target& T, const float* p, int64_t n, const float* w, cons
             for (int k = 0; k < K; ++k) acc[k] = 0.0;
             for (int64_t i = b * kFitBlock + t; i < n; i += nb * kFitBlock) {
                 uint32_t u = 0, nt = 0;
-                fit_point<MODE>(T.g, T.tris.data(), T.starts.data(), T.list.data(), x, p[3 * i], p[3 * i + 1], p[3 * i + 2],
+                fit_point<MODE>(T.g, T.recs.data(), T.starts.data(), T.list.data(), x, p[3 * i], p[3 * i + 1], p[3 * i + 2],
                                 w ? w[i] : 1.0f, md2, acc, &u, &nt);
                 used += u;
             }
@@ -152,9 +95,9 @@ int r3g_emu_mf_closest(const float* v, int64_t nv, const int32_t* f, int64_t nf,
     const int rc = make_target(v, nv, f, nf, resolution, T);
     if (rc) return rc;
     for (int64_t i = 0; i < n; ++i) {
-        nearest(T.g, T.tris.data(), T.starts.data(), T.list.data(), p[3 * i], p[3 * i + 1], p[3 * i + 2], &dist2[i], &face[i], nullptr);
+        nearest(T.g, T.recs.data(), T.starts.data(), T.list.data(), p[3 * i], p[3 * i + 1], p[3 * i + 2], &dist2[i], &face[i], nullptr);
         if (face[i] >= 0) {
-            dist2[i] = tri_closest(p[3 * i], p[3 * i + 1], p[3 * i + 2], T.tris[face[i]], &closest[3 * i], &closest[3 * i + 1], &closest[3 * i + 2]);
+            dist2[i] = tri_closest(p[3 * i], p[3 * i + 1], p[3 * i + 2], T.recs[face[i]], &closest[3 * i], &closest[3 * i + 1], &closest[3 * i + 2]);
         } else {
             dist2[i] = closest[3 * i] = closest[3 * i + 1] = closest[3 * i + 2] = quiet_nan();
         }

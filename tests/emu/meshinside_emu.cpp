@@ -1,10 +1,7 @@
 // meshinside_emu.cpp -- host instantiation of csrc/meshinside_core.h (test only): (a) the brute force over every usable face
-// with the product's `crossed`, (b) the column build (count -> scan -> fill) and the query as host loops.
+// with the product's `crossed`, (b) the column build (csrc/grid_csr.h through host_grid.h) and the query as host loops.
 // Built with -ffp-contract=off, like the kernels.
-#include <stdint.h>
-
-#include <vector>
-
+#include "host_grid.h"
 #include "meshinside_core.h"
 
 using namespace r3g_mi;
@@ -24,7 +21,7 @@ int64_t make_records(const float* v, int64_t nv, const int32_t* f, int64_t nf, i
         if (rec_finite(r)) {
             const float c[6] = {r.au, r.av, r.bu, r.bv, r.cu, r.cv};
             for (int k = 0; k < 6; ++k) {
-                const uint32_t e = enc_float(c[k]);
+                const uint32_t e = r3g_grid::enc_float(c[k]);
                 if (e < elo[k % 2]) elo[k % 2] = e;
                 if (e > ehi[k % 2]) ehi[k % 2] = e;
             }
@@ -35,7 +32,7 @@ int64_t make_records(const float* v, int64_t nv, const int32_t* f, int64_t nf, i
         }
         recs[i] = r;
     }
-    for (int a = 0; a < 2; ++a) lo[a] = dec_float(elo[a]), hi[a] = dec_float(ehi[a]);
+    for (int a = 0; a < 2; ++a) lo[a] = r3g_grid::dec_float(elo[a]), hi[a] = r3g_grid::dec_float(ehi[a]);
     return skipped;
 }
 
@@ -74,50 +71,21 @@ int r3g_emu_meshinside_grid(const float* v, int64_t nv, const int32_t* f, int64_
                             const float* p, int64_t n, int32_t* count, int* resolution_out, int64_t* pairs_out,
                             int64_t* skipped_out, int64_t* tests_out) {
     if (axis < 0 || axis > 2) return -1;
-    std::vector<Rec> recs;
+    HostGrid<2, Rec> T;
     float lo[2], hi[2];
-    const int64_t skipped = make_records(v, nv, f, nf, axis, recs, lo, hi);
+    const int64_t skipped = make_records(v, nv, f, nf, axis, T.recs, lo, hi);
     if (skipped < 0) return (int)skipped;
     if (nf == 0 || skipped >= nf) return -1;
     if (resolution < 0 || resolution > kMaxRes) return -1;
-    int res = resolution ? resolution : initial_resolution(nf);
-    Grid2 g;
-    int64_t pairs = 0;
-    for (;;) {
-        g = make_grid(lo, hi, res);
-        pairs = 0;
-        for (int64_t k = 0; k < nf; ++k)
-            if (recs[k].ia >= 0) pairs += rec_pairs(g, recs[k]);
-        if (resolution || res == 1 || pairs <= kPairMult * nf) break;
-        res /= 2;
-    }
-    const int64_t cols = (int64_t)res * res;
-    std::vector<uint32_t> starts(cols + 1, 0), cursor(cols, 0);
-    std::vector<int32_t> list(pairs);
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int64_t kk = 0; kk < nf; ++kk) {
-            const int64_t k = (pass == 1 && reverse_fill) ? nf - 1 - kk : kk;
-            if (recs[k].ia < 0) continue;
-            int l[2], h[2];
-            rec_range(g, recs[k], l, h);
-            for (int y = l[1]; y <= h[1]; ++y)
-                for (int x = l[0]; x <= h[0]; ++x) {
-                    const int col = col_index(g, x, y);
-                    if (pass == 0) ++starts[col + 1];
-                    else list[starts[col] + cursor[col]++] = (int32_t)k;
-                }
-        }
-        if (pass == 0)
-            for (int64_t c = 0; c < cols; ++c) starts[c + 1] += starts[c];
-    }
+    T.build(lo, hi, resolution, initial_resolution(nf), reverse_fill != 0);
     int64_t tests = 0;
     for (int64_t i = 0; i < n; ++i) {
         uint32_t nt = 0;
-        count[i] = count_crossings(g, axis, recs.data(), starts.data(), list.data(), p[3 * i], p[3 * i + 1], p[3 * i + 2], &nt);
+        count[i] = count_crossings(T.g, axis, T.recs.data(), T.starts.data(), T.list.data(), p[3 * i], p[3 * i + 1], p[3 * i + 2], &nt);
         tests += nt;
     }
-    if (resolution_out) *resolution_out = res;
-    if (pairs_out) *pairs_out = pairs;
+    if (resolution_out) *resolution_out = T.g.res;
+    if (pairs_out) *pairs_out = T.pairs;
     if (skipped_out) *skipped_out = skipped;
     if (tests_out) *tests_out = tests;
     return 0;

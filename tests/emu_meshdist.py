@@ -17,7 +17,8 @@ def _lib():
         so = os.path.join(_HERE, "libr3g_meshdist_emu.so")
         src = os.path.join(_HERE, "meshdist_emu.cpp")
         csrc = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-        deps = [src, os.path.join(csrc, "meshdist_core.h")]
+        deps = [src, os.path.join(csrc, "meshdist_core.h"), os.path.join(csrc, "grid_csr.h"), os.path.join(_HERE, "host_grid.h"),
+                os.path.join(_HERE, "meshdist_host.h")]
         if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
                                    "-I" + csrc, "-o", so, src])

@@ -17,7 +17,7 @@ def _lib():
         so = os.path.join(_HERE, "libr3g_meshinside_emu.so")
         src = os.path.join(_HERE, "meshinside_emu.cpp")
         csrc = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-        deps = [src, os.path.join(csrc, "meshinside_core.h")]
+        deps = [src, os.path.join(csrc, "meshinside_core.h"), os.path.join(csrc, "grid_csr.h"), os.path.join(_HERE, "host_grid.h")]
         if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
                                    "-I" + csrc, "-o", so, src])

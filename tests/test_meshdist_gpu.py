@@ -63,6 +63,15 @@ def test_device_equals_the_twin_bit_for_bit(n, resolution):
     assert info["pairs"] == emu.grid(p[:1], v, f, info["resolution"])[2]["pairs"]
 
 
+@pytest.mark.parametrize("resolution", [127, 128])
+def test_forced_resolutions_on_either_side_of_the_scan_switch(resolution):
+    """127^3 + 1 cells are 1001 scan tiles, 128^3 + 1 are 1025: one block scans the tile sums 4 or 40 to a thread"""
+    v, f, p, a2, af = soup_twin()
+    d2, face, info = gpu_dist2(p[:65], v, f, resolution)
+    assert np.array_equal(bits(d2), bits(a2[:65])) and np.array_equal(face, af[:65])
+    assert info["resolution"] == resolution and info["pairs"] == emu.grid(p[:1], v, f, resolution)[2]["pairs"]
+
+
 def test_two_runs_are_identical_and_the_resolution_does_not_matter():
     import torch
     from r3g import meshdist

@@ -75,6 +75,14 @@ def test_device_equals_the_twin(n, axis):
         assert np.array_equal(got, first)                         # the result does not depend on the resolution
 
 
+def test_the_highest_resolution():
+    """1024^2 + 1 columns: 513 scan tiles, the most the columns can ask of the scan"""
+    v, f, p, want = soup_twin(2)
+    got, info = gpu_counts(p[:65], v, f, 2, 1024)
+    assert np.array_equal(got, want[:65])
+    assert info["resolution"] == 1024 and info["pairs"] == emu.grid(p[:1], v, f, 2, 1024)[1]["pairs"]
+
+
 @pytest.mark.parametrize("axis", [0, 1, 2])
 def test_cube_literals_and_the_sphere_lattice(axis):
     v, f = ref.cube()
