@@ -15,9 +15,7 @@
 
 #include <stdint.h>
 
-#ifndef R3G_DEV
-#define R3G_DEV static inline
-#endif
+#include "surf_common.h"   // R3G_DEV default, range flags, Xform, store_vertex
 #include "dmc_luts.h"
 
 #if defined(__clang__)
@@ -26,9 +24,9 @@
 #define R3G_DMC_UNROLL
 #endif
 
-#define R3G_DMC_FLAG_LE 1u   // some sample <= level
-#define R3G_DMC_FLAG_GE 2u   // some sample >= level
-#define R3G_DMC_FLAG_NAN 4u  // some sample is NaN
+#define R3G_DMC_FLAG_LE R3G_SURF_FLAG_LE    // some sample <= level
+#define R3G_DMC_FLAG_GE R3G_SURF_FLAG_GE    // some sample >= level
+#define R3G_DMC_FLAG_NAN R3G_SURF_FLAG_NAN  // some sample is NaN
 
 namespace r3g_dmc {
 
@@ -42,12 +40,9 @@ struct CellRef {
     uint32_t ecase;  // effective case (the complemented one where the manifold rule applies)
 };
 
-// output transform, as r3g_mc_emit: per OUTPUT column (axis0, axis1, axis2), applied to the float32 value in double
-struct Xform {
-    double grid_size[3];
-    double bbox_size[3];
-    double bbox_min[3];
-};
+// output transform, as r3g_mc_emit (surf_common.h); positions are already in output-column order
+using r3g_surf::Xform;
+using r3g_surf::store_vertex;
 
 R3G_DEV int lut_patch(uint64_t w, int e) { return (int)((w >> (4 * e)) & 0xFu); }
 R3G_DEV int lut_count(uint64_t w) { return (int)((w >> 48) & 0x7u); }
@@ -109,17 +104,6 @@ R3G_DEV unsigned classify_cell(const float* g, const Dims& d, int i, int j, int 
 }
 R3G_DEV unsigned rec_patches(unsigned rec) { return (rec >> 12) & 0x7u; }
 R3G_DEV unsigned rec_quads(unsigned rec) { return (rec >> 16) & 0x3u; }
-
-R3G_DEV void store_vertex(float* dst, double p0, double p1, double p2, const Xform& xf, bool use_xf) {
-    const float o0 = (float)p0, o1 = (float)p1, o2 = (float)p2;
-    if (use_xf) {
-        dst[0] = (float)((double)o0 / xf.grid_size[0] * xf.bbox_size[0] + xf.bbox_min[0]);
-        dst[1] = (float)((double)o1 / xf.grid_size[1] * xf.bbox_size[1] + xf.bbox_min[1]);
-        dst[2] = (float)((double)o2 / xf.grid_size[2] * xf.bbox_size[2] + xf.bbox_min[2]);
-    } else {
-        dst[0] = o0; dst[1] = o1; dst[2] = o2;
-    }
-}
 
 // Pass 3: the vertices of one active cell, and its entry in the cell table.  Per patch: the crossing points of its
 // edges in ascending edge number, summed in double, divided by their number, rounded once.  Loops over the edges are

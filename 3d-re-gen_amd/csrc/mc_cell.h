@@ -22,12 +22,7 @@
 
 #include <stdint.h>
 
-#ifndef R3G_DEV
-#define R3G_DEV static inline
-#endif
-#ifndef R3G_HOSTDEV
-#define R3G_HOSTDEV static inline
-#endif
+#include "surf_common.h"   // R3G_DEV / R3G_HOSTDEV defaults, range flags, Xform, store_vertex
 #include "mc_luts.h"
 
 #if defined(__clang__)
@@ -300,27 +295,10 @@ R3G_DEV void center_vertex(const double* v, int x, int y, int z, double* out) {
     out[2] = (double)z + 1.0 * fz / ff;
 }
 
-// Output transform of one vertex.  pos = kernel (x,y,z); the wrapper returns (z,y,x) float32.
-// With use_xf the upstream hy3dgen rescale is applied on the float32 value in double:
-//   v / grid_size * bbox_size + bbox_min   (surface_extractors.MCSurfaceExtractor.run)
-struct Xform {
-    double grid_size[3];  // per OUTPUT column (axis0, axis1, axis2)
-    double bbox_size[3];
-    double bbox_min[3];
-};
-
-R3G_DEV void store_vertex(float* dst, const double* pos, const Xform& xf, bool use_xf) {
-    const float o0 = (float)pos[2], o1 = (float)pos[1], o2 = (float)pos[0];
-    if (use_xf) {
-        dst[0] = (float)((double)o0 / xf.grid_size[0] * xf.bbox_size[0] + xf.bbox_min[0]);
-        dst[1] = (float)((double)o1 / xf.grid_size[1] * xf.bbox_size[1] + xf.bbox_min[1]);
-        dst[2] = (float)((double)o2 / xf.grid_size[2] * xf.bbox_size[2] + xf.bbox_min[2]);
-    } else {
-        dst[0] = o0;
-        dst[1] = o1;
-        dst[2] = o2;
-    }
-}
+// Output transform of one vertex (surf_common.h).  A position is the kernel's (x,y,z); the wrapper returns (z,y,x) float32,
+// so store_vertex is called with (pos[2], pos[1], pos[0]).
+using r3g_surf::Xform;
+using r3g_surf::store_vertex;
 
 // ---------------------------------------------------------------------------------------------
 // Per-cell bodies of the three passes (shared by the HIP kernels and the host emulation).
@@ -330,9 +308,9 @@ R3G_DEV void store_vertex(float* dst, const double* pos, const Xform& xf, bool u
 // Pass 3 "vertices": the owner computes its vertices and publishes their ids in the edge table.
 // Pass 4 "faces": every triangle corner resolves to an id (own rank or edge-table lookup).
 // ---------------------------------------------------------------------------------------------
-#define R3G_MC_FLAG_LE 1u   // some sample <= level
-#define R3G_MC_FLAG_GE 2u   // some sample >= level
-#define R3G_MC_FLAG_NAN 4u  // some sample is NaN
+#define R3G_MC_FLAG_LE R3G_SURF_FLAG_LE    // some sample <= level
+#define R3G_MC_FLAG_GE R3G_SURF_FLAG_GE    // some sample >= level
+#define R3G_MC_FLAG_NAN R3G_SURF_FLAG_NAN  // some sample is NaN
 
 R3G_DEV unsigned load_corners(const float* g, int nx, int ny, int x, int y, int z, double level,
                               double* v, int* index) {
@@ -443,7 +421,7 @@ R3G_DEV void emit_cell_vertices(unsigned rec, unsigned vbase, const float* g, do
             edge_vertex_ab(a, b, e, x, y, z, pos);
             etab[edge_slot(e, x, y, z, nx, ny)] = (int32_t)id;
         }
-        store_vertex(verts + 3 * (int64_t)id, pos, xf, use_xf);
+        store_vertex(verts + 3 * (int64_t)id, pos[2], pos[1], pos[0], xf, use_xf);
         ++id;
     }
 }

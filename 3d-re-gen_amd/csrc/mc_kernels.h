@@ -5,29 +5,23 @@
 #include <stddef.h>
 #include <stdint.h>
 
-namespace r3g {
+#include "surf_compact_kernels.h"
 
-struct McWorkspaceLayout {
-    uint32_t nblk, nchunk, ncells;
-    uint32_t nnz;                     // non-empty blocks: filled in by the caller from totals[2] after the count pass
-    uint64_t off_small, small_bytes;  // status(u32) @0, totals {nV, nF, nNZ} (3 x u64) @16, chunk sums @64
-    uint64_t zero_bytes;              // bytes from off_small that mc_count_launch clears
-    uint64_t off_blk, off_blkoff, off_nz, off_act, off_etab;
-};
+namespace r3g {
 
 void mc_set_deferred(bool on);         // row kernel: tiling selection batched per wave (default) or per row
 void mc_set_rows_per_wave(int rows);  // node rows a wave marches through in the row kernel (4|8|16|32)
 bool mc_get_deferred();
 int mc_get_rows_per_wave();
-size_t mc_workspace_bytes(int n0, int n1, int n2, McWorkspaceLayout* lay);
+size_t mc_workspace_bytes(int n0, int n1, int n2, SurfWorkspaceLayout* lay);
 
-// K1 + K2.  After the stream drains: status word at ws+off_small, totals {nV, nF, nNZ} at +16.
+// K1 + K2 (surf_scan_launch).  After the stream drains: status word at ws+off_small, totals {nV, nF, nNZ} at +16.
 hipError_t mc_count_launch(const float* grid, int n0, int n1, int n2, double level, int classic, char* ws,
-                           const McWorkspaceLayout& lay, hipStream_t stream);
+                           const SurfWorkspaceLayout& lay, hipStream_t stream);
 
 // K3 + K4.  xf9 = {grid_size[3], bbox_size[3], bbox_min[3]} or null (index-space vertices).
 hipError_t mc_emit_launch(const float* grid, int n0, int n1, int n2, double level, char* ws,
-                          const McWorkspaceLayout& lay, float* verts, int32_t* faces, const double* xf9,
+                          const SurfWorkspaceLayout& lay, float* verts, int32_t* faces, const double* xf9,
                           int reversed, hipStream_t stream);
 
 }  // namespace r3g

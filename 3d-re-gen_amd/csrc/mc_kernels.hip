@@ -19,12 +19,15 @@
 //       mc_classify_rows  (option mc_deferred=0): round 1's variant, per-lane bit masks and the tiling selection
 //                    per row; kept as the cross-check (same outputs bit for bit).
 //       mc_classify      (any other shape): one thread per cell, 8 coalesced row reads, LDS across 4 waves.
-//   K2 mc_scan     : exclusive scan of the block sums (one workgroup per 1024-block chunk) + the
-//                    compacted list of non-empty blocks.
+//   K2 surf_scan   : exclusive scan of the block sums (one workgroup per 1024-block chunk) + the
+//                    compacted list of non-empty blocks (surf_compact_kernels.hip).
 //   K3 mc_vertices : 1 thread per ACTIVE cell: fp64 interpolation, float32 store, edge->id table.
 //   K4 mc_faces    : 1 thread per ACTIVE cell: triangle corners -> ids (own rank or table lookup).
-//                    K3/K4 are launched over the non-empty blocks only, 8 consecutive ones per 256-thread workgroup (24 measured slower: too few workgroups).
+//                    K3/K4 are launched over the non-empty blocks only, 8 consecutive ones per 256-thread workgroup.
 // Only K1 touches the whole grid: algorithmic traffic = one grid read + one mesh write.
+// The skeleton around the per-cell bodies -- block compaction at the end of mc_classify, the scan, the workspace, the
+// emit kernels' walk over the non-empty blocks -- is shared with dual marching cubes: surf_compact_device.h,
+// surf_compact_kernels.{h,hip}.  The row kernels publish per wave with a segmented scan of their own.
 //
 // Built with -ffp-contract=off: the ambiguity tests and interpolation must not be fused.
 #include <hip/hip_runtime.h>
@@ -37,15 +40,14 @@
 #include "mc_cell.h"
 #include "mc_kernels.h"
 #include "prof.h"
+#include "surf_compact_device.h"
 
 #pragma clang fp contract(off)
 
 using namespace r3g_mc;
+using namespace r3g_surf;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kChunk = 1024;  // blocks per scan chunk
 
 __device__ __forceinline__ void cell_coords(uint32_t c, int cx, int cy, int& x, int& y, int& z) {
     const uint32_t row = c / (uint32_t)cx;
@@ -54,24 +56,13 @@ __device__ __forceinline__ void cell_coords(uint32_t c, int cx, int cy, int& x, 
     y = (int)(row - (uint32_t)z * (uint32_t)cy);
 }
 
-// inclusive scan of a packed 3x16-bit counter across the 64 lanes of a wave
-__device__ __forceinline__ unsigned long long wave_inclusive_scan(unsigned long long v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long n = __shfl_up(v, d, 64);
-        if (lane >= d) v += n;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kBlock) void mc_classify(const float* __restrict__ grid, int nx, int ny, int cx,
                                                       int cy, uint32_t ncells, double level, int classic,
                                                       uint2* __restrict__ act, uint4* __restrict__ blk,
                                                       unsigned long long* __restrict__ chunk_sums,
                                                       unsigned* __restrict__ chunk_nz,
                                                       unsigned* __restrict__ status) {
-    __shared__ unsigned long long wave_tot[kBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     const uint32_t b = blockIdx.x;
     const uint32_t c = b * kBlock + tid;
     unsigned rec = 0, flags = 0;
@@ -89,13 +80,7 @@ __global__ __launch_bounds__(kBlock) void mc_classify(const float* __restrict__ 
         flags = load_signs(grid, nx, ny, x, y, z, level, &index);
     }
     const bool active = index != 0 && index != 255;
-    // range flags: one global atomic per wave, and only while it would still change the status word
-    {
-        const unsigned long long le = __ballot(flags & R3G_MC_FLAG_LE), ge = __ballot(flags & R3G_MC_FLAG_GE),
-                                 nn = __ballot(flags & R3G_MC_FLAG_NAN);
-        const unsigned wf = (le ? R3G_MC_FLAG_LE : 0u) | (ge ? R3G_MC_FLAG_GE : 0u) | (nn ? R3G_MC_FLAG_NAN : 0u);
-        if (lane == 0 && (wf & ~*(volatile unsigned*)status)) atomicOr(status, wf);
-    }
+    publish_range_flags(flags, status);
     // most blocks contain no surface cell: they publish zeros and leave before the tiling / scan work
     if (!__syncthreads_or(active ? 1 : 0)) {
         if (tid == 0) blk[b] = make_uint4(0u, 0u, 0u, 0u);
@@ -107,33 +92,8 @@ __global__ __launch_bounds__(kBlock) void mc_classify(const float* __restrict__ 
         load_corners(grid, nx, ny, x, y, z, level, v, &idx2);
         rec = classify_cell(v, index, classic != 0, x, y, z);
     }
-    // packed counters: [0..15] new vertices, [16..31] triangles, [32..47] active cells
-    const unsigned long long mine = (unsigned long long)((rec >> 20) & 0xFu) |
-                                    ((unsigned long long)((rec >> 16) & 0xFu) << 16) |
-                                    ((unsigned long long)(rec ? 1u : 0u) << 32);
-    const unsigned long long incl = wave_inclusive_scan(mine, lane);
-    if (lane == 63) wave_tot[wid] = incl;
-    __syncthreads();
-    unsigned long long base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        const unsigned long long t = wave_tot[w];
-        if (w < wid) base += t;
-        total += t;
-    }
-    const unsigned long long excl = base + incl - mine;
-    if (rec) {
-        const unsigned vloc = (unsigned)(excl & 0xFFFFu), tloc = (unsigned)((excl >> 16) & 0xFFFFu);
-        const unsigned arank = (unsigned)((excl >> 32) & 0xFFFFu);
-        act[(size_t)b * kBlock + arank] = make_uint2(rec, (unsigned)tid | (vloc << 8) | (tloc << 20));
-    }
-    if (tid == 0) {
-        const unsigned sv = (unsigned)(total & 0xFFFFu), st = (unsigned)((total >> 16) & 0xFFFFu);
-        const unsigned sa = (unsigned)((total >> 32) & 0xFFFFu);
-        blk[b] = make_uint4(sv, st, sa, 0u);
-        if (sv | st) atomicAdd(&chunk_sums[b / kChunk], (unsigned long long)sv | ((unsigned long long)st << 32));
-        if (sa) atomicAdd(&chunk_nz[b / kChunk], 1u);
-    }
+    // record: bits 16..19 triangle count, 20..23 new-vertex count
+    publish_block(rec, (rec >> 20) & 0xFu, (rec >> 16) & 0xFu, b, act, blk, chunk_sums, chunk_nz);
 }
 
 // ---- row kernel ------------------------------------------------------------------------------------------------
@@ -286,10 +246,7 @@ void mc_classify_rows(const float* __restrict__ grid, int nx, int ny, int cx, in
         if (acc_sum) atomicAdd(&chunk_sums[acc_chunk], acc_sum);
         atomicAdd(&chunk_nz[acc_chunk], acc_nz);
     }
-    const unsigned long long le = __ballot(flags & R3G_MC_FLAG_LE), ge = __ballot(flags & R3G_MC_FLAG_GE),
-                             nn = __ballot(flags & R3G_MC_FLAG_NAN);
-    const unsigned wf = (le ? R3G_MC_FLAG_LE : 0u) | (ge ? R3G_MC_FLAG_GE : 0u) | (nn ? R3G_MC_FLAG_NAN : 0u);
-    if (lane == 0 && (wf & ~*(volatile unsigned*)status)) atomicOr(status, wf);
+    publish_range_flags(flags, status);
 }
 
 // ---- row kernel, second version: the tiling selection is DEFERRED.  While a wave streams its node rows it only appends
@@ -478,119 +435,11 @@ void mc_classify_rows2(const float* __restrict__ grid, int nx, int ny, int cx, i
             }
         }
     }
-    const unsigned long long le = __ballot(flags & R3G_MC_FLAG_LE), ge = __ballot(flags & R3G_MC_FLAG_GE),
-                             nn = __ballot(flags & R3G_MC_FLAG_NAN);
-    const unsigned wf = (le ? R3G_MC_FLAG_LE : 0u) | (ge ? R3G_MC_FLAG_GE : 0u) | (nn ? R3G_MC_FLAG_NAN : 0u);
-    if (lane == 0 && (wf & ~*(volatile unsigned*)status)) atomicOr(status, wf);
+    publish_range_flags(flags, status);
 }
 
-// One workgroup per chunk of 1024 block sums.  base = sum of all earlier chunks (<= a few hundred
-// values), then an exclusive scan inside the chunk.  The last chunk publishes the totals.
-__global__ __launch_bounds__(kChunk) void mc_scan(const uint4* __restrict__ blk, uint32_t nblk,
-                                                  const unsigned long long* __restrict__ chunk_sums,
-                                                  const unsigned* __restrict__ chunk_nz,
-                                                  uint2* __restrict__ blkoff, uint32_t* __restrict__ nzlist,
-                                                  unsigned long long* __restrict__ totals) {
-    __shared__ unsigned long long s_red[kChunk / 64];
-    __shared__ unsigned long long s_wave[kChunk / 64];
-    __shared__ unsigned s_red_nz[kChunk / 64];
-    __shared__ unsigned s_wave_nz[kChunk / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const uint32_t ch = blockIdx.x;
-    // both halves are < 2^32 in total for any grid the API admits, so packed 2x32 adds cannot carry
-    unsigned long long part = 0;
-    unsigned part_nz = 0;
-    for (uint32_t i = tid; i < ch; i += kChunk) {
-        part += chunk_sums[i];
-        part_nz += chunk_nz[i];
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        part += __shfl_xor(part, d, 64);
-        part_nz += __shfl_xor(part_nz, d, 64);
-    }
-    if (lane == 0) { s_red[wid] = part; s_red_nz[wid] = part_nz; }
-    const uint32_t bi = ch * kChunk + tid;
-    unsigned long long mine = 0;
-    unsigned mine_nz = 0;
-    if (bi < nblk) {
-        const uint4 s = blk[bi];
-        mine = (unsigned long long)s.x | ((unsigned long long)s.y << 32);
-        mine_nz = s.z ? 1u : 0u;
-    }
-    unsigned long long incl = mine;
-    unsigned incl_nz = mine_nz;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long n = __shfl_up(incl, d, 64);
-        const unsigned nn = __shfl_up(incl_nz, d, 64);
-        if (lane >= d) { incl += n; incl_nz += nn; }
-    }
-    if (lane == 63) { s_wave[wid] = incl; s_wave_nz[wid] = incl_nz; }
-    __syncthreads();
-    unsigned long long base = 0;
-    unsigned base_nz = 0;
-#pragma unroll
-    for (int w = 0; w < kChunk / 64; ++w) {
-        base += s_red[w];
-        base_nz += s_red_nz[w];
-        if (w < wid) { base += s_wave[w]; base_nz += s_wave_nz[w]; }
-    }
-    const unsigned long long excl = base + incl - mine;
-    const unsigned excl_nz = base_nz + incl_nz - mine_nz;
-    if (bi < nblk) blkoff[bi] = make_uint2((unsigned)(excl & 0xFFFFFFFFull), (unsigned)(excl >> 32));
-    if (mine_nz) nzlist[excl_nz] = bi;
-    if (bi == nblk - 1) {
-        const unsigned long long tot = excl + mine;
-        totals[0] = tot & 0xFFFFFFFFull;
-        totals[1] = tot >> 32;
-        totals[2] = excl_nz + mine_nz;
-    }
-}
-
-// K3 / K4 geometry (round 5): a workgroup of 256 threads takes kEmitGroup (8) CONSECUTIVE non-empty blocks and spreads their active
-// cells over its threads (a prefix over the blocks' active counts in LDS, a short linear search).  Rounds 1-4 gave every non-empty
-// block a 64-thread workgroup of its own: a block of a smooth surface holds ~11 active cells, so five lanes in six idled and an
-// object-sized mesh took 19 855 workgroups per kernel -- 45 + 25 us for 113 k vertices / 226 k faces (profiles/r05_mc_timeline.md).
-// Every output position comes from the scan (block offset + the record's in-block prefix), so the mesh is the same bit for bit.
-constexpr int kEmitGroup = 8;
-constexpr int kEmitWg = 256;
-
-// the calling thread's (block, index of an active cell in it) for item `i` of the workgroup's cells, or false when i is past them
-struct EmitMap {
-    unsigned pre[kEmitGroup + 1];
-    uint32_t blk_id[kEmitGroup];
-};
-__device__ __forceinline__ void emit_map_build(EmitMap* m, const uint4* __restrict__ blk, const uint32_t* __restrict__ nzlist,
-                                               uint32_t nnz) {
-    if (threadIdx.x == 0) {
-        unsigned run = 0;
-#pragma unroll
-        for (int j = 0; j < kEmitGroup; ++j) {
-            const uint32_t g = blockIdx.x * kEmitGroup + j;
-            m->pre[j] = run;
-            if (g < nnz) {
-                const uint32_t b = nzlist[g];
-                m->blk_id[j] = b;
-                run += blk[b].z;
-            } else {
-                m->blk_id[j] = 0;
-            }
-        }
-        m->pre[kEmitGroup] = run;
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ bool emit_map_find(const EmitMap* m, unsigned i, uint32_t* b, unsigned* local) {
-    if (i >= m->pre[kEmitGroup]) return false;
-    int j = 0;
-#pragma unroll
-    for (int k = 1; k < kEmitGroup; ++k) j += (i >= m->pre[k]) ? 1 : 0;
-    *b = m->blk_id[j];
-    *local = i - m->pre[j];
-    return true;
-}
-
+// K3 / K4: one thread per active cell, found through the shared EmitMap (surf_compact_device.h).  Every output position comes
+// from the scan (block offset + the record's in-block prefix), so the mesh is the same bit for bit whatever the grouping.
 __global__ __launch_bounds__(kEmitWg) void mc_vertices(const float* __restrict__ grid, int nx, int ny, int cx, int cy,
                                                       double level, const uint2* __restrict__ act,
                                                       const uint4* __restrict__ blk, const uint2* __restrict__ blkoff,
@@ -644,40 +493,19 @@ void mc_set_rows_per_wave(int rows) { g_rows_per_wave = rows == 4 || rows == 8 |
 bool mc_get_deferred() { return g_deferred; }
 int mc_get_rows_per_wave() { return g_rows_per_wave; }
 
-size_t mc_workspace_bytes(int n0, int n1, int n2, McWorkspaceLayout* lay) {
-    const uint64_t ncells = (uint64_t)(n0 - 1) * (n1 - 1) * (n2 - 1);
-    const uint64_t nblk = (ncells + kBlock - 1) / kBlock;
-    const uint64_t nchunk = (nblk + kChunk - 1) / kChunk;
-    const uint64_t nnodes = (uint64_t)n0 * n1 * n2;
-    auto align = [](uint64_t v) { return (v + 255) & ~(uint64_t)255; };
-    uint64_t o = 0;
-    lay->nblk = (uint32_t)nblk;
-    lay->nchunk = (uint32_t)nchunk;
-    lay->ncells = (uint32_t)ncells;
-    // [status u32 | pad | totals 3xu64 @16 | chunk_sums u64 x nchunk @64 | chunk_nz u32 x nchunk], then the block
-    // sums: this whole prefix is zeroed per call (one memset)
-    lay->off_small = o;
-    lay->small_bytes = align(64 + 12 * nchunk);
-    o += lay->small_bytes;
-    lay->off_blk = o;    o += align(16 * nblk);
-    lay->zero_bytes = o - lay->off_small;
-    lay->off_blkoff = o; o += align(8 * nblk);
-    lay->off_nz = o;     o += align(4 * nblk);
-    lay->nnz = 0;
-    lay->off_act = o;    o += align(8 * nblk * kBlock);
-    lay->off_etab = o;   o += align(12 * nnodes);
-    return (size_t)o;
+size_t mc_workspace_bytes(int n0, int n1, int n2, SurfWorkspaceLayout* lay) {
+    return surf_workspace_bytes(n0, n1, n2, 12 * (uint64_t)n0 * n1 * n2, lay);   // edge -> vertex id table, int32 x 3 per node
 }
 
 hipError_t mc_count_launch(const float* grid, int n0, int n1, int n2, double level, int classic, char* ws,
-                           const McWorkspaceLayout& lay, hipStream_t stream) {
+                           const SurfWorkspaceLayout& lay, hipStream_t stream) {
     const int nx = n2, ny = n1, cx = n2 - 1, cy = n1 - 1, cz = n0 - 1;
+    // small + blk: the row kernels write only the non-empty entries of blk[]
     hipError_t e = hipMemsetAsync(ws + lay.off_small, 0, lay.zero_bytes, stream);
     if (e != hipSuccess) return e;
-    unsigned* status = (unsigned*)(ws + lay.off_small);
-    unsigned long long* totals = (unsigned long long*)(ws + lay.off_small + 16);
-    unsigned long long* chunk_sums = (unsigned long long*)(ws + lay.off_small + 64);
-    unsigned* chunk_nz = (unsigned*)(ws + lay.off_small + 64 + 8 * (size_t)lay.nchunk);
+    unsigned* status = surf_status(ws, lay);
+    unsigned long long* chunk_sums = surf_chunk_sums(ws, lay);
+    unsigned* chunk_nz = surf_chunk_nz(ws, lay);
     {
     ProfScope ps(PC_MC_CLASSIFY, 4.0 * (double)n0 * n1 * n2, stream);
     if (cx % kBlock == 0) {
@@ -704,32 +532,25 @@ hipError_t mc_count_launch(const float* grid, int n0, int n1, int n2, double lev
     }
     }
     ProfScope ps2(PC_MC_OTHER, 0.0, stream);
-    hipLaunchKernelGGL(mc_scan, dim3(lay.nchunk), dim3(kChunk), 0, stream, (const uint4*)(ws + lay.off_blk), lay.nblk,
-                       chunk_sums, chunk_nz, (uint2*)(ws + lay.off_blkoff), (uint32_t*)(ws + lay.off_nz), totals);
-    return hipGetLastError();
+    return surf_scan_launch(ws, lay, stream);
 }
 
 hipError_t mc_emit_launch(const float* grid, int n0, int n1, int n2, double level, char* ws,
-                          const McWorkspaceLayout& lay, float* verts, int32_t* faces, const double* xf9,
+                          const SurfWorkspaceLayout& lay, float* verts, int32_t* faces, const double* xf9,
                           int reversed, hipStream_t stream) {
     (void)n0;
     const int nx = n2, ny = n1, cx = n2 - 1, cy = n1 - 1;
     if (lay.nnz == 0) return hipSuccess;
-    Xform xf;
-    for (int i = 0; i < 3; ++i) {
-        xf.grid_size[i] = xf9 ? xf9[i] : 1.0;
-        xf.bbox_size[i] = xf9 ? xf9[3 + i] : 1.0;
-        xf.bbox_min[i] = xf9 ? xf9[6 + i] : 0.0;
-    }
+    const Xform xf = xform_from(xf9);
     ProfScope ps(PC_MC_OTHER, 0.0, stream);
     const uint32_t* nz = (const uint32_t*)(ws + lay.off_nz);
     const uint32_t wgs = (lay.nnz + kEmitGroup - 1) / kEmitGroup;
     hipLaunchKernelGGL(mc_vertices, dim3(wgs), dim3(kEmitWg), 0, stream, grid, nx, ny, cx, cy, level,
                        (const uint2*)(ws + lay.off_act), (const uint4*)(ws + lay.off_blk),
-                       (const uint2*)(ws + lay.off_blkoff), nz, (uint32_t)lay.nnz, (int32_t*)(ws + lay.off_etab), verts, xf, xf9 ? 1 : 0);
+                       (const uint2*)(ws + lay.off_blkoff), nz, (uint32_t)lay.nnz, (int32_t*)(ws + lay.off_table), verts, xf, xf9 ? 1 : 0);
     hipLaunchKernelGGL(mc_faces, dim3(wgs), dim3(kEmitWg), 0, stream, nx, ny, cx, cy,
                        (const uint2*)(ws + lay.off_act), (const uint4*)(ws + lay.off_blk),
-                       (const uint2*)(ws + lay.off_blkoff), nz, (uint32_t)lay.nnz, (const int32_t*)(ws + lay.off_etab), faces, reversed);
+                       (const uint2*)(ws + lay.off_blkoff), nz, (uint32_t)lay.nnz, (const int32_t*)(ws + lay.off_table), faces, reversed);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include "r3g_ctx.h"
 #include "mesh_kernels.h"
 #include "meshfit_core.h"
+#include "surf_common.h"
 #include "tex_kernels.h"
 
 namespace r3g {
@@ -186,6 +187,74 @@ static int grid_csr_build(Ctx* c, GridCsrState<U::D>* st, const U& user, const f
     if (skipped_out) *skipped_out = (int64_t)sm.skipped;
     return R3G_OK;
 }
+
+// ---- surface extractors: marching cubes and dual marching cubes (one count and one emit driver) -----------------------------
+// what the drivers need to know of their extractor
+struct McExtract {
+    static constexpr const char* who = "mc";
+    static constexpr uint64_t ids_per_node = 3;      // a vertex lives on one of a node's three edges: ids stay inside int32
+    static constexpr int faces_per_item = 1;         // totals[1] counts triangles
+    static bool no_surface(unsigned long long nv, unsigned long long) { return nv == 0; }
+    static constexpr auto workspace_bytes = mc_workspace_bytes;
+    static constexpr auto count_launch = mc_count_launch;
+    static constexpr auto emit_launch = mc_emit_launch;
+};
+
+struct DmcExtract {
+    static constexpr const char* who = "dmc";
+    static constexpr uint64_t ids_per_node = 6;      // at most 4 vertices and 6 triangles per cell: ids and triangle counts stay inside int32
+    static constexpr int faces_per_item = 2;         // totals[1] counts quads
+    static bool no_surface(unsigned long long, unsigned long long nq) { return nq == 0; }
+    static constexpr auto workspace_bytes = dmc_workspace_bytes;
+    static constexpr auto count_launch = dmc_count_launch;
+    static constexpr auto emit_launch = dmc_emit_launch;
+};
+
+// validate, reserve, classify + scan, 64 B read-back, status / level-range / no-surface decode, state capture
+template <class U>
+static int surf_count(Ctx* c, SurfState* st, const float* d_grid, int n0, int n1, int n2, double level, int flag,
+                      int64_t* n_verts, int64_t* n_faces, hipStream_t s) {
+    const char* who = U::who;
+    if (n0 < 2 || n1 < 2 || n2 < 2) return fail(R3G_ERR_INVALID, "Input array must be at least 2x2x2.");
+    const uint64_t nnodes = (uint64_t)n0 * n1 * n2;
+    if (nnodes * U::ids_per_node >= (1ull << 31)) return fail(R3G_ERR_INVALID, "r3g_%s_count: grid too large for int32 vertex ids", who);
+    st->counted = false;
+    SurfWorkspaceLayout lay;
+    const size_t need = U::workspace_bytes(n0, n1, n2, &lay);
+    int rc = c->reserve(&st->ws, &st->ws_bytes, need, Named("hipMalloc(%s workspace)", who));
+    if (rc) return rc;
+    hipError_t e = U::count_launch(d_grid, n0, n1, n2, level, flag, st->ws, lay, s);
+    if (e != hipSuccess) return hip_fail(e, Named("%s_count_launch", who));
+    e = hipMemcpyAsync(c->h_small, st->ws + lay.off_small, 64, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, Named("hipMemcpyAsync(%s totals)", who));
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, Named("hipStreamSynchronize(%s count)", who));
+    const unsigned status = *(const unsigned*)c->h_small;
+    const unsigned long long* totals = (const unsigned long long*)c->h_small + 2;      // {vertices, triangles or quads, non-empty blocks} @16
+    *n_verts = (int64_t)totals[0];
+    *n_faces = (int64_t)(U::faces_per_item * totals[1]);
+    // numpy: level < vol.min() or level > vol.max(); a NaN anywhere makes both comparisons false
+    if (!(status & R3G_SURF_FLAG_NAN) && (!(status & R3G_SURF_FLAG_LE) || !(status & R3G_SURF_FLAG_GE)))
+        return fail(R3G_ERR_LEVEL_RANGE, "Surface level must be within volume data range.");
+    if (U::no_surface(totals[0], totals[1])) return fail(R3G_ERR_NO_SURFACE, "No surface found at the given iso value.");
+    st->lay = lay;
+    st->lay.nnz = (uint32_t)totals[2];
+    st->grid = d_grid;
+    st->n[0] = n0; st->n[1] = n1; st->n[2] = n2;
+    st->level = level;
+    st->counted = true;
+    return R3G_OK;
+}
+
+template <class U>
+static int surf_emit(SurfState* st, float* d_verts, int32_t* d_faces, const double* xform, int reverse_faces, hipStream_t s) {
+    const char* who = U::who;
+    if (!st->counted) return fail(R3G_ERR_STATE, "r3g_%s_emit: no successful r3g_%s_count precedes this call", who, who);
+    hipError_t e = U::emit_launch(st->grid, st->n[0], st->n[1], st->n[2], st->level, st->ws, st->lay, d_verts, d_faces, xform,
+                                  reverse_faces, s);
+    if (e != hipSuccess) return hip_fail(e, Named("%s_emit_launch", who));
+    return R3G_OK;
+}
 }  // namespace r3g
 
 using namespace r3g;
@@ -230,8 +299,8 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (!ctx) return;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     (void)hipSetDevice(c->device);
-    if (c->mc_ws) (void)hipFree(c->mc_ws);
-    if (c->dmc_ws) (void)hipFree(c->dmc_ws);
+    if (c->mc.ws) (void)hipFree(c->mc.ws);
+    if (c->dmc.ws) (void)hipFree(c->dmc.ws);
     if (c->mesh_ws) (void)hipFree(c->mesh_ws);
     if (c->meshdist.ws) (void)hipFree(c->meshdist.ws);
     if (c->meshdist.pairs) (void)hipFree(c->meshdist.pairs);
@@ -252,98 +321,28 @@ void r3g_destroy(r3g_ctx* ctx) {
 int r3g_mc_count(r3g_ctx* ctx, const float* d_grid, int n0, int n1, int n2, double level, int use_classic,
                  int64_t* n_verts, int64_t* n_faces, void* stream) {
     if (!ctx || !d_grid || !n_verts || !n_faces) return fail(R3G_ERR_INVALID, "r3g_mc_count: null argument");
-    if (n0 < 2 || n1 < 2 || n2 < 2) return fail(R3G_ERR_INVALID, "Input array must be at least 2x2x2.");
-    const uint64_t nnodes = (uint64_t)n0 * n1 * n2;
-    if (nnodes * 3 >= (1ull << 31)) return fail(R3G_ERR_INVALID, "r3g_mc_count: grid too large for int32 vertex ids");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    c->mc_counted = false;
-    McWorkspaceLayout lay;
-    const size_t need = mc_workspace_bytes(n0, n1, n2, &lay);
-    int rc = c->reserve(&c->mc_ws, &c->mc_ws_bytes, need, "hipMalloc(mc workspace)");
-    if (rc) return rc;
-    hipError_t e = mc_count_launch(d_grid, n0, n1, n2, level, use_classic, c->mc_ws, lay, s);
-    if (e != hipSuccess) return hip_fail(e, "mc_count_launch");
-    e = hipMemcpyAsync(c->h_small, c->mc_ws + lay.off_small, 64, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(mc totals)");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(mc count)");
-    const unsigned status = *(const unsigned*)c->h_small;
-    const unsigned long long nv = ((const unsigned long long*)c->h_small)[2];
-    const unsigned long long nf = ((const unsigned long long*)c->h_small)[3];
-    *n_verts = (int64_t)nv;
-    *n_faces = (int64_t)nf;
-    // numpy: level < vol.min() or level > vol.max(); a NaN anywhere makes both comparisons false
-    if (!(status & 4u) && (!(status & 1u) || !(status & 2u)))
-        return fail(R3G_ERR_LEVEL_RANGE, "Surface level must be within volume data range.");
-    if (nv == 0) return fail(R3G_ERR_NO_SURFACE, "No surface found at the given iso value.");
-    c->mc_lay = lay;
-    c->mc_lay.nnz = (uint32_t)((const unsigned long long*)c->h_small)[4];
-    c->mc_grid = d_grid;
-    c->mc_n[0] = n0; c->mc_n[1] = n1; c->mc_n[2] = n2;
-    c->mc_level = level;
-    c->mc_counted = true;
-    return R3G_OK;
+    return surf_count<McExtract>(c, &c->mc, d_grid, n0, n1, n2, level, use_classic, n_verts, n_faces, (hipStream_t)stream);
 }
 
 int r3g_mc_emit(r3g_ctx* ctx, float* d_verts, int32_t* d_faces, const double* xform, int reverse_faces,
                 void* stream) {
     if (!ctx || !d_verts || !d_faces) return fail(R3G_ERR_INVALID, "r3g_mc_emit: null argument");
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c->mc_counted) return fail(R3G_ERR_STATE, "r3g_mc_emit: no successful r3g_mc_count precedes this call");
-    hipError_t e = mc_emit_launch(c->mc_grid, c->mc_n[0], c->mc_n[1], c->mc_n[2], c->mc_level, c->mc_ws, c->mc_lay,
-                                  d_verts, d_faces, xform, reverse_faces, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "mc_emit_launch");
-    return R3G_OK;
+    return surf_emit<McExtract>(&reinterpret_cast<Ctx*>(ctx)->mc, d_verts, d_faces, xform, reverse_faces, (hipStream_t)stream);
 }
 
 // ---- dual marching cubes ----------------------------------------------------------------
 int r3g_dmc_count(r3g_ctx* ctx, const float* d_grid, int n0, int n1, int n2, double level, int manifold,
                   int64_t* n_verts, int64_t* n_faces, void* stream) {
     if (!ctx || !d_grid || !n_verts || !n_faces) return fail(R3G_ERR_INVALID, "r3g_dmc_count: null argument");
-    if (n0 < 2 || n1 < 2 || n2 < 2) return fail(R3G_ERR_INVALID, "Input array must be at least 2x2x2.");
-    const uint64_t nnodes = (uint64_t)n0 * n1 * n2;
-    // at most 4 vertices and 6 triangles per cell: ids and triangle counts stay inside int32
-    if (nnodes * 6 >= (1ull << 31)) return fail(R3G_ERR_INVALID, "r3g_dmc_count: grid too large for int32 vertex ids");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    c->dmc_counted = false;
-    DmcWorkspaceLayout lay;
-    const size_t need = dmc_workspace_bytes(n0, n1, n2, &lay);
-    int rc = c->reserve(&c->dmc_ws, &c->dmc_ws_bytes, need, "hipMalloc(dmc workspace)");
-    if (rc) return rc;
-    hipError_t e = dmc_count_launch(d_grid, n0, n1, n2, level, manifold, c->dmc_ws, lay, s);
-    if (e != hipSuccess) return hip_fail(e, "dmc_count_launch");
-    e = hipMemcpyAsync(c->h_small, c->dmc_ws + lay.off_small, 64, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(dmc totals)");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(dmc count)");
-    const unsigned status = *(const unsigned*)c->h_small;
-    const unsigned long long nv = ((const unsigned long long*)c->h_small)[2];
-    const unsigned long long nq = ((const unsigned long long*)c->h_small)[3];
-    *n_verts = (int64_t)nv;
-    *n_faces = (int64_t)(2 * nq);
-    if (!(status & 4u) && (!(status & 1u) || !(status & 2u)))
-        return fail(R3G_ERR_LEVEL_RANGE, "Surface level must be within volume data range.");
-    if (nq == 0) return fail(R3G_ERR_NO_SURFACE, "No surface found at the given iso value.");
-    c->dmc_lay = lay;
-    c->dmc_lay.nnz = (uint32_t)((const unsigned long long*)c->h_small)[4];
-    c->dmc_grid = d_grid;
-    c->dmc_n[0] = n0; c->dmc_n[1] = n1; c->dmc_n[2] = n2;
-    c->dmc_level = level;
-    c->dmc_counted = true;
-    return R3G_OK;
+    return surf_count<DmcExtract>(c, &c->dmc, d_grid, n0, n1, n2, level, manifold, n_verts, n_faces, (hipStream_t)stream);
 }
 
 int r3g_dmc_emit(r3g_ctx* ctx, float* d_verts, int32_t* d_faces, const double* xform, int reverse_faces,
                  void* stream) {
     if (!ctx || !d_verts || !d_faces) return fail(R3G_ERR_INVALID, "r3g_dmc_emit: null argument");
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c->dmc_counted) return fail(R3G_ERR_STATE, "r3g_dmc_emit: no successful r3g_dmc_count precedes this call");
-    hipError_t e = dmc_emit_launch(c->dmc_grid, c->dmc_n[0], c->dmc_n[1], c->dmc_n[2], c->dmc_level, c->dmc_ws, c->dmc_lay,
-                                   d_verts, d_faces, xform, reverse_faces, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "dmc_emit_launch");
-    return R3G_OK;
+    return surf_emit<DmcExtract>(&reinterpret_cast<Ctx*>(ctx)->dmc, d_verts, d_faces, xform, reverse_faces, (hipStream_t)stream);
 }
 
 // ---- hierarchical volume decoder: the planner steps on their own ----------------------------------------------

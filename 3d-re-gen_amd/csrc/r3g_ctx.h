@@ -23,22 +23,8 @@ struct Ctx {
     int device = 0;
     int num_cu = 0;
     char* h_small = nullptr;  // pinned, 64 B: read-back of tiny device results
-    // marching cubes
-    char* mc_ws = nullptr;
-    size_t mc_ws_bytes = 0;
-    McWorkspaceLayout mc_lay{};
-    const float* mc_grid = nullptr;
-    int mc_n[3] = {0, 0, 0};
-    double mc_level = 0.0;
-    bool mc_counted = false;
-    // dual marching cubes
-    char* dmc_ws = nullptr;
-    size_t dmc_ws_bytes = 0;
-    DmcWorkspaceLayout dmc_lay{};
-    const float* dmc_grid = nullptr;
-    int dmc_n[3] = {0, 0, 0};
-    double dmc_level = 0.0;
-    bool dmc_counted = false;
+    // marching cubes and dual marching cubes (SurfState: surf_compact_kernels.h): a caller may hold a counted state of each at once
+    SurfState mc, dmc;
     // mesh cleaners
     char* mesh_ws = nullptr;
     size_t mesh_ws_bytes = 0;

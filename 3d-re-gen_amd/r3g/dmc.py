@@ -6,41 +6,13 @@ Wodniok dual marching cubes with the manifold rule; not pinned to upstream's `di
     verts, faces = extract_mesh(grid, mc_level, R)             # the frame of upstream's DMCSurfaceExtractor
 Inputs and outputs are torch CUDA tensors; the grid never leaves HBM.
 """
-import ctypes
-
 import numpy as np
-import torch
 
-from . import ffi as _l
-
-
-def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .mc import _extract
 
 
 def _run(grid, level, manifold, xform, reverse, ctx=None):
-    if not isinstance(grid, torch.Tensor) or grid.ndim != 3:
-        raise ValueError("Input volume should be a 3D torch tensor.")
-    if not grid.is_cuda:
-        raise ValueError("r3g.dmc needs a CUDA(HIP) tensor: the product has no CPU path")
-    if min(grid.shape) < 2:
-        raise ValueError("Input array must be at least 2x2x2.")
-    grid = grid.contiguous().float()
-    dev = grid.device.index or 0
-    with torch.cuda.device(dev):
-        ctx = ctx if ctx is not None else _l.context(dev)
-        L = _l.lib()
-        nv, nf = ctypes.c_int64(), ctypes.c_int64()
-        _l.check(L.r3g_dmc_count(ctx, grid.data_ptr(), grid.shape[0], grid.shape[1], grid.shape[2], float(level),
-                                 int(bool(manifold)), ctypes.byref(nv), ctypes.byref(nf), _stream_ptr()))
-        verts = torch.empty((nv.value, 3), dtype=torch.float32, device=grid.device)
-        faces = torch.empty((nf.value, 3), dtype=torch.int32, device=grid.device)
-        xf = None
-        if xform is not None:
-            xf = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64).reshape(3) for a in xform]))
-        _l.check(L.r3g_dmc_emit(ctx, verts.data_ptr(), faces.data_ptr(), xf.ctypes.data if xf is not None else None,
-                                int(bool(reverse)), _stream_ptr()))
-    return verts, faces
+    return _extract("r3g_dmc_count", "r3g_dmc_emit", "dmc", grid, level, manifold, xform, reverse, ctx)
 
 
 def dual_marching_cubes(grid, level, manifold=True):

@@ -172,6 +172,12 @@ def check(rc):
     raise R3GError(rc, msg)
 
 
+def stream_ptr():
+    """torch's current stream, as the `void* stream` argument of the C ABI"""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 def option(name):
     """r3g_get_option: the current value of a process-wide switch, as r3g_set_option would take it back"""
     v = ctypes.c_int(0)

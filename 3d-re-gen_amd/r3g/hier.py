@@ -28,10 +28,6 @@ def levels(R, min_resolution=DEFAULT_MIN_RESOLUTION):
     return out[::-1]
 
 
-def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _ctx(t, ctx):
     return ctx if ctx is not None else _l.context(t.device.index or 0)
 
@@ -51,7 +47,7 @@ def select(coarse, level, band=DEFAULT_BAND, is_finest=True, ctx=None):
     n = ctypes.c_int64()
     with torch.cuda.device(coarse.device):
         _l.check(_l.lib().r3g_hier_select(_ctx(coarse, ctx), coarse.data_ptr(), coarse.shape[0], float(level), float(band),
-                                          int(bool(is_finest)), ctypes.byref(n), _stream_ptr()))
+                                          int(bool(is_finest)), ctypes.byref(n), _l.stream_ptr()))
     return int(n.value)
 
 
@@ -61,7 +57,7 @@ def indices(count, device, ctx=None):
     idx = torch.empty((int(count),), dtype=torch.int32, device=device)
     with torch.cuda.device(device):
         _l.check(_l.lib().r3g_hier_indices(ctx if ctx is not None else _l.context(device.index or 0),
-                                           idx.data_ptr() if count else None, _stream_ptr()))
+                                           idx.data_ptr() if count else None, _l.stream_ptr()))
     return idx
 
 
@@ -73,7 +69,7 @@ def merge(coarse, values, ctx=None):
     fine = torch.empty((n, n, n), dtype=torch.float32, device=coarse.device)
     with torch.cuda.device(coarse.device):
         _l.check(_l.lib().r3g_hier_merge(_ctx(coarse, ctx), coarse.data_ptr(), values.data_ptr() if values.numel() else None,
-                                         fine.data_ptr(), _stream_ptr()))
+                                         fine.data_ptr(), _l.stream_ptr()))
     return fine
 
 

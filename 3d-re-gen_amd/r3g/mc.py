@@ -14,33 +14,35 @@ import torch
 from . import ffi as _l
 
 
-def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _run(grid, level, classic, xform, reverse, ctx=None):
+def _extract(count, emit, who, grid, level, flag, xform, reverse, ctx):
+    """count, allocate, emit: the two C calls of a surface extractor, given by name (looked up once the input is accepted).
+    flag is the extractor's own switch; xform = (grid_size[3], bbox_size[3], bbox_min[3]) or None (index space)."""
     if not isinstance(grid, torch.Tensor) or grid.ndim != 3:
         raise ValueError("Input volume should be a 3D torch tensor.")
     if not grid.is_cuda:
-        raise ValueError("r3g.mc needs a CUDA(HIP) tensor: the product has no CPU path")
+        raise ValueError("r3g.%s needs a CUDA(HIP) tensor: the product has no CPU path" % who)
     if min(grid.shape) < 2:
         raise ValueError("Input array must be at least 2x2x2.")
     grid = grid.contiguous().float()
     dev = grid.device.index or 0
     with torch.cuda.device(dev):
         ctx = ctx if ctx is not None else _l.context(dev)
-        L = _l.lib()
+        lib_count, lib_emit = getattr(_l.lib(), count), getattr(_l.lib(), emit)
         nv, nf = ctypes.c_int64(), ctypes.c_int64()
-        _l.check(L.r3g_mc_count(ctx, grid.data_ptr(), grid.shape[0], grid.shape[1], grid.shape[2], float(level),
-                                int(bool(classic)), ctypes.byref(nv), ctypes.byref(nf), _stream_ptr()))
+        _l.check(lib_count(ctx, grid.data_ptr(), grid.shape[0], grid.shape[1], grid.shape[2], float(level),
+                           int(bool(flag)), ctypes.byref(nv), ctypes.byref(nf), _l.stream_ptr()))
         verts = torch.empty((nv.value, 3), dtype=torch.float32, device=grid.device)
         faces = torch.empty((nf.value, 3), dtype=torch.int32, device=grid.device)
         xf = None
         if xform is not None:
             xf = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64).reshape(3) for a in xform]))
-        _l.check(L.r3g_mc_emit(ctx, verts.data_ptr(), faces.data_ptr(), xf.ctypes.data if xf is not None else None,
-                               int(bool(reverse)), _stream_ptr()))
+        _l.check(lib_emit(ctx, verts.data_ptr(), faces.data_ptr(), xf.ctypes.data if xf is not None else None,
+                          int(bool(reverse)), _l.stream_ptr()))
     return verts, faces
+
+
+def _run(grid, level, classic, xform, reverse, ctx=None):
+    return _extract("r3g_mc_count", "r3g_mc_emit", "mc", grid, level, classic, xform, reverse, ctx)
 
 
 def marching_cubes(grid, level, use_classic=False):

@@ -23,10 +23,6 @@ _G = 1.32471795724474602596          # the plastic number: R2 low-discrepancy se
 _A1, _A2 = 1.0 / _G, 1.0 / (_G * _G)
 
 
-def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _mesh_args(verts, faces):
     if not (torch.is_tensor(verts) and torch.is_tensor(faces) and verts.is_cuda and faces.is_cuda):
         raise ValueError("mesh buffers must live on the GPU (there is no CPU path)")
@@ -48,7 +44,7 @@ def build(verts, faces, resolution=None):
     with ffi.device_lock(dev), torch.cuda.device(v.device):
         ffi.check(ffi.lib().r3g_meshdist_build(ffi.context(dev), ctypes.c_void_p(v.data_ptr()), v.shape[0],
                                                ctypes.c_void_p(f.data_ptr()), f.shape[0], int(resolution or 0), ctypes.byref(res),
-                                               ctypes.byref(pairs), ctypes.byref(skipped), _stream_ptr()))
+                                               ctypes.byref(pairs), ctypes.byref(skipped), ffi.stream_ptr()))
     return {"resolution": res.value, "pairs": pairs.value, "skipped": skipped.value}
 
 
@@ -64,7 +60,7 @@ def query(points):
     face = torch.empty(p.shape[0], dtype=torch.int32, device=p.device)
     with ffi.device_lock(dev), torch.cuda.device(p.device):
         ffi.check(ffi.lib().r3g_meshdist_query(ffi.context(dev), ctypes.c_void_p(p.data_ptr()), p.shape[0],
-                                               ctypes.c_void_p(d2.data_ptr()), ctypes.c_void_p(face.data_ptr()), _stream_ptr()))
+                                               ctypes.c_void_p(d2.data_ptr()), ctypes.c_void_p(face.data_ptr()), ffi.stream_ptr()))
     return d2, face
 
 
@@ -97,7 +93,7 @@ def closest(points):
     with ffi.device_lock(dev), torch.cuda.device(p.device):
         ffi.check(ffi.lib().r3g_meshdist_closest(ffi.context(dev), ctypes.c_void_p(p.data_ptr()), p.shape[0],
                                                  ctypes.c_void_p(d2.data_ptr()), ctypes.c_void_p(face.data_ptr()),
-                                                 ctypes.c_void_p(q.data_ptr()), _stream_ptr()))
+                                                 ctypes.c_void_p(q.data_ptr()), ffi.stream_ptr()))
     return d2, face, q
 
 

@@ -66,7 +66,7 @@ def step(points, xform=None, weights=None, method="plane", max_dist=None):
     with ffi.device_lock(dev), torch.cuda.device(p.device):
         ffi.check(ffi.lib().r3g_meshfit_step(ffi.context(dev), _ptr(p), p.shape[0], _ptr(w), x.ctypes.data, METHODS[method],
                                              _max_dist(max_dist), sums.ctypes.data, ctypes.byref(used),
-                                             meshdist._stream_ptr()))
+                                             ffi.stream_ptr()))
     return sums[:18 if method == "point" else 37], used.value
 
 
@@ -87,7 +87,7 @@ def fit(points, weights=None, init=None, method="plane", with_scale=False, max_i
     with ffi.device_lock(dev), torch.cuda.device(p.device):
         ffi.check(ffi.lib().r3g_meshfit(ffi.context(dev), _ptr(p), p.shape[0], _ptr(w), None if m0 is None else m0.ctypes.data,
                                         METHODS[method], int(bool(with_scale)), int(max_iterations), float(tolerance),
-                                        _max_dist(max_dist), m.ctypes.data, info.ctypes.data, meshdist._stream_ptr()))
+                                        _max_dist(max_dist), m.ctypes.data, info.ctypes.data, ffi.stream_ptr()))
     return m.reshape(4, 4), {"iterations": int(info[0]), "converged": bool(info[1]), "rms": float(info[2]), "used": int(info[3]),
                              "scale": float(info[4])}
 

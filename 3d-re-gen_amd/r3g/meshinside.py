@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import ffi, meshdist
-from .meshdist import _mesh_args, _stream_ptr
+from .meshdist import _mesh_args
 
 _CHUNK = 1 << 22          # lattice points per query of volume_iou
 
@@ -43,7 +43,7 @@ def build(verts, faces, axis=2, resolution=None):
     with ffi.device_lock(dev), torch.cuda.device(v.device):
         ffi.check(ffi.lib().r3g_meshinside_build(ffi.context(dev), ctypes.c_void_p(v.data_ptr()), v.shape[0],
                                                  ctypes.c_void_p(f.data_ptr()), f.shape[0], int(axis), int(resolution or 0),
-                                                 ctypes.byref(res), ctypes.byref(pairs), ctypes.byref(skipped), _stream_ptr()))
+                                                 ctypes.byref(res), ctypes.byref(pairs), ctypes.byref(skipped), ffi.stream_ptr()))
     return {"resolution": res.value, "pairs": pairs.value, "skipped": skipped.value}
 
 
@@ -54,7 +54,7 @@ def query(points):
     count = torch.empty(p.shape[0], dtype=torch.int32, device=p.device)
     with ffi.device_lock(dev), torch.cuda.device(p.device):
         ffi.check(ffi.lib().r3g_meshinside_query(ffi.context(dev), ctypes.c_void_p(p.data_ptr()), p.shape[0],
-                                                 ctypes.c_void_p(count.data_ptr()), _stream_ptr()))
+                                                 ctypes.c_void_p(count.data_ptr()), ffi.stream_ptr()))
     return count
 
 

@@ -8,10 +8,6 @@ import torch
 from . import ffi
 
 
-def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _prepare(verts, faces):
     if not (verts.is_cuda and faces.is_cuda):
         raise ValueError("mesh buffers must live on the GPU (there is no CPU path)")
@@ -30,7 +26,7 @@ def _run(fn, verts, faces, *extra):
     with ffi.device_lock(dev), torch.cuda.device(v.device):
         ctx = ffi.context(dev)
         ffi.check(fn(ctx, ctypes.c_void_p(v.data_ptr()), ctypes.byref(nv), ctypes.c_void_p(f.data_ptr()),
-                     ctypes.byref(nf), *extra, _stream_ptr()))
+                     ctypes.byref(nf), *extra, ffi.stream_ptr()))
     return v[:nv.value], f[:nf.value]
 
 

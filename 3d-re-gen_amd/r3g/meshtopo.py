@@ -14,7 +14,7 @@ import ctypes
 import torch
 
 from . import ffi
-from .meshdist import _mesh_args, _stream_ptr
+from .meshdist import _mesh_args
 
 REPORT_FIELDS = ("usable", "skipped", "vref", "edges", "boundary", "clash", "nonmanifold", "bodies", "unorientable", "euler",
                  "nonfinite", "six_volume_q", "vol_scale", "two_area_q", "area_scale", "has_verts")
@@ -56,7 +56,7 @@ def build(verts, faces, n_verts=None):
     dev = f.device.index or 0
     raw = (ctypes.c_int64 * 16)()
     with ffi.device_lock(dev), torch.cuda.device(f.device):
-        ffi.check(ffi.lib().r3g_meshtopo_build(ffi.context(dev), vp, nv, ctypes.c_void_p(f.data_ptr()), f.shape[0], raw, _stream_ptr()))
+        ffi.check(ffi.lib().r3g_meshtopo_build(ffi.context(dev), vp, nv, ctypes.c_void_p(f.data_ptr()), f.shape[0], raw, ffi.stream_ptr()))
     return _report(raw)
 
 
@@ -79,7 +79,7 @@ def mates(device=0):
     -3 half-edge of a skipped face"""
     with ffi.device_lock(device), torch.cuda.device(device):
         out = torch.empty((_n_faces(device), 3), dtype=torch.int32, device=torch.device("cuda", device))
-        ffi.check(ffi.lib().r3g_meshtopo_mates(ffi.context(device), ctypes.c_void_p(out.data_ptr()), _stream_ptr()))
+        ffi.check(ffi.lib().r3g_meshtopo_mates(ffi.context(device), ctypes.c_void_p(out.data_ptr()), ffi.stream_ptr()))
     return out
 
 
@@ -91,7 +91,7 @@ def bodies(device=0):
         body = torch.empty(n, dtype=torch.int32, device=torch.device("cuda", device))
         flip = torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", device))
         ffi.check(ffi.lib().r3g_meshtopo_bodies(ffi.context(device), ctypes.c_void_p(body.data_ptr()),
-                                                ctypes.c_void_p(flip.data_ptr()), _stream_ptr()))
+                                                ctypes.c_void_p(flip.data_ptr()), ffi.stream_ptr()))
     return body, flip
 
 
@@ -133,7 +133,7 @@ def _orient(verts, faces, outward, n_verts=None):
     nfr, nbr = ctypes.c_int64(0), ctypes.c_int64(0)
     with ffi.device_lock(dev), torch.cuda.device(f.device):
         ffi.check(ffi.lib().r3g_meshtopo_orient(ffi.context(dev), vp, nv, ctypes.c_void_p(f.data_ptr()), f.shape[0], int(outward),
-                                                ctypes.byref(nfr), ctypes.byref(nbr), _stream_ptr()))
+                                                ctypes.byref(nfr), ctypes.byref(nbr), ffi.stream_ptr()))
         rep = report(dev)
     return f, {"faces_reversed": nfr.value, "bodies_reversed": nbr.value, "report": rep}
 

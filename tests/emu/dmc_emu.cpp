@@ -56,10 +56,7 @@ extern "C" int r3g_emu_dmc(const float* grid, int n0, int n1, int n2, double lev
     CellRef poison;
     poison.vbase = 0xFFFFFFFFu; poison.ecase = 0;      // only to catch bugs: the GPU table is uninitialised
     std::vector<CellRef> ctab((size_t)ncells, poison);
-    Xform xf;
-    for (int a = 0; a < 3; ++a) {
-        xf.grid_size[a] = xf9 ? xf9[a] : 1.0; xf.bbox_size[a] = xf9 ? xf9[3 + a] : 1.0; xf.bbox_min[a] = xf9 ? xf9[6 + a] : 0.0;
-    }
+    const Xform xf = r3g_surf::xform_from(xf9);
     // pass 3: vertices
     for (int64_t b = 0; b < nblk; ++b)
         for (uint32_t a = 0; a < blkA[b]; ++a) {

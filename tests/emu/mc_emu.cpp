@@ -69,8 +69,7 @@ extern "C" int r3g_emu_mc(const float* grid, int n0, int n1, int n2, double leve
     float* verts = (float*)malloc(sizeof(float) * 3 * (tv ? tv : 1));
     int32_t* faces = (int32_t*)malloc(sizeof(int32_t) * 3 * (tt ? tt : 1));
     std::vector<int32_t> etab((size_t)3 * nx * ny * nz, -1);  // -1 only to catch bugs; the GPU table is uninitialised
-    Xform xf;
-    if (xf9) for (int i = 0; i < 3; ++i) { xf.grid_size[i] = xf9[i]; xf.bbox_size[i] = xf9[3 + i]; xf.bbox_min[i] = xf9[6 + i]; }
+    const Xform xf = r3g_surf::xform_from(xf9);
     // pass 3: vertices
     for (int64_t b = 0; b < nblk; ++b)
         for (uint32_t a = 0; a < blkA[b]; ++a) {

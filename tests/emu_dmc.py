@@ -15,7 +15,7 @@ def _lib():
     global _LIB
     if _LIB is None:
         so = os.path.join(_HERE, "libr3g_dmc_emu.so")
-        deps = [os.path.join(_HERE, "dmc_emu.cpp"), os.path.join(_CSRC, "dmc_cell.h"), os.path.join(_CSRC, "dmc_luts.h")]
+        deps = [os.path.join(_HERE, "dmc_emu.cpp")] + [os.path.join(_CSRC, h) for h in ("dmc_cell.h", "dmc_luts.h", "surf_common.h")]
         if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in deps):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
                                    "-I" + _CSRC, "-o", so, deps[0]])

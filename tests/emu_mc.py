@@ -14,11 +14,11 @@ def _lib():
     global _LIB
     if _LIB is None:
         so = os.path.join(_HERE, "libr3g_emu.so")
-        src = os.path.join(_HERE, "mc_emu.cpp")
-        hdr = os.path.join(_ROOT, "3d-re-gen_amd", "csrc", "mc_cell.h")
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+        csrc = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
+        deps = [os.path.join(_HERE, "mc_emu.cpp")] + [os.path.join(csrc, h) for h in ("mc_cell.h", "mc_luts.h", "surf_common.h")]
+        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in deps):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
-                                   "-I" + os.path.join(_ROOT, "3d-re-gen_amd", "csrc"), "-o", so, src])
+                                   "-I" + csrc, "-o", so, deps[0]])
         lib = ctypes.CDLL(so)
         lib.r3g_emu_mc.restype = ctypes.c_int
         lib.r3g_emu_mc.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,

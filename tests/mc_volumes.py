@@ -95,3 +95,43 @@ def cube_zoo(per_index=16, n_int=2500, n13=1500, seed=99):
     a = np.stack(cubes)
     b = rng.integers(-3, 4, (n_int, 2, 2, 2))
     return np.concatenate([a, b]).astype(np.float32)
+
+
+CHUNK_BLOCKS = 1024      # blocks of 256 cells that one workgroup of the extractors' block-sum scan takes
+
+
+def active_cells(vol, level):
+    """bool [n0-1, n1-1, n2-1]: cells whose 8 corners are not all on one side of `level` (sample > level, in double);
+    flattened in C order it is the extractors' linear cell order, 256 consecutive cells to a block"""
+    g = vol.astype(np.float64) > level
+    n = sum(g[a:g.shape[0] - 1 + a, b:g.shape[1] - 1 + b, c:g.shape[2] - 1 + c].astype(np.int32)
+            for a in (0, 1) for b in (0, 1) for c in (0, 1))
+    return (n != 0) & (n != 8)
+
+
+def chunk_edge_volumes(shape, seed=77):
+    """-> (field, shifted, cells).  A smoothed-noise field whose cell count reaches or passes one scan chunk, and
+    the same field plus a constant that puts the level-0 surface through `cells`: one (i, j, k) in the last block of the
+    first chunk and, where the grid has a second chunk, one in that chunk's first block."""
+    rng = np.random.default_rng(seed)
+    field = (_smooth(rng, shape, 2) * 10).astype(np.float32)
+    cs = tuple(s - 1 for s in shape)
+    nblk = -(-(cs[0] * cs[1] * cs[2]) // 256)
+    assert nblk >= CHUNK_BLOCKS
+    f64 = field.astype(np.float64)
+    corners = np.stack([f64[a:cs[0] + a, b:cs[1] + b, c:cs[2] + c].reshape(-1)
+                        for a in (0, 1) for b in (0, 1) for c in (0, 1)])
+    lo, hi = corners.min(0), corners.max(0)               # a cell is active at level L iff lo <= L < hi
+    blocks = [CHUNK_BLOCKS - 1] + ([CHUNK_BLOCKS] if nblk > CHUNK_BLOCKS else [])
+    ids = [np.arange(b * 256, min((b + 1) * 256, lo.size)) for b in blocks]
+    if len(ids) == 1:
+        a = ids[0][np.argmax(hi[ids[0]] - lo[ids[0]])]
+        picked, level = [a], 0.5 * (lo[a] + hi[a])
+    else:
+        l2 = np.maximum(lo[ids[0]][:, None], lo[ids[1]][None, :])
+        h2 = np.minimum(hi[ids[0]][:, None], hi[ids[1]][None, :])
+        a, b = np.unravel_index(np.argmax(h2 - l2), l2.shape)
+        assert h2[a, b] > l2[a, b]
+        picked, level = [ids[0][a], ids[1][b]], 0.5 * (l2[a, b] + h2[a, b])
+    shifted = (field - np.float32(level)).astype(np.float32)
+    return field, shifted, [tuple(int(x) for x in np.unravel_index(c, cs)) for c in picked]

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import dmc_ref
-from mc_volumes import golden_volume, small_volumes
+from mc_volumes import CHUNK_BLOCKS, active_cells, chunk_edge_volumes, golden_volume, small_volumes
 from test_dmc_cpu import bits_equal, check_padded_b, check_padded_small, check_sphere, padded
 
 pytestmark = pytest.mark.gpu
@@ -101,6 +101,22 @@ def test_random_ragged_volumes_equal_the_restatement():
         assert_gpu_equals_restatement(vol, 0.0, shape)
 
 
+@pytest.mark.parametrize("shape", [(65, 65, 65), (65, 65, 66)])
+def test_scan_chunk_edge_equals_the_restatement(shape):
+    """1024 and 1040 blocks: the block-sum scan's chunk of 1024 blocks ends with the grid, and hands over to a second
+    workgroup; the surface crosses the blocks either side of the edge (as tests/test_mc_gpu.py, same volumes)"""
+    field, shifted, cells = chunk_edge_volumes(shape)
+    nblk = -(-int(np.prod([n - 1 for n in shape])) // 256)
+    act = np.flatnonzero(active_cells(shifted, 0.0).reshape(-1)) // 256
+    assert {CHUNK_BLOCKS - 1, min(CHUNK_BLOCKS, nblk - 1)} <= set(act.tolist())
+    rv, _, _ = dmc_ref.dual_marching_cubes(shifted, 0.0)
+    for c in cells:         # the restatement's mesh has a vertex inside each cell the constant was chosen for
+        lo = np.array(c, np.float32)
+        assert np.any(np.all((rv >= lo) & (rv <= lo + 1), axis=1)), c
+    assert_gpu_equals_restatement(field, 0.0, (shape, "field"))
+    assert_gpu_equals_restatement(shifted, 0.0, (shape, "shifted"))
+
+
 @pytest.mark.parametrize("name", ["A", "D"])
 def test_golden_spheres_properties(name):
     vol, level = golden_volume(name)
@@ -144,6 +160,38 @@ def test_emit_without_count_is_a_state_error_and_arguments_are_checked():
         assert np.array_equal(f.cpu().numpy(), rf[:, ::-1])
         assert L.r3g_dmc_emit(ctx, v.data_ptr(), f.data_ptr(), None, 0, None) == 0             # emit may be repeated
         assert np.array_equal(f.cpu().numpy(), rf) and bits_equal(v.cpu().numpy(), rv)
+    finally:
+        L.r3g_destroy(ctx)
+
+
+def test_counted_mc_and_dmc_states_coexist():
+    """a context holds a counted marching-cubes state and a counted dual-marching-cubes state at once: neither count
+    touches the other's workspace, grid or layout"""
+    import torch
+    from oracle import mc as omc
+    from r3g import ffi
+    vols = small_volumes()
+    X, lx = vols["smooth_12"], float(vols["level_smooth_12"])
+    Y, ly = vols["noise_ragged"], float(vols["level_noise_ragged"])
+    assert X.shape != Y.shape
+    wv, wf = omc.marching_cubes(X, lx)
+    rv, rf, _ = dmc_ref.dual_marching_cubes(Y, ly)
+    L = ffi.lib()
+    ctx = ffi.new_context(0)
+    try:
+        gx, gy = dev(X), dev(Y)
+        nv, nf, mv, mf = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        assert L.r3g_mc_count(ctx, gx.data_ptr(), *gx.shape, lx, 0, ctypes.byref(nv), ctypes.byref(nf), None) == 0
+        assert L.r3g_dmc_count(ctx, gy.data_ptr(), *gy.shape, ly, 1, ctypes.byref(mv), ctypes.byref(mf), None) == 0
+        assert (nv.value, nf.value, mv.value, mf.value) == (len(wv), len(wf), len(rv), len(rf))
+        v = torch.empty((nv.value, 3), device="cuda")
+        f = torch.empty((nf.value, 3), dtype=torch.int32, device="cuda")
+        assert L.r3g_mc_emit(ctx, v.data_ptr(), f.data_ptr(), None, 1, None) == 0      # reversed: skimage's winding
+        dv = torch.empty((mv.value, 3), device="cuda")
+        df = torch.empty((mf.value, 3), dtype=torch.int32, device="cuda")
+        assert L.r3g_dmc_emit(ctx, dv.data_ptr(), df.data_ptr(), None, 0, None) == 0
+        assert np.array_equal(f.cpu().numpy(), wf) and bits_equal(v.cpu().numpy(), wv)
+        assert np.array_equal(df.cpu().numpy(), rf) and bits_equal(dv.cpu().numpy(), rv)
     finally:
         L.r3g_destroy(ctx)
 

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from mc_volumes import cube_zoo, golden_volume, small_volumes
+from mc_volumes import CHUNK_BLOCKS, active_cells, chunk_edge_volumes, cube_zoo, golden_volume, small_volumes
 
 pytestmark = pytest.mark.gpu
 
@@ -129,6 +129,32 @@ def test_row_kernel_shapes_vs_oracle(gmc, shape):
         v, f = gmc(vol, level)
         assert np.array_equal(f, of), (shape, level)
         assert bits_equal(v, ov), (shape, level)
+
+
+@pytest.mark.parametrize("shape", [(65, 65, 65), (65, 65, 66), (9, 129, 257), (9, 130, 257)])
+def test_scan_chunk_edge_vs_oracle(gmc, shape):
+    """The edge of a scan chunk (1024 blocks of 256 cells), where the block-sum scan hands over from one workgroup to
+    the next: 1024 and 1040 blocks through the generic classify kernel, 1024 and 1032 through the row kernel.  A
+    smoothed-noise field at level 0 and the same field moved by a constant that puts the surface through the last block
+    of the first chunk and the first block of the second; against the oracle, bit for bit."""
+    from oracle import mc as omc
+    field, shifted, cells = chunk_edge_volumes(shape)
+    nblk = -(-int(np.prod([n - 1 for n in shape])) // 256)
+    assert nblk in (CHUNK_BLOCKS, CHUNK_BLOCKS + 16, CHUNK_BLOCKS + 8)
+    edge = [CHUNK_BLOCKS - 1] + ([CHUNK_BLOCKS] if nblk > CHUNK_BLOCKS else [])
+    for vol in (field, shifted):
+        ov, of = omc.marching_cubes(vol, 0.0)
+        if vol is shifted:
+            # the boundary is not empty: the blocks either side of it hold cells the surface crosses, and the oracle's mesh
+            # has a vertex inside each of the cells the constant was chosen for
+            act = np.flatnonzero(active_cells(vol, 0.0).reshape(-1)) // 256
+            assert set(edge) <= set(act.tolist())
+            for c in cells:
+                lo = np.array(c, np.float32)
+                assert np.any(np.all((ov >= lo) & (ov <= lo + 1), axis=1)), c
+        v, f = gmc(vol, 0.0)
+        assert np.array_equal(f, of), shape
+        assert bits_equal(v, ov), shape
 
 
 def test_row_kernel_range_errors(gmc):
