@@ -8,7 +8,7 @@ from r3g.mesh import Mesh as Trimesh, load_glb as load  # noqa: F401
 
 import sys as _sys
 
-if __name__ in _sys.modules:      # `import trimesh.repair`: fix_winding, fix_normals, fix_inversion, broken_faces on the GPU
+if __name__ in _sys.modules:      # `import trimesh.repair`: fill_holes, fix_winding, fix_normals, fix_inversion, broken_faces on the GPU
     from . import repair  # noqa: F401
 else:       # executed from its file under a name that is not in sys.modules: there is no package to import from
     import importlib.util as _util

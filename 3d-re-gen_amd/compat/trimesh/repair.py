@@ -1,7 +1,14 @@
 """trimesh.repair as the reference's consumers of this stage call it (pose fitting: fix_normals on every loaded GLB; the
-background mesher: fix_winding, fix_normals(multibody=True), broken_faces), on the GPU through r3g.meshtopo.  The mesh is
-changed in place, as trimesh does.  fill_holes, fix_invalid_faces and anything that adds or welds geometry are not provided."""
+background mesher: fill_holes, fix_winding, fix_normals(multibody=True), broken_faces), on the GPU through r3g.meshtopo and
+r3g.meshfill.  The mesh is changed in place, as trimesh does.  fill_holes closes simple boundary loops by a fan from the loop's
+first vertex (trimesh closes triangles and quads only and picks its own quad diagonal: the default max_loop=4 keeps to its
+reach).  fix_invalid_faces and anything that welds geometry are not provided."""
 import numpy as np
+
+
+def fill_holes(mesh, max_loop=4):
+    """close every simple boundary loop of at most max_loop edges -> is the mesh watertight afterwards"""
+    return mesh.fill_holes(max_loop=max_loop)
 
 
 def fix_winding(mesh):

@@ -310,6 +310,7 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->meshinside.pairs) (void)hipFree(c->meshinside.pairs);
     if (c->meshtopo_ws) (void)hipFree(c->meshtopo_ws);
     if (c->h_topo) (void)hipHostFree(c->h_topo);
+    if (c->meshfill_ws) (void)hipFree(c->meshfill_ws);
     if (c->tex_ws) (void)hipFree(c->tex_ws);
     if (c->hier_ws) (void)hipFree(c->hier_ws);
     if (c->h_small) (void)hipHostFree(c->h_small);
@@ -732,6 +733,81 @@ int r3g_meshtopo_orient(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, int
     }
     if (faces_reversed) *faces_reversed = (int64_t)sm.faces_reversed;
     if (bodies_reversed) *bodies_reversed = (int64_t)sm.bodies_reversed;
+    return R3G_OK;
+}
+
+// ---- mesh fill ----------------------------------------------------------------------------------------------------
+int r3g_meshfill_plan(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces, int64_t max_loop,
+                      int mode, int64_t* report, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshfill_plan: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    c->meshfill_planned = false;
+    c->meshtopo_built = false;
+    int rc = meshtopo_args("r3g_meshfill_plan", d_verts, n_verts, d_faces, n_faces);
+    if (rc) return rc;
+    if (max_loop < r3g_mf::kMinLoop) return fail(R3G_ERR_INVALID, "r3g_meshfill_plan: max_loop must be at least 3");
+    if (mode != r3g_mf::kModeFan && mode != r3g_mf::kModeCentroid) return fail(R3G_ERR_INVALID, "r3g_meshfill_plan: mode must be 0 (fan) or 1 (centroid)");
+    if (mode == r3g_mf::kModeCentroid && !d_verts) return fail(R3G_ERR_INVALID, "r3g_meshfill_plan: mode 1 needs the vertices");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = meshtopo_build(c, "r3g_meshfill_plan", d_verts, n_verts, d_faces, n_faces, s))) return rc;
+    const int64_t boundary = c->meshtopo_report[4];
+    const int rounds = r3g_mf::rounds_for(boundary);
+    r3g_mf::Small sm{};
+    MeshfillLayout lay{};
+    if (boundary > 0) {
+        rc = c->reserve(&c->meshfill_ws, &c->meshfill_ws_bytes, meshfill_workspace_bytes(n_verts, n_faces, boundary, &lay),
+                        "hipMalloc(meshfill workspace)");
+        if (rc) return rc;
+        hipError_t e = meshfill_plan(c->meshfill_ws, &lay, (const int32_t*)(c->meshtopo_ws + c->meshtopo_lay.off_mate), d_verts, n_verts,
+                                     d_faces, rounds, max_loop, mode, s);
+        if (e != hipSuccess) return hip_fail(e, "meshfill_plan");
+        e = hipMemcpyAsync(c->h_small, c->meshfill_ws + lay.off_small, sizeof sm, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshfill)");
+        e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshfill)");
+        memcpy(&sm, c->h_small, sizeof sm);
+    }
+    meshfill_add_counters(1, 2 * (int64_t)rounds);
+    const int64_t verts_added = mode == r3g_mf::kModeCentroid ? (int64_t)sm.filled : 0;
+    if (n_verts + verts_added >= (1ll << 31))
+        return fail(R3G_ERR_INVALID, "r3g_meshfill_plan: the added vertices do not fit an int32 index");
+    int64_t* r = c->meshfill_report;
+    memset(r, 0, sizeof c->meshfill_report);
+    r[r3g_mf::kRepBoundary] = boundary, r[r3g_mf::kRepLoops] = (int64_t)sm.loops;
+    r[r3g_mf::kRepTangled] = boundary - (int64_t)sm.loop_edges, r[r3g_mf::kRepFilled] = (int64_t)sm.filled;
+    r[r3g_mf::kRepOversize] = (int64_t)(sm.loops - sm.filled), r[r3g_mf::kRepLongest] = sm.longest;
+    r[r3g_mf::kRepLoopEdges] = (int64_t)sm.loop_edges, r[r3g_mf::kRepFacesAdded] = (int64_t)sm.faces_added;
+    r[r3g_mf::kRepVertsAdded] = verts_added, r[r3g_mf::kRepRounds] = rounds;
+    r[r3g_mf::kRepMaxLoop] = max_loop, r[r3g_mf::kRepMode] = mode, r[r3g_mf::kRepFaces] = n_faces, r[r3g_mf::kRepVerts] = n_verts;
+    c->meshfill_lay = lay;
+    c->meshfill_planned = true;
+    if (report) memcpy(report, r, sizeof c->meshfill_report);
+    return R3G_OK;
+}
+
+int r3g_meshfill_emit(r3g_ctx* ctx, int32_t* d_new_faces, float* d_new_verts, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshfill_emit: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->meshfill_planned) return fail(R3G_ERR_STATE, "r3g_meshfill_emit: no successful r3g_meshfill_plan on this context");
+    const int64_t* r = c->meshfill_report;
+    if (r[r3g_mf::kRepFacesAdded] == 0) return R3G_OK;
+    if (!d_new_faces) return fail(R3G_ERR_INVALID, "r3g_meshfill_emit: null buffer");
+    hipError_t e = meshfill_emit(c->meshfill_ws, c->meshfill_lay, r[r3g_mf::kRepVerts], r[r3g_mf::kRepMaxLoop], (int)r[r3g_mf::kRepMode],
+                                 r[r3g_mf::kRepFilled], r[r3g_mf::kRepFacesAdded], d_new_faces, d_new_verts, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "meshfill_emit");
+    return R3G_OK;
+}
+
+int r3g_meshfill_loops(r3g_ctx* ctx, int64_t* d_loop_start, int32_t* d_loop_verts, int32_t* d_loop_status, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshfill_loops: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->meshfill_planned) return fail(R3G_ERR_STATE, "r3g_meshfill_loops: no successful r3g_meshfill_plan on this context");
+    const int64_t* r = c->meshfill_report;
+    if (!d_loop_start || (r[r3g_mf::kRepLoops] && (!d_loop_verts || !d_loop_status)))
+        return fail(R3G_ERR_INVALID, "r3g_meshfill_loops: null buffer");
+    hipError_t e = meshfill_loops(c->meshfill_ws, c->meshfill_lay, r[r3g_mf::kRepMaxLoop], r[r3g_mf::kRepLoops], r[r3g_mf::kRepLoopEdges],
+                                  d_loop_start, d_loop_verts, d_loop_status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "meshfill_loops");
     return R3G_OK;
 }
 

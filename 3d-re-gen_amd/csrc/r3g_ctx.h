@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "mc_kernels.h"
 #include "meshdist_kernels.h"
+#include "meshfill_kernels.h"
 #include "meshfit_kernels.h"
 #include "meshinside_kernels.h"
 #include "meshtopo_kernels.h"
@@ -48,6 +49,13 @@ struct Ctx {
     int64_t meshtopo_nf = 0;
     int64_t meshtopo_report[16] = {0};
     bool meshtopo_built = false;
+    // mesh fill: the slots, loops and scans of the last r3g_meshfill_plan (a state of its own again; the plan also leaves the
+    // topology state above describing its input mesh)
+    char* meshfill_ws = nullptr;
+    size_t meshfill_ws_bytes = 0;
+    MeshfillLayout meshfill_lay{};
+    int64_t meshfill_report[16] = {0};
+    bool meshfill_planned = false;
     // texture stage (z-buffer / inpainting workspace)
     char* tex_ws = nullptr;
     size_t tex_ws_bytes = 0;

@@ -3,7 +3,7 @@
 `trimesh` is what the reference stage holds between shapegen, the cleaners and `mesh.export(path)`
 (src/2d_to_3d_models/run.py:84-102); it is not installed in this image, so this class provides the
 attributes that script touches: .vertices, .faces, .is_empty, .export(path), update_vertices,
-update_faces, remove_unreferenced_vertices, nondegenerate_faces, process, plus apply_transform, closest_point and register.  The GLB carries POSITION
+update_faces, remove_unreferenced_vertices, nondegenerate_faces, process, plus apply_transform, closest_point, register and fill_holes.  The GLB carries POSITION
 (float32) + uint32 indices (+ optional per-vertex COLOR_0, + optional TEXCOORD_0 with a PNG baseColorTexture), which is
 what the downstream consumer loads with load_textures=True (src/scene_reconstruction/source/pose_matching_planar.py:882-906).
 """
@@ -296,6 +296,23 @@ class Mesh:
         """trimesh.Trimesh.fix_normals: consistent winding, normals outward (r3g.meshtopo.fix_normals), in place -> self"""
         self._orient(1 if multibody else 2)
         return self
+
+    def fill_holes(self, max_loop=64, mode="fan"):
+        """trimesh.Trimesh.fill_holes: close every simple boundary loop of at most max_loop edges (r3g.meshfill.fill_holes), in
+        place -> is_watertight afterwards.  mode "centroid" adds one vertex per filled loop and is refused on a mesh that carries
+        vertex_colors or uv (no attribute is made up for a new vertex).  An empty mesh answers False without a launch."""
+        if mode == "centroid" and (self.vertex_colors is not None or getattr(self, "uv", None) is not None):
+            raise ValueError("Mesh.fill_holes: mode 'centroid' adds vertices, and this mesh carries per-vertex attributes")
+        if self.is_empty:
+            return False
+        from . import meshfill
+        v, f, info = meshfill.fill_holes(*self.device_buffers(), max_loop=max_loop, mode=mode)
+        if info["faces_added"]:
+            self._dv, self._df = v, f
+            self._f = None if self._f is None else f.cpu().numpy().astype(np.int64)
+            if info["verts_added"]:
+                self._v = None if self._v is None else v.cpu().numpy().astype(np.float64)
+        return bool(info["topology"]["watertight"])
 
     def invert(self):
         """trimesh.Trimesh.invert: reverse every face, (v0, v1, v2) -> (v2, v1, v0), in place -> self"""

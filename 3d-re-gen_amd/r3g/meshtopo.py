@@ -7,7 +7,8 @@ csrc/meshtopo_kernels.hip.  All of it is a pure function of the faces (and, for 
 atomics only, nothing depends on the order in which they land.  `fix_winding` and `fix_normals` rewrite the faces in place
 (trimesh.repair's functions of the same names); `face_adjacency` and `broken_faces` are read off the mate table.
 
-Out of scope: filling holes, welding vertices, any repair of non-manifold edges.
+Filling holes is r3g.meshfill, on this module's mate table.  Out of scope: welding vertices, any
+repair of non-manifold edges.
 """
 import ctypes
 

@@ -268,6 +268,43 @@ int r3g_meshtopo_bodies(r3g_ctx* ctx, int32_t* d_body, uint8_t* d_flip, void* st
 int r3g_meshtopo_orient(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, int32_t* d_faces, int64_t n_faces, int outward,
                         int64_t* faces_reversed, int64_t* bodies_reversed, void* stream);
 
+/* ---- mesh fill ------------------------------------------------------------------------
+ * Close the holes of a triangle mesh: chain the boundary half-edges of the mate table of section 4i into loops and append the
+ * faces that close each loop (r3g/meshfill.py; trimesh's repair.fill_holes).  Everything is a pure function of d_faces, n_verts,
+ * max_loop and mode, and for the centroids of d_verts (csrc/meshfill_core.h; tests/emu/meshfill_emu.cpp reproduces it exactly on
+ * the host): integer atomics only, and the order in which they land decides nothing.
+ *
+ * A half-edge h is a BOUNDARY half-edge iff mate[h] = -1.  nout[v] / nin[v] count the boundary half-edges with tail / head v; v is
+ * SIMPLE iff nout[v] = nin[v] = 1.  succ[h] = the boundary half-edge whose tail is head(h) if head(h) is simple, else -1.  A LOOP is
+ * a cycle of succ; a boundary half-edge on no cycle is TANGLED (pinch vertices, chains through inconsistently wound faces, edges
+ * beside a non-manifold vertex) and is never filled.  A loop's LEADER is its lowest half-edge id, rank[h] the succ steps from the
+ * leader to h, L its length (L >= 3), its vertices a_i = tail of the half-edge of rank i.  A loop with L > max_loop is OVERSIZE and
+ * left alone.  The filled loops are numbered j = 0, 1, ... by ascending leader; the faces of loop j follow those of loop j - 1:
+ *     mode 0 (fan, no new vertex):         (a_0, a_(i+1), a_i)       for i = 1 .. L - 2
+ *     mode 1 (centroid, one new vertex):   (c_j, a_(i+1)%L, a_i)     for i = 0 .. L - 1,  c_j = n_verts + j
+ *   The centroid is, per coordinate, the float64 sum of the float32 values in rank order (one rounding per addition), the float64
+ *   quotient by L, converted once to float32; non-finite inputs propagate.  Every new face carries the reverse of each boundary
+ *   half-edge it closes, so it is wound like its neighbours.  A fan diagonal may repeat an edge the mesh has elsewhere; that edge
+ *   is then non-manifold in the result (it shows in the result's topology report; it is not prevented).
+ *
+ * r3g_meshfill_plan: run r3g_meshtopo_build on the mesh (its state stays on the context and describes the input mesh), find the
+ *   loops and leave on the context what _emit and _loops need.  d_verts may be NULL in mode 0.
+ *   report (int64 [16], may be NULL): 0 boundary half-edges, 1 loops, 2 tangled half-edges, 3 filled loops, 4 oversize loops,
+ *   5 longest loop, 6 loop_edges (sum of L over all loops; [2] = [0] - [6]), 7 faces_added, 8 verts_added, 9 rounds (of each of the
+ *   two pointer doublings: ceil(log2 max([0], 2)), 0 without a boundary), 10 max_loop, 11 mode, 12 n_faces, 13 n_verts, rest 0.
+ *   n_faces == 0 or above 2^29, max_loop < 3, a mode other than 0 or 1, mode 1 without d_verts, or n_verts + verts_added beyond
+ *   int32: R3G_ERR_INVALID; a face index outside [0, n_verts): -2, as r3g_meshtopo_build.  A failed plan leaves the context
+ *   without a fill state.  Synchronises `stream` (the read-backs of the topology build and one 40-byte read-back of its own).
+ * r3g_meshfill_emit: write the appended elements only -- d_new_faces int32 [faces_added][3] and, in mode 1, d_new_verts float32
+ *   [verts_added][3] (may be NULL: not written); the caller concatenates.  Nothing to add: nothing is written, buffers may be NULL.
+ * r3g_meshfill_loops: every loop, filled or not, ascending by leader, each in rank order: d_loop_start int64 [loops + 1],
+ *   d_loop_verts int32 [loop_edges], d_loop_status int32 [loops] (0 filled, 1 oversize; the last two may be NULL without a loop).
+ * _emit and _loops without a successful plan on this context: R3G_ERR_STATE.  Both are enqueued on `stream`. */
+int r3g_meshfill_plan(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces, int64_t max_loop,
+                      int mode, int64_t* report, void* stream);
+int r3g_meshfill_emit(r3g_ctx* ctx, int32_t* d_new_faces, float* d_new_verts, void* stream);
+int r3g_meshfill_loops(r3g_ctx* ctx, int64_t* d_loop_start, int32_t* d_loop_verts, int32_t* d_loop_status, void* stream);
+
 /* ---- texture stage: native pieces ------------------------------------------------------------
  * SURVEY.md 8(f) rank 3.  Upstream's Hunyuan3DPaintPipeline (reference call site src/2d_to_3d_models/run.py:97, built at
  * :126-128) uses two native extensions, `custom_rasterizer` (CUDA) and `mesh_processor.cpp`, and bakes the generated views
@@ -767,6 +804,8 @@ int r3g_get_option(const char* name, int* value);
  * "meshfit_steps": accumulation launches of the mesh registration (r3g_meshfit_step, and each one r3g_meshfit makes) so far.
  * "meshtopo_builds": successful builds of the mesh topology (r3g_meshtopo_build, and the one or two r3g_meshtopo_orient makes) so far.
  * "meshtopo_rounds": label rounds those builds launched so far.
+ * "meshfill_plans": successful plans of the mesh fill (r3g_meshfill_plan) so far.
+ * "meshfill_rounds": pointer-doubling rounds those plans launched so far (twice the report's `rounds` each).
  * "geo_lnf_passes" / "geo_lnd_passes": geo decoder passes that took the folded ln_3 ("geo_ln3_fold") / ln_post + output_proj
  * ("geo_lnd_fused") epilogues.
  * Kernel-choice counters, one per form a launch can end in, bumped on the host where the launch is issued (tests read them to see
