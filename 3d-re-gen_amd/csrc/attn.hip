@@ -620,6 +620,12 @@ constexpr float SCORE_LIMIT = 8.f;     // a block with a score more than 8 (log2
 
 // D = A B + C with D in registers DISTINCT from C (hipcc ties vdst to srcC for the builtin and copies the 16 registers
 // of the stabiliser block first: 32 v_mov per key tile).  The s_nop covers a VALU write of an operand just before.
+// RULE FOR CALLERS: the compiler cannot see into the asm, so it covers NONE of the MFMA's hazards behind it.  The matrix pipe reads C
+// over the instruction's passes: the registers of `c` must not be written by a vector instruction while it does -- keep `c` LIVE
+// behind the call (a later read, or an empty asm use as at the end of the pipelined key loop of attn2_kernel), or the register
+// allocator may hand them out to the very next instruction.  Where `c` dies at the call, the result is wrong by timing (seen in the
+// pipelined body: profiles/mfma_edge_parity.md).  OPEN: the last key block of the other bodies (attn2_kernel's plain body, attn3_kernel,
+// attn6_kernel) lets `c` die at the call as well; no shape has shown a wrong result there.
 __device__ __forceinline__ f32x16 mfma_32x32x16_fresh(const bf16x8& a, const bf16x8& b, const f32x16& c) {
     f32x16 d;
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
@@ -778,7 +784,9 @@ __global__ __launch_bounds__(NW * 64, (PIPE || NW == 8) ? 2 : 3) void attn2_kern
                 ps0 += ps1;
             };
             expsum();
-            if (__any(!(ps0 <= PSUM_LIMIT))) {   // rare: re-stabilise before anything of this block is used
+            // rare: re-stabilise before anything of this block is used.  (rows past Lq hold stale data: they must not decide
+            // anything -- the branch is wave-uniform, and a valid query re-stabilised on their account rounds its P at another scale)
+            if (__any(q < Lq && !(ps0 <= PSUM_LIMIT))) {
                 float mx = sc_[0];
 #pragma unroll
                 for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc_[r]);
@@ -857,6 +865,12 @@ __global__ __launch_bounds__(NW * 64, (PIPE || NW == 8) ? 2 : 3) void attn2_kern
         }
         if (pad_tail) tile(std::true_type{}, std::false_type{}, ntiles - 1, slot);
         else tile(std::false_type{}, std::false_type{}, ntiles - 1, slot);
+        // The stabiliser block stays LIVE to here.  It is the C operand of mfma_32x32x16_fresh, an instruction the compiler cannot see
+        // into: behind its last use -- block 1 of the last tile, which has no next block to compute scores for -- the register
+        // allocator handed negm's registers out again at once, and a vector write two instructions behind the MFMA changed C while
+        // the matrix pipe was still reading it (a write-after-read hazard the compiler covers only for MFMAs it knows): wrong scores
+        // in whole waves, or not, by timing, for a single masked tile with 33 .. 63 keys (profiles/mfma_edge_parity.md).
+        asm volatile("" ::"v"(negm));
     } else {
     // variant bit 0 (round 6, comment at PSUM_LIMIT2): the FAST pass takes no maximum after the first key block -- a lane whose 16
     // exponentials sum past the bound (or to NaN) only sets a sticky flag -- and when a valid query of the workgroup set it, the

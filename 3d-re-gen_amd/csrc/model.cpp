@@ -1667,6 +1667,23 @@ int r3g_grid_query_hier(r3g_ctx* ctx, double bound, int octree_resolution, doubl
 // ---- single-op entry points (parity tests call the kernels through the C ABI) ---------------------------
 int r3g_op_gemm(const uint16_t* d_a, int64_t lda, const uint16_t* d_w, int64_t ldw, const float* d_bias, void* d_c,
                 int64_t ldc, const float* d_gate, int m_, int n_, int k_, int epilogue, int use_lds_dma, void* stream) {
+    // The contract of include/r3g.h, checked here and not in gemm_launch: the model's own launches meet it by construction.
+    const bool f32_out = epilogue == EPI_RESID_F32 || epilogue == EPI_F32;
+    const bool b16_out = epilogue == EPI_BF16 || epilogue == EPI_BF16_GELU_TANH || epilogue == EPI_BF16_GELU_ERF ||
+                         epilogue == EPI_RESID_BF16 || epilogue == EPI_RESID_F16;
+    if (!f32_out && !b16_out)     // 5 and 9-11 need operands this entry point cannot carry, 7 belongs to r3g_op_gemm_fp8
+        return fail(R3G_ERR_INVALID, "r3g_op_gemm: epilogue %d is not one of 0, 1, 2, 3, 4, 6, 8", epilogue);
+    if (m_ < 0 || n_ < 0 || k_ <= 0 || k_ % 64 || (n_ & 3)) return fail(R3G_ERR_INVALID, "r3g_op_gemm: needs k %% 64 == 0, n %% 4 == 0");
+    if (m_ > 0 && n_ > 0) {
+        auto misaligned = [](const void* q, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; };
+        if (!d_a || !d_w || !d_c) return fail(R3G_ERR_INVALID, "r3g_op_gemm: null operand");
+        if ((lda & 7) || (ldw & 7) || lda < k_ || ldw < k_ || misaligned(d_a, 15) || misaligned(d_w, 15))
+            return fail(R3G_ERR_INVALID, "r3g_op_gemm: a / w rows are staged 16 bytes at a time: lda, ldw %% 8 == 0, >= k, 16-byte aligned pointers");
+        if (misaligned(d_bias, 15) || misaligned(d_gate, 15)) return fail(R3G_ERR_INVALID, "r3g_op_gemm: bias / gate must be 16-byte aligned");
+        // the narrow epilogues store 4 consecutive columns at a time: 8 bytes of a 16-bit output, 16 bytes of an fp32 one
+        if ((ldc & 3) || ldc < n_ || misaligned(d_c, f32_out ? 15 : 7))
+            return fail(R3G_ERR_INVALID, "r3g_op_gemm: needs ldc %% 4 == 0, ldc >= n and c aligned to 4 elements (%d bytes)", f32_out ? 16 : 8);
+    }
     GemmArgs p{};
     p.A = d_a; p.lda = lda; p.W = d_w; p.ldw = ldw; p.bias = d_bias; p.C = d_c; p.ldc = ldc; p.gate = d_gate;
     p.M = m_; p.N = n_; p.K = k_; p.epi = epilogue;

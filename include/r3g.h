@@ -651,7 +651,15 @@ int r3g_sched_euler_ancestral_step(float* d_sample, const float* d_model_out, co
 
 /* ---- single kernels, for parity tests through the ABI ------------------------------------------ */
 /* C = epilogue(A[m][k] . W[n][k]^T + bias); epilogue: 0 bf16, 1 bf16 gelu(tanh), 2 bf16 gelu(erf),
- * 3 f32 C += gate*(..), 4 f32.  k % 64 == 0, n % 4 == 0. */
+ * 3 f32 C += gate*(..), 4 f32, 6 bf16 C = bf16(C + gate*(..)), 8 the same in fp16 (the sum formed in fp32; gate null: 1).  Any other
+ * epilogue is R3G_ERR_INVALID: 5 and 9-11 need operands this entry point cannot carry, 7 belongs to r3g_op_gemm_fp8.
+ * Shapes: m >= 0 (0: nothing is launched), k % 64 == 0, n % 4 == 0.  Operands: a and w are staged 16 bytes at a time -- lda % 8 == 0,
+ * ldw % 8 == 0, both >= k, d_a and d_w 16-byte aligned; d_bias and d_gate (either may be null) 16-byte aligned, n floats each.
+ * Output: the kernels store four consecutive columns at a time on their narrowest path, so ldc % 4 == 0, ldc >= n, and d_c aligned to
+ * four elements: 8 bytes for the 16-bit outputs (0, 1, 2, 6, 8), 16 bytes for the fp32 ones (3, 4).  With n % 8 == 0, ldc % 8 == 0 and a
+ * 16-byte aligned d_c the 16-bit outputs leave through the LDS transpose in 16-byte stores instead (same values).  Nothing outside
+ * [m) x [n) of C is written; rows past m and columns past n of a, w, bias and gate are never read.  A violation is R3G_ERR_INVALID
+ * (tests/test_gemm_edges_gpu.py runs every tile kernel at the loosest alignment this admits). */
 int r3g_op_gemm(const uint16_t* d_a, int64_t lda, const uint16_t* d_w, int64_t ldw, const float* d_bias, void* d_c,
                 int64_t ldc, const float* d_gate, int m, int n, int k, int epilogue, int use_lds_dma, void* stream);
 /* r3g_op_gemm for the fp32 epilogues (3, 4) with the caller's split-K workspace d_ws (ws_elems floats), as the texture UNets' 3 x 3
