@@ -724,6 +724,7 @@ hipError_t layernorm_launch(const LnArgs& p, hipStream_t s) {
     } else if (p.C % 256 == 0 && (p.ldx & 3) == 0 && (p.ldy & 3) == 0) {
         R3G_LN_LAUNCH(0)
     } else {
+        if (p.y8) return hipErrorInvalidValue;   // the scalar kernel has no e4m3 output
         hipLaunchKernelGGL(layernorm_small_kernel, dim3((p.rows + 3) / 4), dim3(256), 0, s, p);
     }
     return hipGetLastError();
@@ -809,7 +810,7 @@ hipError_t nonfinite_flag_launch(const float* x, int64_t n, int* flag, hipStream
 }
 
 hipError_t swiglu_launch(const uint16_t* in, int64_t ldi, uint16_t* out, int64_t ldo, int rows, int F, hipStream_t s) {
-    if (F % 8) return hipErrorInvalidValue;
+    if (F % 8 || (ldi & 7) || (ldo & 7)) return hipErrorInvalidValue;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(swiglu_kernel, dim3(blocks_for((int64_t)rows * F / 8, 256)), dim3(256), 0, s, in, ldi, out, ldo,
                        rows, F);
@@ -983,6 +984,7 @@ hipError_t lnd_finalize_launch(const float* part, int rows, int parts, float eps
 
 hipError_t ln_dot_launch(const float* x, int64_t ldx, int rows, int C, int do_ln, const float* lnw, const float* lnb,
                          float eps, const float* w, float b, float* out, hipStream_t s, int x_bf16) {
+    if (rows <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     if (x_bf16) {
         if (C % 256 || C > 2048 || (ldx & 3)) return hipErrorInvalidValue;

@@ -1792,6 +1792,160 @@ int r3g_op_geo_tail(const uint16_t* d_cat, const uint16_t* d_x0, int n, int hidd
     return R3G_OK;
 }
 
+// ---- the row kernels (LayerNorm, ln_dot, qkv_split, GroupNorm, softmax rows, GEGLU, SwiGLU), one launch each.  As in r3g_op_gemm the
+// contract of include/r3g.h is checked HERE: the model's own launches meet it by construction and the launchers check only part of it.
+static bool op_misaligned(const void* q, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; }
+
+int r3g_op_layernorm(const void* d_x, int x_format, int64_t ldx, int64_t x_batch_stride, uint16_t* d_y, int64_t ldy, int64_t y_batch_stride,
+                     uint8_t* d_y8, int64_t ldy8, float* d_y_scale, const float* d_w, const float* d_b, const float* d_scale,
+                     const float* d_shift, int64_t mod_stride, int seg2_row0, int seg2_row1, const float* d_scale2, const float* d_shift2,
+                     int rows, int c, int rows_per_batch, float eps, void* stream) {
+    const char* bad = nullptr;
+    const bool fp8 = d_y8 != nullptr;
+    const bool seg2 = seg2_row1 > seg2_row0;
+    const bool batched = rows_per_batch >= 1 && rows > rows_per_batch;
+    // the row-in-registers kernel (float4 / uint2 accesses) or, for f32 rows only, the scalar one (layernorm_launch's rule)
+    const bool vec = x_format != 0 || (c % 256 == 0 && (ldx & 3) == 0 && (fp8 || (ldy & 3) == 0));
+    if (rows < 1 || rows_per_batch < 1) bad = "rows >= 1 and rows_per_batch >= 1";
+    else if (c < 64 || c % 64 || c > 2048) bad = "c % 64 == 0, 64 <= c <= 2048";
+    else if (x_format < 0 || x_format > 2 || (x_format && c % 256)) bad = "x_format 0 | 1 | 2, the 16-bit formats with c % 256 == 0";
+    else if (!d_x || (fp8 ? (d_y != nullptr || !d_y_scale) : !d_y)) bad = "x and exactly one of y | (y8 and y_scale)";
+    else if (ldx < c || x_batch_stride < 0 || mod_stride < 0) bad = "ldx >= c, batch and modulation strides >= 0";
+    else if (seg2 && (!d_scale2 || !d_shift2)) bad = "seg2 rows need scale2 and shift2";
+    else if (fp8 && (c % 256 || !vec || ldy8 < c || (ldy8 & 3) || op_misaligned(d_y8, 3) || batched || x_batch_stride || y_batch_stride || ldy))
+        bad = "the e4m3 output indexes y8 / y_scale by the launch row: c % 256 == 0, vector rows, ldy8 % 4 == 0, ldy8 >= c, one batch "
+              "(rows_per_batch >= rows), x_batch_stride = y_batch_stride = ldy = 0";
+    else if (!fp8 && (ldy < c || y_batch_stride < 0 || (batched && y_batch_stride < (int64_t)(rows_per_batch - 1) * ldy + c)))
+        bad = "ldy >= c, and y batches that do not overlap";
+    else if (vec && ((ldx & 3) || (x_batch_stride & 3) || op_misaligned(d_x, x_format ? 7 : 15)))
+        bad = "four x elements per access: ldx % 4 == 0, x_batch_stride % 4 == 0, x aligned to four elements";
+    else if (vec && !fp8 && ((ldy & 3) || (y_batch_stride & 3) || op_misaligned(d_y, 7)))
+        bad = "four y elements per store: ldy % 4 == 0, y_batch_stride % 4 == 0, y 8-byte aligned";
+    else if (vec && ((mod_stride & 3) || op_misaligned(d_w, 15) || op_misaligned(d_b, 15) || op_misaligned(d_scale, 15) ||
+                     op_misaligned(d_shift, 15) || op_misaligned(d_scale2, 15) || op_misaligned(d_shift2, 15)))
+        bad = "w, b, scale, shift, scale2, shift2 16-byte aligned, mod_stride % 4 == 0";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_layernorm: needs %s", bad);
+    LnArgs p{};
+    p.x = static_cast<const float*>(d_x); p.ldx = ldx; p.x_bf16 = x_format; p.y = d_y; p.ldy = ldy;
+    p.y8 = d_y8; p.ldy8 = ldy8; p.y_scale = d_y_scale;
+    p.x_batch_stride = x_batch_stride; p.y_batch_stride = y_batch_stride;
+    p.w = d_w; p.b = d_b; p.scale = d_scale; p.shift = d_shift; p.mod_stride = mod_stride;
+    p.seg2_row0 = seg2_row0; p.seg2_row1 = seg2_row1; p.scale2 = d_scale2; p.shift2 = d_shift2;
+    p.rows = rows; p.C = c; p.rows_per_batch = rows_per_batch; p.eps = eps;
+    hipError_t e = layernorm_launch(p, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_layernorm");
+    return R3G_OK;
+}
+
+int r3g_op_ln_dot(const void* d_x, int x_bf16, int64_t ldx, int rows, int c, int do_ln, const float* d_lnw, const float* d_lnb, float eps,
+                  const float* d_w, float b, float* d_out, void* stream) {
+    const char* bad = nullptr;
+    const bool vec = x_bf16 != 0 || (c % 256 == 0 && (ldx & 3) == 0);      // ln_dot_launch's rule
+    if (rows < 1) bad = "rows >= 1";
+    else if (c < 64 || c % 64 || c > 2048) bad = "c % 64 == 0, 64 <= c <= 2048";
+    else if (x_bf16 < 0 || x_bf16 > 1 || (x_bf16 && c % 256)) bad = "x_bf16 0 | 1, bf16 rows with c % 256 == 0";
+    else if (!d_x || !d_w || !d_out) bad = "x, w and out";
+    else if (do_ln && d_lnw && !d_lnb) bad = "lnb wherever lnw is given (the kernels load both)";
+    else if (ldx < c) bad = "ldx >= c";
+    else if (vec && ((ldx & 3) || op_misaligned(d_x, x_bf16 ? 7 : 15) || op_misaligned(d_w, 15) ||
+                     (do_ln && d_lnw && (op_misaligned(d_lnw, 15) || op_misaligned(d_lnb, 15)))))
+        bad = "four elements per access: ldx % 4 == 0, x aligned to four elements, w / lnw / lnb 16-byte aligned";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_ln_dot: needs %s", bad);
+    hipError_t e = ln_dot_launch(static_cast<const float*>(d_x), ldx, rows, c, do_ln, d_lnw, d_lnb, eps, d_w, b, d_out, (hipStream_t)stream, x_bf16);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_ln_dot");
+    return R3G_OK;
+}
+
+int r3g_op_qkv_split(const uint16_t* d_src, int64_t ld, int64_t src_batch_stride, int q_off, int k_off, int v_off, int head_stride,
+                     uint16_t* d_q, uint16_t* d_k, uint16_t* d_vt, int lq_pad, int lk_pad, int dst_row0, int batch, int heads, int l,
+                     int norm, const float* d_qw, const float* d_qb, const float* d_kw, const float* d_kb, float eps, float q_scale,
+                     void* stream) {
+    const char* bad = nullptr;
+    const int offs[3] = {q_off, k_off, v_off};
+    const void* dst[3] = {d_q, d_k, d_vt};
+    bool any = false, cols_ok = true, pairs_ok = true;
+    for (int i = 0; i < 3; ++i) {
+        if ((offs[i] >= 0) != (dst[i] != nullptr)) pairs_ok = false;
+        if (offs[i] >= 0) {
+            any = true;
+            if (heads >= 1 && head_stride >= 0 && (int64_t)offs[i] + (int64_t)(heads - 1) * head_stride + 64 > ld) cols_ok = false;
+        }
+    }
+    if (l < 1 || batch < 1 || heads < 1 || batch > 65535 || heads > 65535) bad = "l >= 1, 1 <= batch, heads <= 65535";
+    else if (!d_src || !any || !pairs_ok) bad = "src, and for each of q, k, v either a column offset >= 0 with its destination or -1 with null";
+    else if (head_stride < 0 || src_batch_stride < 0 || !cols_ok) bad = "every head's 64 columns inside [0, ld)";
+    else if (norm < QKN_NONE || norm > QKN_LAYERNORM) bad = "norm 0 | 1 | 2";
+    else if (dst_row0 < 0 || dst_row0 % 64) bad = "dst_row0 % 64 == 0, >= 0";
+    else if (lq_pad < 0 || lk_pad < 0 || lq_pad % 128 || lk_pad % 64) bad = "lq_pad % 128 == 0, lk_pad % 64 == 0";
+    else if (d_q && (int64_t)dst_row0 + l > lq_pad) bad = "dst_row0 + l <= lq_pad";
+    else if ((d_k || d_vt) && (int64_t)dst_row0 + l > lk_pad) bad = "dst_row0 + l <= lk_pad";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_qkv_split: needs %s", bad);
+    QkvSplitArgs p{};
+    p.src = d_src; p.ld = ld; p.src_batch_stride = src_batch_stride;
+    p.q_off = q_off; p.k_off = k_off; p.v_off = v_off; p.head_stride = head_stride;
+    p.Q = d_q; p.K = d_k; p.Vt = d_vt; p.Lq_pad = lq_pad; p.Lk_pad = lk_pad; p.dst_row0 = dst_row0;
+    p.B = batch; p.H = heads; p.L = l; p.norm = norm; p.qw = d_qw; p.qb = d_qb; p.kw = d_kw; p.kb = d_kb; p.eps = eps; p.q_scale = q_scale;
+    hipError_t e = qkv_split_launch(p, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_qkv_split");
+    return R3G_OK;
+}
+
+int r3g_op_group_norm(const float* d_x, int rows, int c, int groups, const float* d_gamma, const float* d_beta, float eps, int do_silu,
+                      uint16_t* d_y, int nb, const float* d_addv, int64_t add_stride, void* stream) {
+    const char* bad = nullptr;
+    if (rows < 1 || nb < 1 || nb > 65535) bad = "rows >= 1, 1 <= nb <= 65535";
+    else if (c < 4 || c % 4 || c > 3072 || groups < 1 || groups > 256 || c % groups) bad = "c % 4 == 0, c <= 3072, 1 <= groups <= 256, c % groups == 0";
+    else if (!d_x || !d_gamma || !d_beta || !d_y) bad = "x, gamma, beta and y";
+    else if (op_misaligned(d_x, 15) || op_misaligned(d_gamma, 15) || op_misaligned(d_beta, 15) || op_misaligned(d_y, 7))
+        bad = "x, gamma, beta 16-byte aligned, y 8-byte aligned (four channels per access)";
+    else if (d_addv && (add_stride < c || (add_stride & 3) || op_misaligned(d_addv, 15))) bad = "addv 16-byte aligned, add_stride % 4 == 0, add_stride >= c";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_group_norm: needs %s", bad);
+    hipStream_t s = (hipStream_t)stream;
+    double* partial = nullptr;      // the workspace the UNet keeps per model: here per call (a test hook; synchronous)
+    R3G_TRY(hipMalloc((void**)&partial, sizeof(double) * (size_t)nb * ((size_t)group_norm_blocks(rows) * groups * 2 + groups)));
+    hipError_t e = group_norm_launch(d_x, rows, c, groups, d_gamma, d_beta, eps, do_silu, d_y, partial, s, nb, d_addv, add_stride);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    (void)hipFree(partial);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_group_norm");
+    if (e2 != hipSuccess) return hip_fail(e2, "r3g_op_group_norm");
+    return R3G_OK;
+}
+
+int r3g_op_softmax_rows(const float* d_s, int64_t lds, uint16_t* d_p, int64_t ldp, int rows, int n, float scale, void* stream) {
+    const char* bad = nullptr;
+    if (rows < 1 || n < 4 || n % 4) bad = "rows >= 1, n >= 4, n % 4 == 0";
+    else if (!d_s || !d_p) bad = "s and p";
+    else if (lds < n || ldp < n || (lds & 3) || (ldp & 3) || op_misaligned(d_s, 15) || op_misaligned(d_p, 7))
+        bad = "four elements per access: lds, ldp % 4 == 0 and >= n, s 16-byte and p 8-byte aligned";
+    else if (!(scale > 0.f) || !(scale <= 3.0e38f)) bad = "a finite scale > 0 (the kernel scales the maximum of the scores, not the scaled scores)";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_softmax_rows: needs %s", bad);
+    hipError_t e = softmax_rows_launch(d_s, lds, d_p, ldp, rows, n, scale, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_softmax_rows");
+    return R3G_OK;
+}
+
+static const char* glu_contract(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f) {
+    if (rows < 1 || f < 8 || f % 8) return "rows >= 1, f >= 8, f % 8 == 0";
+    if (!d_in || !d_out) return "in and out";
+    if (ldi < 2 * (int64_t)f || ldo < f || (ldi & 7) || (ldo & 7) || op_misaligned(d_in, 15) || op_misaligned(d_out, 15))
+        return "eight elements per access: ldi >= 2 f, ldo >= f, ldi % 8 == 0, ldo % 8 == 0, 16-byte aligned pointers";
+    return nullptr;
+}
+
+int r3g_op_geglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f, void* stream) {
+    if (const char* bad = glu_contract(d_in, ldi, d_out, ldo, rows, f)) return fail(R3G_ERR_INVALID, "r3g_op_geglu: needs %s", bad);
+    hipError_t e = geglu_launch(d_in, ldi, d_out, ldo, rows, f, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_geglu");
+    return R3G_OK;
+}
+
+int r3g_op_swiglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f, void* stream) {
+    if (const char* bad = glu_contract(d_in, ldi, d_out, ldo, rows, f)) return fail(R3G_ERR_INVALID, "r3g_op_swiglu: needs %s", bad);
+    hipError_t e = swiglu_launch(d_in, ldi, d_out, ldo, rows, f, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_swiglu");
+    return R3G_OK;
+}
+
 int r3g_kv_selection_last(r3g_ctx* ctx, int32_t* d_idx, int64_t capacity, int* groups, int* heads, int* k, void* stream) {
     NEED_MODEL("r3g_kv_selection_last");
     if (!m->kv_last_groups) return fail(R3G_ERR_STATE, "r3g_kv_selection_last: no pass has been evaluated in top-k mode");

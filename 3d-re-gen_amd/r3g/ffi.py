@@ -109,6 +109,15 @@ SYMBOLS = {
     "r3g_op_kv_select": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "r3g_op_kv_gather": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
     "r3g_op_geo_tail": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, _P, _P]),
+    "r3g_op_layernorm": (_I, [_P, _I, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _P,
+                              ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, ctypes.c_float, _P]),
+    "r3g_op_ln_dot": (_I, [_P, _I, ctypes.c_int64, _I, _I, _I, _P, _P, ctypes.c_float, _P, ctypes.c_float, _P, _P]),
+    "r3g_op_qkv_split": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,
+                              ctypes.c_float, ctypes.c_float, _P]),
+    "r3g_op_group_norm": (_I, [_P, _I, _I, _I, _P, _P, ctypes.c_float, _I, _P, _I, _P, ctypes.c_int64, _P]),
+    "r3g_op_softmax_rows": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, ctypes.c_float, _P]),
+    "r3g_op_geglu": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P]),
+    "r3g_op_swiglu": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P]),
     "r3g_set_staging": (_I, [_I]),
     "r3g_set_option": (_I, [ctypes.c_char_p, _I]),
     "r3g_get_option": (_I, [ctypes.c_char_p, _P]),

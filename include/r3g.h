@@ -695,6 +695,52 @@ int r3g_op_geo_tail(const uint16_t* d_cat, const uint16_t* d_x0, int n, int hidd
                     const float* d_ln3_w, const float* d_ln3_b, const uint16_t* d_w_fc, const float* d_b_fc, const uint16_t* d_w_fp,
                     const float* d_b_fp, const float* d_lnpost_w, const float* d_lnpost_b, const float* d_out_w, float out_b,
                     float* d_logits, void* stream);
+/* The row kernels of the hot path, one launch each on caller-owned operands (tests/test_row_kernels_gpu.py,
+ * tests/test_tex_row_kernels_gpu.py).  Every entry point checks the contract stated here -- the model's own launches meet it by
+ * construction, the launchers check only part of it -- and a violation is R3G_ERR_INVALID with nothing written.  Common to all:
+ * rows >= 1 (l, batch, heads, nb likewise), every pointer named as required non-null, a row stride at least the row's width.
+ *
+ * layernorm: y bf16 [rows][c] = ((x - mean) rstd (w ? w[c] : 1) + (b ? b[c] : 0)) (1 + scale[batch][c]) + shift[batch][c], every product and
+ *   sum rounded on its own, biased variance, rstd = 1 / sqrt(var + eps).  x_format 0 f32 | 1 bf16 | 2 fp16 (16-bit rows: c % 256 == 0);
+ *   c % 64 == 0, 64 <= c <= 2048.  Row r is row r % rows_per_batch of batch r / rows_per_batch: x at batch * x_batch_stride + row * ldx,
+ *   y likewise (y batches must not overlap), scale / shift (each may be null) at batch * mod_stride.  Rows in [seg2_row0, seg2_row1) take
+ *   d_scale2 / d_shift2 (both required then) instead.  16-bit rows, and f32 rows with c % 256 == 0, ldx % 4 == 0 and ldy % 4 == 0, run on
+ *   the row-in-registers kernel, which moves four elements per access: ldx, x_batch_stride, ldy, y_batch_stride, mod_stride % 4 == 0, x
+ *   and y aligned to four elements, the six vectors to 16 bytes.  Any other f32 row runs on the scalar kernel (no alignment demands).
+ *   d_y8 != null: INSTEAD of y, OCP e4m3 bytes [rows][ldy8] and d_y_scale f32 [rows] (amax / 448 of the finished row, 1 for an all-zero
+ *   row; round to nearest even).  That form indexes its outputs by the launch row, so it takes one batch only: d_y null, ldy = 0, both
+ *   batch strides 0, rows_per_batch >= rows, c % 256 == 0 on the row-in-registers kernel, ldy8 % 4 == 0, d_y8 4-byte aligned.
+ * ln_dot: d_out f32 [rows] = (do_ln ? LN(x) (lnw, lnb: both or neither) : x) . w + b; x f32 or bf16 (x_bf16 1: c % 256 == 0), c as above;
+ *   f32 rows with c % 256 == 0 and ldx % 4 == 0, and all bf16 rows, move four elements per access (alignment as for layernorm).
+ * qkv_split: src bf16 [batch][l][ld] -> Q bf16 [batch][heads][lq_pad][64], K bf16 [batch][heads][lk_pad][64], Vt bf16
+ *   [batch][heads][64][lk_pad] in the attention kernel's key order (r3g_op_attention), token t at destination row dst_row0 + t.  Head h of
+ *   q | k | v sits at columns x_off + h * head_stride .. + 63; x_off = -1 with a null destination: absent.  norm 0 none | 1 RMSNorm | 2
+ *   LayerNorm over the 64 columns of q and of k (weights optional, biases for 2 only), q then times q_scale (0: 1).  dst_row0 % 64 == 0,
+ *   lq_pad % 128 == 0, lk_pad % 64 == 0, dst_row0 + l <= the pad of every destination given.  V^T columns of the last 64-token block
+ *   past l are written as zeros; nothing else outside the call's rows and columns is written.
+ * group_norm: x f32 [nb][rows][c] -> y bf16 [nb][rows][c] = act(((x + addv[sample]) - mean) rstd gamma + beta), statistics per (sample,
+ *   group) over rows x c / groups values, biased; act = SiLU when do_silu.  c % 4 == 0, c <= 3072, 1 <= groups <= 256, c % groups == 0;
+ *   addv (may be null) f32 [nb][add_stride], add_stride % 4 == 0; 16-byte aligned x / gamma / beta / addv, 8-byte aligned y.
+ *   Synchronous (it allocates the partial-sum workspace per call).
+ * softmax_rows: P bf16 [rows][n] = softmax(scale * S[r][:]), S f32; n % 4 == 0, lds % 4 == 0, ldp % 4 == 0, S 16-byte and P 8-byte
+ *   aligned, scale > 0 (the kernel scales the maximum of the raw scores).
+ * geglu: out bf16 [rows][f] = in[r][c] * gelu_erf(in[r][f + c]);  swiglu: out = silu(in[r][c]) * in[r][f + c].  in bf16 [rows][ldi];
+ *   f % 8 == 0, ldi >= 2 f, ldi % 8 == 0, ldo % 8 == 0, both pointers 16-byte aligned. */
+int r3g_op_layernorm(const void* d_x, int x_format, int64_t ldx, int64_t x_batch_stride, uint16_t* d_y, int64_t ldy, int64_t y_batch_stride,
+                     uint8_t* d_y8, int64_t ldy8, float* d_y_scale, const float* d_w, const float* d_b, const float* d_scale,
+                     const float* d_shift, int64_t mod_stride, int seg2_row0, int seg2_row1, const float* d_scale2, const float* d_shift2,
+                     int rows, int c, int rows_per_batch, float eps, void* stream);
+int r3g_op_ln_dot(const void* d_x, int x_bf16, int64_t ldx, int rows, int c, int do_ln, const float* d_lnw, const float* d_lnb, float eps,
+                  const float* d_w, float b, float* d_out, void* stream);
+int r3g_op_qkv_split(const uint16_t* d_src, int64_t ld, int64_t src_batch_stride, int q_off, int k_off, int v_off, int head_stride,
+                     uint16_t* d_q, uint16_t* d_k, uint16_t* d_vt, int lq_pad, int lk_pad, int dst_row0, int batch, int heads, int l,
+                     int norm, const float* d_qw, const float* d_qb, const float* d_kw, const float* d_kb, float eps, float q_scale,
+                     void* stream);
+int r3g_op_group_norm(const float* d_x, int rows, int c, int groups, const float* d_gamma, const float* d_beta, float eps, int do_silu,
+                      uint16_t* d_y, int nb, const float* d_addv, int64_t add_stride, void* stream);
+int r3g_op_softmax_rows(const float* d_s, int64_t lds, uint16_t* d_p, int64_t ldp, int rows, int n, float scale, void* stream);
+int r3g_op_geglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f, void* stream);
+int r3g_op_swiglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f, void* stream);
 /* FP8 operands (BASELINE.json configs[3]).  quant_fp8: bf16 [rows][k] -> OCP e4m3 bytes [rows][k] + one fp32 scale per row
  * (amax / 448; round to nearest even, saturating).  gemm_fp8: C = epilogue((scale_a[m] scale_w[n]) sum_k a8[m][k] w8[n][k] +
  * bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the bf16 matrix rate); k % 256 == 0, lda / ldw in bytes and multiples
