@@ -1,10 +1,22 @@
 """Stand-in for the `trimesh` package where it is not installed (it is not in this image).
 
 The reference stage imports trimesh only for `isinstance(mesh, trimesh.Trimesh)` in its optional remesh step
-(src/2d_to_3d_models/run.py:21,36); the mesh object itself comes from hy3dgen.  With this directory on PYTHONPATH
+(src/2d_to_3d_models/run.py:21,36); the mesh object itself comes from hy3dgen.  Its evaluation
+(src/evaluation/run_eval.py) loads two .ply clouds with `trimesh.load(path).vertices`; `PointCloud` and the PLY reader
+of r3g/cloud.py serve that.  With this directory on PYTHONPATH
 *instead of* a real trimesh, that check sees the mesh class of the MI355X path.  Do NOT put it on the path when the real
 trimesh is installed."""
-from r3g.mesh import Mesh as Trimesh, load_glb as load  # noqa: F401
+from r3g.cloud import PointCloud, load_ply as _load_ply  # noqa: F401
+from r3g.mesh import Mesh as Trimesh, load_glb as _load_glb  # noqa: F401
+
+
+def load(data):
+    """a path ending in .ply: the PointCloud of its vertices (the reference's evaluation reads its clouds so); anything else
+    (a .glb path, or GLB bytes) as before: the Mesh written by Mesh.to_glb"""
+    if isinstance(data, str) and data.lower().endswith(".ply"):
+        return _load_ply(data)
+    return _load_glb(data)
+
 
 import sys as _sys
 

@@ -168,5 +168,24 @@ static inline void host_fill(const GridN<D>& g, const R* recs, int64_t nf, bool 
     }
 }
 
+// ---- records with one home cell each (the point clouds of section 4k) -------------------------------------------------------
+// A record type R with a third function
+//   int grid_home(const GridN<D>&, const R&)          the one cell that lists the record
+// is listed exactly once, without the kBinMargin widening, and the build moves the records themselves into cell order:
+// sorted[starts[cell] .. starts[cell + 1]) are cell's records.  Same arrays and the same open order inside a cell as above.
+template <int D, class R>
+static inline void host_fill_home(const GridN<D>& g, const R* recs, int64_t n, bool reverse_fill, uint32_t* starts, uint32_t* cursor,
+                                  R* sorted) {
+    for (int64_t k = 0; k < n; ++k)
+        if (grid_member(recs[k])) ++starts[grid_home(g, recs[k]) + 1];
+    for (int64_t c = 0, nc = cells<D>(g.res); c < nc; ++c) starts[c + 1] += starts[c];
+    for (int64_t kk = 0; kk < n; ++kk) {
+        const int64_t k = reverse_fill ? n - 1 - kk : kk;
+        if (!grid_member(recs[k])) continue;
+        const int cell = grid_home(g, recs[k]);
+        sorted[starts[cell] + cursor[cell]++] = recs[k];
+    }
+}
+
 }  // namespace r3g_grid
 #endif

@@ -1,6 +1,6 @@
 // grid_csr_device.h -- the device build of a grid in CSR form (grid_csr.h) as templates over (D, record type): the end of
 // the records kernel, the pair count, the per-cell count and fill, and the launch sequences around them.  Included by
-// meshdist_kernels.hip and meshinside_kernels.hip only; the anonymous namespace gives each its own kernels, so no kernel
+// meshdist_kernels.hip, meshinside_kernels.hip and cloud_kernels.hip only; the anonymous namespace gives each its own kernels, so no kernel
 // symbol is shared between code objects.  Integer atomics only, and their order decides nothing: the bounding box is a
 // min / max, the counts are sums, and the order of the records inside a cell is left open by contract.
 #ifndef R3G_GRID_CSR_DEVICE_H
@@ -95,6 +95,36 @@ hipError_t csr_fill_launch(char* ws, const GridCsrLayout& lay, int64_t nf, const
     R3G_HIP(csr_exclusive_scan(counts, starts, n1, (unsigned*)(ws + lay.off_sums), s));
     R3G_HIP(hipMemsetAsync(counts, 0, 4 * (size_t)n1, s));
     hipLaunchKernelGGL((csr_bin<D, R, true>), dim3(grid_for(nf)), dim3(kT), 0, s, recs, nf, g, counts, (const unsigned*)starts, pairs);
+    return hipGetLastError();
+}
+
+// ---- records with one home cell each (grid_csr.h, the last section) ------------------------------------------------------------
+// FILL == false: counts[home] += 1;  FILL == true: sorted[starts[home] + cursor[home]++] = the record
+template <int D, class R, bool FILL>
+__global__ __launch_bounds__(kT) void csr_bin_home(const R* __restrict__ recs, int64_t n, GridN<D> g, unsigned* __restrict__ counts,
+                                                   const unsigned* __restrict__ starts, R* __restrict__ sorted) {
+    for (int64_t f = (int64_t)blockIdx.x * kT + threadIdx.x; f < n; f += (int64_t)gridDim.x * kT) {
+        const R r = recs[f];
+        if (!grid_member(r)) continue;
+        const int cell = grid_home(g, r);
+        const unsigned slot = atomicAdd(&counts[cell], 1u);
+        if (FILL) sorted[starts[cell] + slot] = r;
+    }
+}
+
+// per-cell counts -> exclusive scan -> the member records into sorted [members] in cell order
+template <int D, class R>
+hipError_t csr_fill_home_launch(char* ws, const GridCsrLayout& lay, int64_t n, const GridN<D>& g, R* sorted, hipStream_t s) {
+    const int64_t n1 = r3g_grid::cells<D>(g.res) + 1;          // the extra element receives the total
+    unsigned* counts = (unsigned*)(ws + lay.off_counts);
+    unsigned* starts = (unsigned*)(ws + lay.off_starts);
+    const R* recs = (const R*)(ws + lay.off_recs);
+    R3G_HIP(hipMemsetAsync(counts, 0, 4 * (size_t)n1, s));
+    hipLaunchKernelGGL((csr_bin_home<D, R, false>), dim3(grid_for(n)), dim3(kT), 0, s, recs, n, g, counts, (const unsigned*)nullptr,
+                       (R*)nullptr);
+    R3G_HIP(csr_exclusive_scan(counts, starts, n1, (unsigned*)(ws + lay.off_sums), s));
+    R3G_HIP(hipMemsetAsync(counts, 0, 4 * (size_t)n1, s));
+    hipLaunchKernelGGL((csr_bin_home<D, R, true>), dim3(grid_for(n)), dim3(kT), 0, s, recs, n, g, counts, (const unsigned*)starts, sorted);
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // grid_csr_kernels.h -- host-side interface of the device build of a grid in CSR form (grid_csr.h; internal to libr3g.so):
 // what a build leaves behind, and the exclusive scan of grid_csr_kernels.hip.  The kernels that depend on the record type
-// are templates (grid_csr_device.h), instantiated by meshdist_kernels.hip and meshinside_kernels.hip.
+// are templates (grid_csr_device.h), instantiated by meshdist_kernels.hip, meshinside_kernels.hip and cloud_kernels.hip.
 #ifndef R3G_GRID_CSR_KERNELS_H
 #define R3G_GRID_CSR_KERNELS_H
 #include <hip/hip_runtime.h>

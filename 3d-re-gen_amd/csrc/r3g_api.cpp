@@ -308,6 +308,8 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->h_fit) (void)hipHostFree(c->h_fit);
     if (c->meshinside.ws) (void)hipFree(c->meshinside.ws);
     if (c->meshinside.pairs) (void)hipFree(c->meshinside.pairs);
+    if (c->cloud.ws) (void)hipFree(c->cloud.ws);
+    if (c->cloud.pairs) (void)hipFree(c->cloud.pairs);
     if (c->meshtopo_ws) (void)hipFree(c->meshtopo_ws);
     if (c->h_topo) (void)hipHostFree(c->h_topo);
     if (c->meshfill_ws) (void)hipFree(c->meshfill_ws);
@@ -453,6 +455,67 @@ int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, fl
 }
 
 // ---- mesh registration ------------------------------------------------------------------------
+// ---- point clouds ----------------------------------------------------------------------------------------
+int r3g_cloud_build(r3g_ctx* ctx, const float* d_points, int64_t n_points, int resolution, int* resolution_out, int64_t* skipped_out,
+                    void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_cloud_build: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    GridCsrState<3>* st = &c->cloud;
+    hipStream_t s = (hipStream_t)stream;
+    st->built = false;
+    if (n_points <= 0 || n_points > 0x7fffffffll) return fail(R3G_ERR_INVALID, "r3g_cloud_build: n_points outside [1, 2^31 - 1]");
+    if (!d_points) return fail(R3G_ERR_INVALID, "r3g_cloud_build: null buffer");
+    if (resolution < 0 || resolution > r3g_cl::kMaxRes)
+        return fail(R3G_ERR_INVALID, "r3g_cloud_build: resolution outside [0, %d] (0 = automatic)", r3g_cl::kMaxRes);
+    // the automatic resolution can only fall when points are skipped: the workspace sized for all of them is enough
+    const int res_most = resolution ? resolution : r3g_cl::auto_resolution(n_points, r3g_cl::kPointsPerCell);
+    GridCsrLayout lay;
+    const size_t need = grid_csr_workspace_bytes(n_points, sizeof(r3g_cl::Pt), r3g_grid::cells<3>(res_most), &lay);
+    int rc = c->reserve(&st->ws, &st->ws_bytes, need, "hipMalloc(cloud workspace)");
+    if (rc) return rc;
+    st->lay = lay;
+    hipError_t e = cloud_records(st->ws, lay, d_points, n_points, s);
+    if (e != hipSuccess) return hip_fail(e, "cloud_records");
+    GridCsrSmall sm;
+    if ((rc = grid_small(c, st->ws, lay, "cloud", s, &sm))) return rc;
+    if ((int64_t)sm.skipped >= n_points)
+        return fail(R3G_ERR_INVALID, "r3g_cloud_build: every point has a non-finite coordinate (%lld skipped)", (long long)sm.skipped);
+    const int64_t usable = n_points - (int64_t)sm.skipped;
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) lo[a] = r3g_grid::dec_float(sm.box[a]), hi[a] = r3g_grid::dec_float(sm.box[3 + a]);
+    const int res = resolution ? resolution : r3g_cl::auto_resolution(usable, r3g_cl::kPointsPerCell);
+    const r3g_cl::Grid g = r3g_grid::make_grid(lo, hi, res);
+    if ((rc = c->reserve(&st->pairs, &st->pairs_bytes, sizeof(r3g_cl::Pt) * (size_t)usable, "hipMalloc(cloud points)"))) return rc;
+    e = cloud_fill(st->ws, lay, n_points, g, (r3g_cl::Pt*)st->pairs, s);
+    if (e != hipSuccess) return hip_fail(e, "cloud_fill");
+    e = hipStreamSynchronize(s);      // the caller may free its points, and a fault would surface here
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(cloud_fill)");
+    st->grid = g;
+    st->built = true;
+    if (resolution_out) *resolution_out = g.res;
+    if (skipped_out) *skipped_out = (int64_t)sm.skipped;
+    return R3G_OK;
+}
+
+int r3g_cloud_knn(r3g_ctx* ctx, const float* d_queries, int64_t n_queries, int k, float* d_dist2, int32_t* d_index, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_cloud_knn: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->cloud.built) return fail(R3G_ERR_STATE, "r3g_cloud_knn: no successful r3g_cloud_build on this context");
+    if (k < 1 || k > r3g_cl::kMaxK) return fail(R3G_ERR_INVALID, "r3g_cloud_knn: k outside [1, %d]", r3g_cl::kMaxK);
+    if (n_queries < 0 || n_queries >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_cloud_knn: n_queries out of range");
+    if (n_queries == 0) return R3G_OK;
+    if (!d_queries || !d_dist2 || !d_index) return fail(R3G_ERR_INVALID, "r3g_cloud_knn: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = cloud_knn(c->cloud.ws, c->cloud.lay, c->cloud.grid, (const r3g_cl::Pt*)c->cloud.pairs, d_queries, n_queries, k, d_dist2,
+                             d_index, s);
+    if (e != hipSuccess) return hip_fail(e, "cloud_knn");
+    GridCsrSmall sm;
+    int rc = grid_small(c, c->cloud.ws, c->cloud.lay, "cloud", s, &sm);
+    if (rc) return rc;
+    cloud_add_tests((int64_t)sm.tests);
+    return R3G_OK;
+}
+
 int r3g_meshdist_closest(r3g_ctx* ctx, const float* d_points, int64_t n_points, float* d_dist2, int32_t* d_face, float* d_closest,
                          void* stream) {
     if (!ctx) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: null argument");

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "cloud_kernels.h"
 #include "dmc_kernels.h"
 #include "hier_kernels.h"
 #include "kernels.h"
@@ -39,6 +40,9 @@ struct Ctx {
     // point in mesh: the columns of the last r3g_meshinside_build (separate from the distance grid: both may be held at once)
     GridCsrState<2> meshinside;
     int meshinside_axis = 0;
+    // point clouds: the grid of the last r3g_cloud_build; its `pairs` buffer holds the packed points in cell order (r3g_cl::Pt),
+    // not ids.  Independent of the two grids above: all three may be held at once
+    GridCsrState<3> cloud;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
     // fit h_small), made on first use

@@ -1,0 +1,370 @@
+"""Point clouds on the GPU: exact k nearest neighbours and what the reference's evaluation builds on them
+(include/r3g.h "point clouds").
+
+The primitive is `knn`: for every query point the k smallest (d2, index) pairs over the target cloud, d2 = ((px-qx)^2 +
+(py-qy)^2) + (pz-qz)^2 in float32, by the uniform-grid kernels of csrc/cloud_kernels.hip.  Everything else here is thin
+device-side tensor arithmetic on its output: the scores of the reference's src/evaluation/run_eval.py (`evaluate`), the
+normals that stand in front of its Poisson step (`estimate_normals`) and its cloud ICP (`icp`).  Means and sums are taken
+in float64 on the device.  CUDA tensors in and out; there is no CPU path.  `PointCloud`, `load_ply` and `save_ply` are the
+host-side file layer (numpy) behind compat/trimesh.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import ffi
+
+
+def _cloud_arg(points, what="points"):
+    if not (torch.is_tensor(points) and points.is_cuda):
+        raise ValueError("%s must live on the GPU (there is no CPU path)" % what)
+    p = points.detach().to(torch.float32).contiguous()
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("expected %s [N,3]" % what)
+    return p
+
+
+def build(points, resolution=None):
+    """r3g_cloud_build on the shared context of the points' device -> dict(resolution, skipped).
+    The context keeps its own packed copy until the next build (`points` may be freed); hold ffi.device_lock(device)
+    across build and knn."""
+    p = _cloud_arg(points)
+    dev = p.device.index or 0
+    res, skipped = ctypes.c_int(0), ctypes.c_int64(0)
+    with ffi.device_lock(dev), torch.cuda.device(p.device):
+        ffi.check(ffi.lib().r3g_cloud_build(ffi.context(dev), ctypes.c_void_p(p.data_ptr()), p.shape[0], int(resolution or 0),
+                                            ctypes.byref(res), ctypes.byref(skipped), ffi.stream_ptr()))
+    return {"resolution": res.value, "skipped": skipped.value}
+
+
+def knn(queries, k=1):
+    """r3g_cloud_knn against the last build on the queries' device -> (dist2 float32 [N,k], index int32 [N,k]), each row
+    ascending by (dist2, index); (+inf, -1) past the number of usable points, (NaN, -1) for a non-finite query."""
+    q = _cloud_arg(queries, "queries")
+    dev = q.device.index or 0
+    k = int(k)
+    d2 = torch.empty((q.shape[0], max(k, 0)), dtype=torch.float32, device=q.device)
+    idx = torch.empty((q.shape[0], max(k, 0)), dtype=torch.int32, device=q.device)
+    with ffi.device_lock(dev), torch.cuda.device(q.device):
+        ffi.check(ffi.lib().r3g_cloud_knn(ffi.context(dev), ctypes.c_void_p(q.data_ptr()), q.shape[0], k,
+                                          ctypes.c_void_p(d2.data_ptr()), ctypes.c_void_p(idx.data_ptr()), ffi.stream_ptr()))
+    return d2, idx
+
+
+def nearest(queries, points, resolution=None):
+    """Distance from every query to its nearest point of `points` and that point's index -> (dist float32 [N], index int32
+    [N]): dist = sqrt(min d2), index = the lowest one attaining it; a non-finite query gets (NaN, -1).  The result does not
+    depend on `resolution` (cells per axis; None: automatic)."""
+    q = _cloud_arg(queries, "queries")
+    dev = q.device.index or 0
+    with ffi.device_lock(dev):
+        build(points, resolution)
+        d2, idx = knn(q, 1)
+    return d2[:, 0].sqrt(), idx[:, 0]
+
+
+# ---- the reference's evaluation (src/evaluation/run_eval.py, src/utils/metrics.py), each stated once ---------------------------
+def _both_ways(a, b):
+    """unsquared NN distances a->b and b->a"""
+    return nearest(a, b)[0], nearest(b, a)[0]
+
+
+def chamfer_distance(a, b):
+    """[UPSTREAM-RECALLED] pytorch3d.loss.chamfer_distance(a, b, point_reduction="mean", norm=2) for one pair of clouds, as
+    recalled: the mean over a of the SQUARED distance to the nearest point of b, plus the same from b to a (batch of one, so
+    the batch reduction changes nothing).  -> (cd, cd_ab, cd_ba) as Python floats; the means are float64 sums of the float32
+    squared distances."""
+    a, b = _cloud_arg(a, "a"), _cloud_arg(b, "b")
+    dev = a.device.index or 0
+    with ffi.device_lock(dev):
+        build(b)
+        d_ab = knn(a, 1)[0][:, 0]
+        build(a)
+        d_ba = knn(b, 1)[0][:, 0]
+    ab = float(d_ab.to(torch.float64).sum() / d_ab.shape[0])
+    ba = float(d_ba.to(torch.float64).sum() / d_ba.shape[0])
+    return ab + ba, ab, ba
+
+
+def hausdorff(a, b):
+    """max(max over a of dist(a_i, b), max over b of dist(b_j, a)), unsquared (point-cloud-utils' hausdorff_distance)"""
+    d_ab, d_ba = _both_ways(a, b)
+    return max(float(d_ab.max()), float(d_ba.max()))
+
+
+def fscore(pred, gt, tau=0.1):
+    """metrics.py::compute_fscore: P = share of pred points strictly closer than tau to gt, R = share of gt points strictly
+    closer than tau to pred, 2 P R / (P + R + 1e-8), the shares and the ratio in float32 as upstream has them."""
+    d_pg, d_gp = _both_ways(pred, gt)
+    tau = float(tau)
+    p = (d_pg < tau).to(torch.float64).sum().to(torch.float32) / d_pg.shape[0]
+    r = (d_gp < tau).to(torch.float64).sum().to(torch.float32) / d_gp.shape[0]
+    return float(2 * (p * r) / (p + r + 1e-8))
+
+
+def precision_recall(pred, gt, threshold=0.01):
+    """run_eval.py::compute_precision_recall, WITH ITS NAMING: `precision` is the share of **gt** points strictly within
+    `threshold` of pred (it queries pred's tree with the gt points), `recall` the share of pred points within it of gt --
+    the reverse of the usual convention, and of `fscore` above.  Kept so that the numbers compare with upstream's reports.
+    -> (precision, recall) as Python floats"""
+    d_pg, d_gp = _both_ways(pred, gt)
+    t = float(threshold)
+    precision = float((d_gp < t).to(torch.float64).sum() / d_gp.shape[0])
+    recall = float((d_pg < t).to(torch.float64).sum() / d_pg.shape[0])
+    return precision, recall
+
+
+def _voxelize(points, voxel_size, grid_size, min_bound):
+    idx = torch.floor((points - min_bound) / voxel_size).long().clamp(0, grid_size - 1)
+    grid = torch.zeros((grid_size, grid_size, grid_size), dtype=torch.bool, device=points.device)
+    grid[idx[:, 0], idx[:, 1], idx[:, 2]] = True
+    return grid
+
+
+def volume_iou(pred, gt, voxel_size=0.05, grid_size=64, mode="pcd"):
+    """metrics.py::compute_volume_iou in its own float32 arithmetic, torch ops only.  mode "pcd": both clouds voxelised from
+    their common lower corner (floor((x - min) / voxel_size), clamped to the grid), occupied voxels intersected and united;
+    mode "bbox": the IoU of the two axis-aligned bounding boxes.  Both / (union + 1e-8)."""
+    pred, gt = _cloud_arg(pred, "pred"), _cloud_arg(gt, "gt")
+    if mode == "pcd":
+        min_bound = torch.min(pred.min(0).values, gt.min(0).values)
+        pv = _voxelize(pred, voxel_size, grid_size, min_bound)
+        gv = _voxelize(gt, voxel_size, grid_size, min_bound)
+        inter = (pv & gv).sum().float()
+        union = (pv | gv).sum().float()
+        return float(inter / (union + 1e-8))
+    if mode == "bbox":
+        pmin, pmax, gmin, gmax = pred.min(0).values, pred.max(0).values, gt.min(0).values, gt.max(0).values
+        inter = (torch.min(pmax, gmax) - torch.max(pmin, gmin)).clamp(min=0)
+        inter_vol = inter[0] * inter[1] * inter[2]
+        pd, gd = (pmax - pmin).clamp(min=0), (gmax - gmin).clamp(min=0)
+        union_vol = pd[0] * pd[1] * pd[2] + gd[0] * gd[1] * gd[2] - inter_vol
+        return float(inter_vol / (union_vol + 1e-8))
+    raise ValueError("Invalid mode: %s" % mode)
+
+
+def evaluate(pred, gt):
+    """The point-cloud scores of run_eval.py under its keys: CD (`chamfer_distance`), FSCORE (`fscore`, tau 0.1), IOU_BBOX
+    (`volume_iou`, mode "bbox"), HAUSDORFF, PRECISION and RECALL (`precision_recall`, threshold 0.01, upstream's naming).
+    Two builds and two queries serve all of them."""
+    pred, gt = _cloud_arg(pred, "pred"), _cloud_arg(gt, "gt")
+    dev = pred.device.index or 0
+    with ffi.device_lock(dev):
+        build(gt)
+        d2_pg = knn(pred, 1)[0][:, 0]
+        build(pred)
+        d2_gp = knn(gt, 1)[0][:, 0]
+    d_pg, d_gp = d2_pg.sqrt(), d2_gp.sqrt()
+    n_p, n_g = d_pg.shape[0], d_gp.shape[0]
+    p = (d_pg < 0.1).to(torch.float64).sum().to(torch.float32) / n_p
+    r = (d_gp < 0.1).to(torch.float64).sum().to(torch.float32) / n_g
+    return {"CD": float(d2_pg.to(torch.float64).sum() / n_p) + float(d2_gp.to(torch.float64).sum() / n_g),
+            "FSCORE": float(2 * (p * r) / (p + r + 1e-8)),
+            "IOU_BBOX": volume_iou(pred, gt, mode="bbox"),
+            "HAUSDORFF": max(float(d_pg.max()), float(d_gp.max())),
+            "PRECISION": float((d_gp < 0.01).to(torch.float64).sum() / n_g),
+            "RECALL": float((d_pg < 0.01).to(torch.float64).sum() / n_p)}
+
+
+# ---- normals ---------------------------------------------------------------------------------------------------------------------
+def neighbour_covariances(points, k=30):
+    """float64 covariance of each point's k nearest neighbours in the cloud itself (the point included, as Open3D's KNN search
+    has it) -> (cov float64 [N,3,3], count int64 [N], index int32 [N,k]).  Gathered and summed in the k-list's order, one
+    operation at a time: mean = (sum_j x_j) / count, cov = (sum_j (x_j - mean)(x_j - mean)^T) / count.  Slots without a
+    neighbour (index -1) take no part."""
+    p = _cloud_arg(points)
+    dev = p.device.index or 0
+    with ffi.device_lock(dev):
+        build(p)
+        _, idx = knn(p, k)
+    have = idx >= 0
+    count = have.sum(1)
+    w = have.to(torch.float64)
+    nb = p.to(torch.float64)[idx.clamp(min=0).long()]         # [N,k,3]
+    nb = torch.where(have[:, :, None], nb, torch.zeros_like(nb))
+    s = torch.zeros((p.shape[0], 3), dtype=torch.float64, device=p.device)
+    for j in range(idx.shape[1]):
+        s = s + nb[:, j]
+    cnt = count.clamp(min=1).to(torch.float64)
+    mean = s / cnt[:, None]
+    d = (nb - mean[:, None, :]) * w[:, :, None]
+    cov = torch.zeros((p.shape[0], 3, 3), dtype=torch.float64, device=p.device)
+    for j in range(idx.shape[1]):
+        outer = d[:, j, :, None] * d[:, j, None, :]
+        cov = cov + outer
+    return cov / cnt[:, None, None], count, idx
+
+
+def estimate_normals(points, k=30):
+    """Open3D's pcd.estimate_normals(KDTreeSearchParamKNN(k)): the unit eigenvector of the smallest eigenvalue of the
+    covariance of each point's k nearest neighbours (`neighbour_covariances`, torch.linalg.eigh in float64) -> float32 [N,3].
+    The SIGN is left open -- n and -n are the same plane; orienting normals consistently is a propagation step this module
+    does not do.  A point with fewer than 3 usable neighbours (itself included) gets NaN, and so does a non-finite point."""
+    cov, count, _ = neighbour_covariances(points, k)
+    ok = (count >= 3) & torch.isfinite(cov).all(-1).all(-1)
+    eye = torch.eye(3, dtype=torch.float64, device=cov.device)
+    _, vec = torch.linalg.eigh(torch.where(ok[:, None, None], cov, eye))
+    n = vec[:, :, 0]
+    n = n / n.norm(dim=1, keepdim=True)
+    n = torch.where(ok[:, None], n, torch.full_like(n, float("nan")))
+    return n.to(torch.float32)
+
+
+# ---- cloud ICP -------------------------------------------------------------------------------------------------------------------
+def rigid_transform(a, b):
+    """metrics.py::compute_rigid_transform: the rotation R and translation t that minimise sum |R a_i + t - b_i|^2 (Kabsch,
+    with the reflection fix: the last singular direction is negated when det < 0).  Sums in float64.  a, b [N,3]
+    -> (R float64 [3,3], t float64 [3])"""
+    a64, b64 = a.to(torch.float64), b.to(torch.float64)
+    ca, cb = a64.sum(0) / a64.shape[0], b64.sum(0) / b64.shape[0]
+    h = (a64 - ca).T @ (b64 - cb)
+    u, _, vh = torch.linalg.svd(h)
+    v = vh.T
+    det = torch.linalg.det(v @ u.T)
+    diag = torch.diag(torch.stack([torch.ones_like(det), torch.ones_like(det), det]))
+    r = v @ diag @ u.T
+    return r, cb - r @ ca
+
+
+def icp(src, dst, max_iterations=20, tolerance=1e-5):
+    """metrics.py::icp for one pair of clouds: per iteration the nearest point of dst to every moved source point (knn, k = 1,
+    one build of dst for all iterations), `rigid_transform` on those pairs, the move, and upstream's stop test
+    |previous mean distance - mean distance| < tolerance on the mean distance to the pairs just used.  The moved points are
+    float32 (they are what the next search sees); R, t and every sum are float64.
+    -> (moved float32 [N,3], R float64 [3,3], t float64 [3]) with moved ~ src @ R^T + t"""
+    cur, dst = _cloud_arg(src, "src").clone(), _cloud_arg(dst, "dst")
+    dev = cur.device.index or 0
+    r_all = torch.eye(3, dtype=torch.float64, device=cur.device)
+    t_all = torch.zeros(3, dtype=torch.float64, device=cur.device)
+    prev = float("inf")
+    with ffi.device_lock(dev):
+        build(dst)
+        for _ in range(int(max_iterations)):
+            _, idx = knn(cur, 1)
+            near = dst[idx[:, 0].clamp(min=0).long()]
+            r, t = rigid_transform(cur, near)
+            cur = (cur.to(torch.float64) @ r.T + t).to(torch.float32)
+            r_all, t_all = r @ r_all, r @ t_all + t
+            err = float((cur.to(torch.float64) - near.to(torch.float64)).norm(dim=1).sum() / cur.shape[0])
+            if abs(prev - err) < tolerance:
+                break
+            prev = err
+    return cur, r_all, t_all
+
+
+# ---- files: the PLY layer behind compat/trimesh (host side, numpy) ---------------------------------------------------------------
+class PointCloud:
+    """trimesh.PointCloud as the reference's evaluation uses it: `.vertices` (float64 [N,3], numpy), optional `.colors`
+    (uint8 [N,3]) and `.export(path)`, which writes a binary little-endian PLY."""
+
+    def __init__(self, vertices, colors=None):
+        self.vertices = np.asarray(vertices, np.float64).reshape(-1, 3)
+        self.colors = None if colors is None else np.asarray(colors)[:, :3].astype(np.uint8).reshape(-1, 3)
+        if self.colors is not None and len(self.colors) != len(self.vertices):
+            raise ValueError("PointCloud: %d colours for %d vertices" % (len(self.colors), len(self.vertices)))
+
+    def export(self, path=None, file_type="ply"):
+        if file_type != "ply" or (path is not None and not str(path).lower().endswith(".ply")):
+            raise ValueError("PointCloud.export writes PLY only")
+        data = save_ply(None, self.vertices, self.colors)
+        if path is not None:
+            with open(path, "wb") as fh:
+                fh.write(data)
+        return data
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def save_ply(path, vertices, colors=None, binary=True):
+    """vertices [N,3] (written as float32) and optional uint8 colours [N,3] as a PLY with one `vertex` element, binary
+    little-endian or ascii -> the bytes (also written to `path` unless it is None)"""
+    v = np.asarray(vertices, np.float32).reshape(-1, 3)
+    c = None if colors is None else np.asarray(colors).astype(np.uint8).reshape(-1, 3)
+    head = ["ply", "format %s 1.0" % ("binary_little_endian" if binary else "ascii"), "element vertex %d" % len(v),
+            "property float x", "property float y", "property float z"]
+    if c is not None:
+        head += ["property uchar red", "property uchar green", "property uchar blue"]
+    head = ("\n".join(head + ["end_header"]) + "\n").encode("ascii")
+    if binary:
+        rec = np.zeros(len(v), dtype=[("v", "<f4", 3)] + ([("c", "u1", 3)] if c is not None else []))
+        rec["v"] = v
+        if c is not None:
+            rec["c"] = c
+        body = rec.tobytes()
+    else:
+        rows = []
+        for i in range(len(v)):
+            row = " ".join(repr(float(x)) for x in v[i])
+            rows.append(row + (" %d %d %d" % tuple(c[i]) if c is not None else ""))
+        body = ("\n".join(rows) + ("\n" if rows else "")).encode("ascii")
+    data = head + body
+    if path is not None:
+        with open(path, "wb") as fh:
+            fh.write(data)
+    return data
+
+
+def load_ply(data):
+    """A PLY file (path or bytes), ascii or binary little-endian -> PointCloud of its `vertex` element's x y z and, when all
+    three are there, red green blue.  Other properties, and every other element (faces), are ignored."""
+    if isinstance(data, str):
+        with open(data, "rb") as fh:
+            data = fh.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError("not a PLY file")
+    body = data.find(b"\n", end) + 1
+    fmt, elements = None, []
+    for line in data[:end].decode("ascii", "replace").splitlines():
+        w = line.split()
+        if not w or w[0] == "comment":
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property" and elements:
+            elements[-1][2].append(w[1:])
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError("PLY format %r is not supported (ascii and binary_little_endian are)" % fmt)
+    cols = None
+    tokens = data[body:].split() if fmt == "ascii" else None
+    pos = 0 if fmt == "ascii" else body
+    for name, count, props in elements:
+        scalar = all(p[0] != "list" for p in props)
+        if name == "vertex":
+            if not scalar:
+                raise ValueError("PLY: list property in the vertex element")
+            names = [p[1] for p in props]
+            if fmt == "ascii":
+                tab = np.array(tokens[pos:pos + count * len(names)], dtype=np.float64).reshape(count, len(names))
+                cols = {n: tab[:, i] for i, n in enumerate(names)}
+            else:
+                dt = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in props])
+                tab = np.frombuffer(data, dt, count, pos)
+                cols = {n: tab[n] for n in names}
+            break                                           # nothing after the vertices is needed
+        if fmt == "ascii":                                  # skip an element that precedes the vertices
+            for _ in range(count):
+                for p in props:
+                    pos += 1 + int(tokens[pos]) if p[0] == "list" else 1
+        elif scalar:
+            pos += count * sum(np.dtype(_PLY_TYPES[p[0]]).itemsize for p in props)
+        else:
+            for _ in range(count):
+                for p in props:
+                    if p[0] == "list":
+                        n = int(np.frombuffer(data, "<" + _PLY_TYPES[p[1]], 1, pos)[0])
+                        pos += np.dtype(_PLY_TYPES[p[1]]).itemsize + n * np.dtype(_PLY_TYPES[p[2]]).itemsize
+                    else:
+                        pos += np.dtype(_PLY_TYPES[p[0]]).itemsize
+    if cols is None or not all(a in cols for a in "xyz"):
+        raise ValueError("PLY: no vertex element with x y z")
+    v = np.stack([np.asarray(cols[a], np.float64) for a in "xyz"], 1)
+    c = None
+    if all(a in cols for a in ("red", "green", "blue")):
+        c = np.stack([np.asarray(cols[a]).astype(np.uint8) for a in ("red", "green", "blue")], 1)
+    return PointCloud(v, c)

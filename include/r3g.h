@@ -305,6 +305,29 @@ int r3g_meshfill_plan(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const
 int r3g_meshfill_emit(r3g_ctx* ctx, int32_t* d_new_faces, float* d_new_verts, void* stream);
 int r3g_meshfill_loops(r3g_ctx* ctx, int64_t* d_loop_start, int32_t* d_loop_verts, int32_t* d_loop_status, void* stream);
 
+/* ---- point clouds: exact k nearest neighbours ---------------------------------------------------
+ * Point against point, where sections 4f-4h are point against triangle (r3g/cloud.py builds the reference's evaluation scores,
+ * normals and cloud ICP on it).  For a query p and a target point q_i, d2(p, q_i) = ((px-qx)^2 + (py-qy)^2) + (pz-qz)^2 in
+ * float32, one rounding per operation, left to right, no contraction (csrc/cloud_core.h; tests/emu/cloud_emu.cpp reproduces it
+ * exactly on the host).  The answer for k is the k smallest pairs (d2, i) in lexicographic order, ascending; equal coordinates
+ * under distinct indices are distinct neighbours.  The grid only prunes: the result does not depend on the resolution.
+ *
+ * r3g_cloud_build: take the target points (d_points float32 [n_points][3]) into a uniform grid of resolution^3 cells over their
+ *   bounding box; resolution 0 = automatic, min(256, max(1, floor(cbrt(usable / P)))) with P = 1 point per cell.  A point with a non-finite coordinate is
+ *   left out and counted in *skipped_out; indices stay those of d_points.  The context keeps a packed copy of its own in cell order
+ *   (16 bytes a point), so d_points may be freed afterwards; the copy is separate from the grids of r3g_meshdist_build and
+ *   r3g_meshinside_build, a context holds all three at once.  Synchronises `stream`.  n_points == 0 or above 2^31 - 1, no usable
+ *   point, a resolution outside [0, 256]: R3G_ERR_INVALID, before any launch where the sizes show it.  A failed build leaves the
+ *   context without a cloud.  The out pointers may be NULL.
+ * r3g_cloud_knn: for each of d_queries float32 [n_queries][3] its k nearest target points, k in [1, 32] (else R3G_ERR_INVALID):
+ *   d_dist2 float32 [n_queries][k] and d_index int32 [n_queries][k], ascending by (d2, index).  With fewer than k usable points
+ *   the remaining slots are (+inf, -1); a query with a non-finite coordinate gets (NaN 0x7fc00000, -1) in every slot.  Without a
+ *   successful build on this context: R3G_ERR_STATE.  n_queries == 0: success, nothing launched.  Synchronises `stream` (one
+ *   read-back: counter "cloud_tests"). */
+int r3g_cloud_build(r3g_ctx* ctx, const float* d_points, int64_t n_points, int resolution, int* resolution_out, int64_t* skipped_out,
+                    void* stream);
+int r3g_cloud_knn(r3g_ctx* ctx, const float* d_queries, int64_t n_queries, int k, float* d_dist2, int32_t* d_index, void* stream);
+
 /* ---- texture stage: native pieces ------------------------------------------------------------
  * SURVEY.md 8(f) rank 3.  Upstream's Hunyuan3DPaintPipeline (reference call site src/2d_to_3d_models/run.py:97, built at
  * :126-128) uses two native extensions, `custom_rasterizer` (CUDA) and `mesh_processor.cpp`, and bakes the generated views
@@ -860,6 +883,7 @@ int r3g_get_option(const char* name, int* value);
  * "meshtopo_rounds": label rounds those builds launched so far.
  * "meshfill_plans": successful plans of the mesh fill (r3g_meshfill_plan) so far.
  * "meshfill_rounds": pointer-doubling rounds those plans launched so far (twice the report's `rounds` each).
+ * "cloud_tests": point-point distance tests made by r3g_cloud_knn so far.
  * "geo_lnf_passes" / "geo_lnd_passes": geo decoder passes that took the folded ln_3 ("geo_ln3_fold") / ln_post + output_proj
  * ("geo_lnd_fused") epilogues.
  * Kernel-choice counters, one per form a launch can end in, bumped on the host where the launch is issued (tests read them to see
