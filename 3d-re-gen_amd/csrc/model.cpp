@@ -1516,6 +1516,9 @@ int r3g_get_counter(const char* name, int64_t* value) {
     else if (!strcmp(name, "meshfill_plans")) *value = meshfill_plans_total();
     else if (!strcmp(name, "meshfill_rounds")) *value = meshfill_rounds_total();
     else if (!strcmp(name, "cloud_tests")) *value = cloud_tests_total();
+    else if (!strcmp(name, "orient_rounds")) *value = orient_rounds_total();
+    else if (!strcmp(name, "recon_solves")) *value = recon_solves_total();
+    else if (!strcmp(name, "recon_cycles")) *value = recon_cycles_total();
     else {
         for (int i = 0; i < LC_COUNT; ++i)
             if (!strcmp(name, launch_counter_name(i))) { *value = g_launch_counters[i].load(std::memory_order_relaxed); return R3G_OK; }

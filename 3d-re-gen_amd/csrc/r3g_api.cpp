@@ -310,6 +310,9 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->meshinside.pairs) (void)hipFree(c->meshinside.pairs);
     if (c->cloud.ws) (void)hipFree(c->cloud.ws);
     if (c->cloud.pairs) (void)hipFree(c->cloud.pairs);
+    if (c->recon.channels) (void)hipFree(c->recon.channels);
+    if (c->recon.levels) (void)hipFree(c->recon.levels);
+    if (c->orient_ws) (void)hipFree(c->orient_ws);
     if (c->meshtopo_ws) (void)hipFree(c->meshtopo_ws);
     if (c->h_topo) (void)hipHostFree(c->h_topo);
     if (c->meshfill_ws) (void)hipFree(c->meshfill_ws);
@@ -513,6 +516,144 @@ int r3g_cloud_knn(r3g_ctx* ctx, const float* d_queries, int64_t n_queries, int k
     int rc = grid_small(c, c->cloud.ws, c->cloud.lay, "cloud", s, &sm);
     if (rc) return rc;
     cloud_add_tests((int64_t)sm.tests);
+    return R3G_OK;
+}
+
+// ---- normal orientation over the k-NN graph -------------------------------------------------------------
+int r3g_cloud_orient(r3g_ctx* ctx, const float* d_points, const float* d_normals, int64_t n_points, int k, int resolution, int8_t* d_sign,
+                     int32_t* d_tree, int64_t* report, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_points <= 0 || n_points > 0x7fffffffll) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: n_points outside [1, 2^31 - 1]");
+    if (k < r3g_or::kMinK || k > r3g_or::kMaxK) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: k outside [%d, %d]", r3g_or::kMinK, r3g_or::kMaxK);
+    if (resolution < 0 || resolution > r3g_cl::kMaxRes)
+        return fail(R3G_ERR_INVALID, "r3g_cloud_orient: resolution outside [0, %d] (0 = automatic)", r3g_cl::kMaxRes);
+    if (!d_points || !d_normals || !d_sign || !d_tree) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: null buffer");
+    OrientLayout lay;
+    int rc = c->reserve(&c->orient_ws, &c->orient_ws_bytes, orient_workspace_bytes(n_points, k, &lay), "hipMalloc(orient workspace)");
+    if (rc) return rc;
+    char* ws = c->orient_ws;
+    auto small = [&](OrientSmall* out) -> int {
+        hipError_t e = hipMemcpyAsync(c->h_small, ws + lay.off_small, sizeof(OrientSmall), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return hip_fail(e, "r3g_cloud_orient: read-back");
+        memcpy(out, c->h_small, sizeof(OrientSmall));
+        return R3G_OK;
+    };
+    static_assert(sizeof(OrientSmall) <= 64, "the pinned read-back buffer");
+    hipError_t e = orient_prepare(ws, lay, d_points, d_normals, n_points, s);
+    if (e != hipSuccess) return hip_fail(e, "orient_prepare");
+    OrientSmall sm;
+    if ((rc = small(&sm))) return rc;
+    int64_t rounds = 0;
+    if (sm.usable > 0) {
+        // the cloud of the usable points alone (the others are NaN, which the build leaves out): indices stay those of d_points
+        const float* q = (const float*)(ws + lay.off_q);
+        if ((rc = r3g_cloud_build(ctx, q, n_points, resolution, nullptr, nullptr, stream))) return rc;
+        if ((rc = r3g_cloud_knn(ctx, q, n_points, k + 1, (float*)(ws + lay.off_d2), (int32_t*)(ws + lay.off_idx), stream))) return rc;
+        for (;;) {
+            if (rounds >= 64) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: 64 rounds without an end");
+            if ((e = orient_round(ws, lay, n_points, k, s)) != hipSuccess) return hip_fail(e, "orient_round");
+            ++rounds;
+            if ((rc = small(&sm))) return rc;
+            if (sm.merged == 0) break;
+        }
+    }
+    if ((e = orient_finish(ws, lay, d_normals, n_points, k, d_sign, d_tree, s)) != hipSuccess) return hip_fail(e, "orient_finish");
+    if ((rc = small(&sm))) return rc;
+    orient_add_rounds(rounds);
+    if (report) {
+        const int64_t r[r3g_or::kReport] = {(int64_t)sm.usable, (int64_t)sm.trees, (int64_t)sm.flipped, rounds, (int64_t)sm.frustrated, 0, 0, 0};
+        memcpy(report, r, sizeof r);
+    }
+    return R3G_OK;
+}
+
+// ---- Poisson surface on a uniform lattice ---------------------------------------------------------------
+static int recon_small(Ctx* c, ReconState* st, const char* what, hipStream_t s, ReconSmall* out) {
+    hipError_t e = hipMemcpyAsync(c->h_small, st->channels + recon_small_offset(st->lat.depth), sizeof(ReconSmall), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, what);
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, what);
+    memcpy(out, c->h_small, sizeof(ReconSmall));
+    return R3G_OK;
+}
+
+int r3g_recon_splat(r3g_ctx* ctx, const float* d_points, const float* d_normals, int64_t n_points, int depth, const double* centre,
+                    double side, int64_t* d_channels_out, int64_t* usable_out, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_recon_splat: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    ReconState* st = &c->recon;
+    hipStream_t s = (hipStream_t)stream;
+    st->splatted = st->solved = false;
+    if (n_points <= 0 || n_points > 0x7fffffffll) return fail(R3G_ERR_INVALID, "r3g_recon_splat: n_points outside [1, 2^31 - 1]");
+    if (!d_points || !d_normals || !centre) return fail(R3G_ERR_INVALID, "r3g_recon_splat: null buffer");
+    if (depth < r3g_rc::kMinDepth || depth > r3g_rc::kMaxDepth)
+        return fail(R3G_ERR_INVALID, "r3g_recon_splat: depth outside [%d, %d]", r3g_rc::kMinDepth, r3g_rc::kMaxDepth);
+    const r3g_rc::Lattice L = r3g_rc::make_lattice(depth, centre, side);
+    bool ok = side > 0.0 && side - side == 0.0 && L.inv_h > 0.0f && L.inv_2h > 0.0f && L.inv_h - L.inv_h == 0.0f;
+    for (int a = 0; a < 3; ++a) ok = ok && L.lo[a] - L.lo[a] == 0.0f;
+    if (!ok) return fail(R3G_ERR_INVALID, "r3g_recon_splat: the box (centre, side) is not finite and positive in float32");
+    int rc = c->reserve(&st->channels, &st->channels_bytes, recon_channels_bytes(depth), "hipMalloc(recon channels)");
+    if (rc) return rc;
+    if ((rc = c->reserve(&st->levels, &st->levels_bytes, recon_levels_bytes(depth), "hipMalloc(recon levels)"))) return rc;
+    st->lat = L;
+    st->side = side;
+    hipError_t e = recon_splat(st, d_points, d_normals, n_points, s);
+    if (e != hipSuccess) return hip_fail(e, "recon_splat");
+    if (d_channels_out && (e = hipMemcpyAsync(d_channels_out, st->channels, recon_small_offset(depth), hipMemcpyDeviceToDevice, s)) != hipSuccess)
+        return hip_fail(e, "hipMemcpyAsync(recon channels)");
+    ReconSmall sm;
+    if ((rc = recon_small(c, st, "r3g_recon_splat: read-back", s, &sm))) return rc;
+    if (sm.usable == 0) return fail(R3G_ERR_INVALID, "r3g_recon_splat: no usable point (finite coordinates, finite non-zero normal)");
+    st->splatted = true;
+    if (usable_out) *usable_out = (int64_t)sm.usable;
+    return R3G_OK;
+}
+
+int r3g_recon_solve(r3g_ctx* ctx, int cycles, float* d_b_out, float* d_chi_out, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_recon_solve: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    ReconState* st = &c->recon;
+    if (!st->splatted) return fail(R3G_ERR_STATE, "r3g_recon_solve: no successful r3g_recon_splat on this context");
+    if (cycles < 0 || cycles > 1000) return fail(R3G_ERR_INVALID, "r3g_recon_solve: cycles outside [0, 1000]");
+    hipStream_t s = (hipStream_t)stream;
+    st->solved = false;
+    hipError_t e = recon_solve(st, cycles, s);
+    if (e != hipSuccess) return hip_fail(e, "recon_solve");
+    const int depth = st->lat.depth;
+    const size_t bytes = (size_t)recon_nodes(depth) * 4;
+    const float* lv = (const float*)st->levels;
+    if (d_b_out && (e = hipMemcpyAsync(d_b_out, lv + recon_level_offset(depth, depth, 2), bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+        return hip_fail(e, "hipMemcpyAsync(recon b)");
+    if (d_chi_out && (e = hipMemcpyAsync(d_chi_out, lv + recon_level_offset(depth, depth, 0), bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+        return hip_fail(e, "hipMemcpyAsync(recon chi)");
+    e = hipStreamSynchronize(s);      // a fault would surface here, before the state counts as solved
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(recon_solve)");
+    st->solved = true;
+    recon_add_counters(1, cycles);
+    return R3G_OK;
+}
+
+int r3g_recon_sample(r3g_ctx* ctx, int field, const float* d_points, const float* d_normals, int64_t n_points, float* d_values_out,
+                     int64_t* sum_out, int64_t* count_out, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_recon_sample: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    ReconState* st = &c->recon;
+    if (field != 0 && field != 1) return fail(R3G_ERR_INVALID, "r3g_recon_sample: field is 0 (density) or 1 (chi)");
+    if (!st->splatted) return fail(R3G_ERR_STATE, "r3g_recon_sample: no successful r3g_recon_splat on this context");
+    if (field == 1 && !st->solved) return fail(R3G_ERR_STATE, "r3g_recon_sample: field 1 needs a successful r3g_recon_solve on this context");
+    if (n_points <= 0 || n_points > 0x7fffffffll) return fail(R3G_ERR_INVALID, "r3g_recon_sample: n_points outside [1, 2^31 - 1]");
+    if (!d_points) return fail(R3G_ERR_INVALID, "r3g_recon_sample: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = recon_sample(st, field, d_points, d_normals, n_points, d_values_out, s);
+    if (e != hipSuccess) return hip_fail(e, "recon_sample");
+    ReconSmall sm;
+    int rc = recon_small(c, st, "r3g_recon_sample: read-back", s, &sm);
+    if (rc) return rc;
+    if (sum_out) *sum_out = (int64_t)sm.sum;
+    if (count_out) *count_out = (int64_t)sm.usable;
     return R3G_OK;
 }
 

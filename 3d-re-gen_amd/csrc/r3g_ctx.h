@@ -15,6 +15,8 @@
 #include "meshfit_kernels.h"
 #include "meshinside_kernels.h"
 #include "meshtopo_kernels.h"
+#include "orient_kernels.h"
+#include "recon_kernels.h"
 
 namespace r3g {
 
@@ -43,6 +45,11 @@ struct Ctx {
     // point clouds: the grid of the last r3g_cloud_build; its `pairs` buffer holds the packed points in cell order (r3g_cl::Pt),
     // not ids.  Independent of the two grids above: all three may be held at once
     GridCsrState<3> cloud;
+    // Poisson surface: the int64 channels of the last r3g_recon_splat and the solver's float32 lattices (recon_kernels.h)
+    ReconState recon;
+    // normal orientation: the rows, labels and parities of one r3g_cloud_orient (nothing is kept between calls but the buffer)
+    char* orient_ws = nullptr;
+    size_t orient_ws_bytes = 0;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
     // fit h_small), made on first use

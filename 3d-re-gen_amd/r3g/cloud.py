@@ -196,11 +196,43 @@ def neighbour_covariances(points, k=30):
     return cov / cnt[:, None, None], count, idx
 
 
-def estimate_normals(points, k=30):
+ORIENT_MAX_K = 31
+
+
+def orient_normals(points, normals, k=30, resolution=None):
+    """Open3D's pcd.orient_normals_consistent_tangent_plane(k): the sign of every normal by propagation over the minimum
+    spanning forest of the k-nearest-neighbour graph under the weight 1 - |n_i . n_j| (r3g_cloud_orient, DESIGN.md section
+    4l) -> (oriented normals float32 [N,3], info dict: sign int8 [N], tree int32 [N], usable, trees, flipped, rounds,
+    frustrated, k).  k is clamped to [1, 31] (upstream's usual 100 becomes 31: the neighbour lists hold at most 32 entries).
+    In every tree the point with the largest z ends with n_z >= 0; separate trees (k-NN components) are not connected to each
+    other.  A point that is not usable (non-finite, or a zero normal) keeps its normal and gets sign 0.  The call replaces
+    the cloud of `build` on the device's shared context (built at `resolution` cells per axis, None: automatic; the result does
+    not depend on it)."""
+    p, nr = _cloud_arg(points), _cloud_arg(normals, "normals")
+    if p.shape != nr.shape:
+        raise ValueError("points and normals differ in shape")
+    k = min(max(int(k), 1), ORIENT_MAX_K)
+    dev = p.device.index or 0
+    sign = torch.zeros(p.shape[0], dtype=torch.int8, device=p.device)
+    tree = torch.full((p.shape[0],), -1, dtype=torch.int32, device=p.device)
+    rep = (ctypes.c_int64 * 8)()
+    if p.shape[0]:
+        with ffi.device_lock(dev), torch.cuda.device(p.device):
+            ffi.check(ffi.lib().r3g_cloud_orient(ffi.context(dev), ctypes.c_void_p(p.data_ptr()), ctypes.c_void_p(nr.data_ptr()), p.shape[0], k,
+                                                 int(resolution or 0), ctypes.c_void_p(sign.data_ptr()), ctypes.c_void_p(tree.data_ptr()), rep, ffi.stream_ptr()))
+    out = torch.where((sign < 0)[:, None], -nr, nr)
+    info = {"sign": sign, "tree": tree, "usable": rep[0], "trees": rep[1], "flipped": rep[2], "rounds": rep[3], "frustrated": rep[4], "k": k}
+    return out, info
+
+
+def estimate_normals(points, k=30, orient=False, k_orient=30):
     """Open3D's pcd.estimate_normals(KDTreeSearchParamKNN(k)): the unit eigenvector of the smallest eigenvalue of the
     covariance of each point's k nearest neighbours (`neighbour_covariances`, torch.linalg.eigh in float64) -> float32 [N,3].
-    The SIGN is left open -- n and -n are the same plane; orienting normals consistently is a propagation step this module
-    does not do.  A point with fewer than 3 usable neighbours (itself included) gets NaN, and so does a non-finite point."""
+    The SIGN is left open -- n and -n are the same plane -- unless orient=True, which hands the result to `orient_normals`
+    (k_orient neighbours) and returns its normals.  A point with fewer than 3 usable neighbours (itself included) gets NaN,
+    and so does a non-finite point."""
+    if orient:
+        return orient_normals(points, estimate_normals(points, k), k_orient)[0]
     cov, count, _ = neighbour_covariances(points, k)
     ok = (count >= 3) & torch.isfinite(cov).all(-1).all(-1)
     eye = torch.eye(3, dtype=torch.float64, device=cov.device)
@@ -258,11 +290,38 @@ class PointCloud:
     """trimesh.PointCloud as the reference's evaluation uses it: `.vertices` (float64 [N,3], numpy), optional `.colors`
     (uint8 [N,3]) and `.export(path)`, which writes a binary little-endian PLY."""
 
-    def __init__(self, vertices, colors=None):
+    def __init__(self, vertices, colors=None, normals=None):
         self.vertices = np.asarray(vertices, np.float64).reshape(-1, 3)
         self.colors = None if colors is None else np.asarray(colors)[:, :3].astype(np.uint8).reshape(-1, 3)
         if self.colors is not None and len(self.colors) != len(self.vertices):
             raise ValueError("PointCloud: %d colours for %d vertices" % (len(self.colors), len(self.vertices)))
+        self.normals = normals
+
+    @property
+    def normals(self):
+        """float64 [N,3] or None; set by the caller or by `to_mesh`, which keeps the oriented normals it meshed with"""
+        return self._normals
+
+    @normals.setter
+    def normals(self, value):
+        self._normals = None if value is None else np.asarray(value, np.float64).reshape(-1, 3)
+        if self._normals is not None and len(self._normals) != len(self.vertices):
+            raise ValueError("PointCloud: %d normals for %d vertices" % (len(self._normals), len(self.vertices)))
+
+    def to_mesh(self, device="cuda", **kw):
+        """The cloud as a surface, on the GPU (r3g.recon).  Without `.normals`: the reference's `mesh_pointcloud(points, **kw)`,
+        which estimates and orients its own.  With `.normals` (taken as oriented): `reconstruct(points, normals, **kw)`
+        followed by `trim`; trim_quantile (default 0.025) is taken out of kw.  -> Mesh"""
+        from . import recon
+        p = torch.from_numpy(np.ascontiguousarray(self.vertices, np.float32)).to(device)
+        if self.normals is None:
+            return recon.mesh_pointcloud(p, **kw)
+        quantile = kw.pop("trim_quantile", 0.025)
+        nr = torch.from_numpy(np.ascontiguousarray(self.normals, np.float32)).to(device)
+        mesh, densities, info = recon.reconstruct(p, nr, **kw)
+        out = recon.trim(mesh, densities, quantile)
+        out.metadata["recon"] = {k: info[k] for k in ("depth", "level", "residual", "usable")}
+        return out
 
     def export(self, path=None, file_type="ply"):
         if file_type != "ply" or (path is not None and not str(path).lower().endswith(".ply")):

@@ -328,6 +328,58 @@ int r3g_cloud_build(r3g_ctx* ctx, const float* d_points, int64_t n_points, int r
                     void* stream);
 int r3g_cloud_knn(r3g_ctx* ctx, const float* d_queries, int64_t n_queries, int k, float* d_dist2, int32_t* d_index, void* stream);
 
+/* ---- point clouds: consistent orientation of normals --------------------------------------------
+ * The sign of every normal by propagation over the minimum spanning forest of the k-nearest-neighbour graph (Hoppe).  A point is
+ * usable when its coordinates and normal are finite and the normal is non-zero.  {i, j} is an edge when j is among the k nearest
+ * usable neighbours of i other than i, or the other way round (the (k + 1)-list of r3g_cloud_knn of the usable points against
+ * themselves, without the entry i, or without the last one when i is absent).  w(i, j) = 1 - |u_i . u_j| in float32 on the unit
+ * normals; edges are totally ordered by (w, min(i, j), max(i, j)), so the forest is unique.  Along every forest edge
+ * s_i s_j = (u_i . u_j >= 0 ? +1 : -1); in every tree the member with the largest z (the lowest index on a tie) ends with
+ * s n_z >= 0 (+1 where n_z == 0).  csrc/orient_core.h; tests/emu/orient_emu.cpp reproduces it exactly on the host.
+ *
+ * r3g_cloud_orient: d_points, d_normals float32 [n_points][3], k in [1, 31] -> d_sign int8 [n_points] (+1 keep, -1 reverse, 0 for
+ *   a point that is not usable) and d_tree int32 [n_points] (the lowest index of the point's tree, -1 for a point that is not
+ *   usable).  report (int64 [8], may be NULL): usable points, trees, signs that are -1, Boruvka rounds launched (the last one
+ *   merges nothing), frustrated graph edges (their ends disagree with s_i s_j above: a quality figure, not an error), 0, 0, 0.
+ *   The call REPLACES the cloud of r3g_cloud_build on this context by the usable points, built at `resolution` (0 = automatic; the
+ *   grid only prunes, the result does not depend on it).  n_points == 0 or above 2^31 - 1, k outside [1, 31], a resolution outside
+ *   [0, 256], a null buffer: R3G_ERR_INVALID before any launch.  No usable point: success, every sign 0.  Synchronises
+ *   `stream` (one small read-back per round: counter "orient_rounds"). */
+int r3g_cloud_orient(r3g_ctx* ctx, const float* d_points, const float* d_normals, int64_t n_points, int k, int resolution, int8_t* d_sign,
+                     int32_t* d_tree, int64_t* report, void* stream);
+
+/* ---- point clouds: Poisson surface on a uniform lattice -----------------------------------------
+ * Oriented points -> an implicit function chi whose level set is the surface (r3g/recon.py runs marching cubes on it).  The
+ * lattice has n = 2^depth + 1 nodes per axis over the cube (centre, side), node (i0, i1, i2) stored [i0][i1][i2].  Every value is
+ * a pure function of its inputs or an integer sum (csrc/recon_core.h; tests/emu/recon_emu.cpp reproduces each bit on the host).
+ * A context keeps the four int64 channels [4][n^3] and the solver's float32 lattices (3 per level); both buffers only grow.  At
+ * depth 8 that is 0.54 GB of channels and 0.23 GB of float32 lattices.
+ *
+ * r3g_recon_splat: d_points, d_normals float32 [n_points][3]; centre double [3] and side are the caller's (host) choice of box.
+ *   A point is usable when its coordinates and normal are finite and the normal is non-zero; every usable point adds its trilinear
+ *   weights to the 8 nodes of its cell (density channel) and the weights times its unit normal (three vector channels), as int64
+ *   sums in units of 2^-30.  A point outside the box counts into the nearest border cell.  d_channels_out (may be NULL): a copy
+ *   of the channels, int64 [4][n^3] (density, V0, V1, V2).  *usable_out (may be NULL): usable points.
+ *   n_points == 0 or above 2^31 - 1, depth outside [2, 8], a null buffer, a box that is not finite and positive in float32:
+ *   R3G_ERR_INVALID before any launch; no usable point: R3G_ERR_INVALID.  A failed call leaves the context without a splat.
+ *   Synchronises `stream` (one read-back).
+ * r3g_recon_solve: b = div V by central differences (0 on the boundary), then `cycles` V-cycles (in [0, 1000], else
+ *   R3G_ERR_INVALID) of geometric multigrid on the 7-point Laplacian with chi = 0 on the boundary, from chi = 0.  d_b_out and
+ *   d_chi_out, float32 [n^3], may each be NULL; the context keeps chi for r3g_recon_sample.  Without a successful splat on this
+ *   context: R3G_ERR_STATE.  A failed call leaves the context without a solution.  Synchronises `stream`.  Counters
+ *   "recon_solves", "recon_cycles".
+ * r3g_recon_sample: trilinear sample of field 0 (the density channel) or field 1 (chi) at d_points float32 [n_points][3] into
+ *   d_values_out float32 [n_points] (may be NULL).  A point takes part when its coordinates are finite and, where d_normals is
+ *   non-NULL, its normal is usable; any other point gets NaN.  *sum_out: the sum of the values that are finite, each rounded to
+ *   units of 2^-30, over *count_out points (both may be NULL): an integer sum, so its order decides nothing; it holds while
+ *   count * max|value| stays below 2^33.  Without a splat, or field 1 without a solve, on this context: R3G_ERR_STATE; a field other
+ *   than 0 or 1, n_points == 0 or above 2^31 - 1, null d_points: R3G_ERR_INVALID, before any launch.  Synchronises `stream`. */
+int r3g_recon_splat(r3g_ctx* ctx, const float* d_points, const float* d_normals, int64_t n_points, int depth, const double* centre,
+                    double side, int64_t* d_channels_out, int64_t* usable_out, void* stream);
+int r3g_recon_solve(r3g_ctx* ctx, int cycles, float* d_b_out, float* d_chi_out, void* stream);
+int r3g_recon_sample(r3g_ctx* ctx, int field, const float* d_points, const float* d_normals, int64_t n_points, float* d_values_out,
+                     int64_t* sum_out, int64_t* count_out, void* stream);
+
 /* ---- texture stage: native pieces ------------------------------------------------------------
  * SURVEY.md 8(f) rank 3.  Upstream's Hunyuan3DPaintPipeline (reference call site src/2d_to_3d_models/run.py:97, built at
  * :126-128) uses two native extensions, `custom_rasterizer` (CUDA) and `mesh_processor.cpp`, and bakes the generated views
@@ -884,6 +936,8 @@ int r3g_get_option(const char* name, int* value);
  * "meshfill_plans": successful plans of the mesh fill (r3g_meshfill_plan) so far.
  * "meshfill_rounds": pointer-doubling rounds those plans launched so far (twice the report's `rounds` each).
  * "cloud_tests": point-point distance tests made by r3g_cloud_knn so far.
+ * "orient_rounds": Boruvka rounds launched by r3g_cloud_orient so far.
+ * "recon_solves": successful r3g_recon_solve calls so far; "recon_cycles": the V-cycles they ran.
  * "geo_lnf_passes" / "geo_lnd_passes": geo decoder passes that took the folded ln_3 ("geo_ln3_fold") / ln_post + output_proj
  * ("geo_lnd_fused") epilogues.
  * Kernel-choice counters, one per form a launch can end in, bumped on the host where the launch is issued (tests read them to see
