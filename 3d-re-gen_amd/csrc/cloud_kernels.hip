@@ -86,7 +86,6 @@ std::atomic<int64_t> g_tests{0};
 }  // namespace
 
 static_assert(sizeof(Pt) == 16, "a target point is one 16-byte load");
-static_assert(r3g_grid::cells<3>(r3g_cl::kMaxRes) + 1 <= kCsrScanMax, "one block scans the tile sums");
 
 hipError_t cloud_records(char* ws, const GridCsrLayout& lay, const float* points, int64_t n, hipStream_t s) {
     R3G_HIP(csr_records_begin<3>(ws, lay, s));

@@ -9,6 +9,7 @@
 
 #include "grid_csr_kernels.h"
 #include "mesh_launch.h"
+#include "scan_kernels.h"
 
 namespace r3g {
 namespace {
@@ -92,7 +93,7 @@ hipError_t csr_fill_launch(char* ws, const GridCsrLayout& lay, int64_t nf, const
     R3G_HIP(hipMemsetAsync(counts, 0, 4 * (size_t)n1, s));
     hipLaunchKernelGGL((csr_bin<D, R, false>), dim3(grid_for(nf)), dim3(kT), 0, s, recs, nf, g, counts, (const unsigned*)nullptr,
                        (int32_t*)nullptr);
-    R3G_HIP(csr_exclusive_scan(counts, starts, n1, (unsigned*)(ws + lay.off_sums), s));
+    R3G_HIP(exclusive_scan_u32(counts, starts, n1, (unsigned*)(ws + lay.off_sums), nullptr, s));
     R3G_HIP(hipMemsetAsync(counts, 0, 4 * (size_t)n1, s));
     hipLaunchKernelGGL((csr_bin<D, R, true>), dim3(grid_for(nf)), dim3(kT), 0, s, recs, nf, g, counts, (const unsigned*)starts, pairs);
     return hipGetLastError();
@@ -122,7 +123,7 @@ hipError_t csr_fill_home_launch(char* ws, const GridCsrLayout& lay, int64_t n, c
     R3G_HIP(hipMemsetAsync(counts, 0, 4 * (size_t)n1, s));
     hipLaunchKernelGGL((csr_bin_home<D, R, false>), dim3(grid_for(n)), dim3(kT), 0, s, recs, n, g, counts, (const unsigned*)nullptr,
                        (R*)nullptr);
-    R3G_HIP(csr_exclusive_scan(counts, starts, n1, (unsigned*)(ws + lay.off_sums), s));
+    R3G_HIP(exclusive_scan_u32(counts, starts, n1, (unsigned*)(ws + lay.off_sums), nullptr, s));
     R3G_HIP(hipMemsetAsync(counts, 0, 4 * (size_t)n1, s));
     hipLaunchKernelGGL((csr_bin_home<D, R, true>), dim3(grid_for(n)), dim3(kT), 0, s, recs, n, g, counts, (const unsigned*)starts, sorted);
     return hipGetLastError();

@@ -1,6 +1,7 @@
 // grid_csr_kernels.h -- host-side interface of the device build of a grid in CSR form (grid_csr.h; internal to libr3g.so):
-// what a build leaves behind, and the exclusive scan of grid_csr_kernels.hip.  The kernels that depend on the record type
-// are templates (grid_csr_device.h), instantiated by meshdist_kernels.hip, meshinside_kernels.hip and cloud_kernels.hip.
+// what a build leaves behind, and its workspace layout (grid_csr_kernels.hip).  The kernels that depend on the record type
+// are templates (grid_csr_device.h), instantiated by meshdist_kernels.hip, meshinside_kernels.hip and cloud_kernels.hip; the
+// scan of the per-cell counts is the library's exclusive_scan_u32 (scan_kernels.h).
 #ifndef R3G_GRID_CSR_KERNELS_H
 #define R3G_GRID_CSR_KERNELS_H
 #include <hip/hip_runtime.h>
@@ -17,7 +18,7 @@ struct GridCsrLayout {
     size_t off_recs;      // the user's 48-byte record [nf]
     size_t off_counts;    // uint32 [cells + 1]: per-cell counts, then the fill cursors
     size_t off_starts;    // uint32 [cells + 1]: CSR row starts
-    size_t off_sums;      // uint32 [scan tiles]
+    size_t off_sums;      // uint32 [scan_scratch_elems(cells + 1)]: the scan's tile sums
     size_t total;
 };
 
@@ -44,14 +45,7 @@ struct GridCsrState {
     bool built = false;
 };
 
-constexpr int kCsrScanTile = 2048;                                    // elements per block of the scan
-constexpr int64_t kCsrScanMax = (int64_t)256 * 40 * kCsrScanTile;     // one block scans the tile sums: 10240 tiles at the most
-
 size_t grid_csr_workspace_bytes(int64_t nf, size_t record_bytes, int64_t cells, GridCsrLayout* lay);
-
-// starts[i] = counts[0] + ... + counts[i - 1] for i in [0, n1); sums: uint32 [ceil(n1 / kCsrScanTile)] of scratch.
-// hipErrorInvalidValue when n1 > kCsrScanMax.
-hipError_t csr_exclusive_scan(const unsigned* counts, unsigned* starts, int64_t n1, unsigned* sums, hipStream_t s);
 
 }  // namespace r3g
 #endif

@@ -13,10 +13,9 @@ namespace r3g {
 struct HierLayout {
     int nc = 0, nf = 0;
     int64_t coarse_pts = 0, fine_pts = 0, nwords = 0;   // nwords = ceil(fine_pts / 64): bit q & 63 of word q >> 6 is point q
-    int nblocks = 0;                                     // scan blocks of HIER_SCAN_WORDS words
+    int nblocks = 0;                                     // tiles of the popcount scan (scan_device.h: 2048 words each)
     size_t off_cand = 0, off_dil = 0, off_words = 0, off_prefix = 0, off_bsum = 0, off_small = 0, total = 0;
 };
-constexpr int HIER_SCAN_WORDS = 2048;   // words per block of the popcount scan (256 threads x 8)
 
 size_t hier_workspace_bytes(int nc, HierLayout* lay);
 

@@ -10,6 +10,7 @@
 
 #include "hier_kernels.h"
 #include "prof.h"
+#include "scan_device.h"
 
 namespace r3g {
 
@@ -86,79 +87,20 @@ __global__ __launch_bounds__(256) void hier_mask_kernel(const uint8_t* __restric
     }
 }
 
-// exclusive scan of one value per thread over a workgroup of NW waves; *total receives the workgroup's sum
-template <int NW>
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* lds, unsigned* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    unsigned base = 0, sum = 0;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        const unsigned t = lds[i];
-        if (i < wv) base += t;
-        sum += t;
-    }
-    __syncthreads();
-    *total = sum;
-    return base + inc - v;
-}
+// an element of the scan (scan_device.h) is the popcount of a mask word
+struct PopcLoad {
+    const unsigned long long* words;
+    __device__ unsigned operator()(int64_t w) const { return (unsigned)__popcll(words[w]); }
+};
 
-__global__ __launch_bounds__(256) void hier_popc_kernel(const unsigned long long* __restrict__ words, int64_t nwords,
-                                                        unsigned* __restrict__ bsum) {
-    __shared__ unsigned lds[4];
-    const int64_t w0 = (int64_t)blockIdx.x * HIER_SCAN_WORDS + threadIdx.x * 8;
-    unsigned c = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-        if (w0 + e < nwords) c += (unsigned)__popcll(words[w0 + e]);
-    unsigned total;
-    (void)block_exclusive_scan<4>(c, lds, &total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one workgroup: exclusive scan of the per-block sums in place, the grand total to small[0]
-__global__ __launch_bounds__(1024) void hier_scan_bsum_kernel(unsigned* __restrict__ bsum, int nblocks,
-                                                              unsigned long long* __restrict__ small) {
-    __shared__ unsigned lds[16];
-    unsigned carry = 0;
-    for (int b0 = 0; b0 < nblocks; b0 += 1024) {           // uniform trip count
-        const int b = b0 + threadIdx.x;
-        const unsigned v = b < nblocks ? bsum[b] : 0u;
-        unsigned total;
-        const unsigned ex = block_exclusive_scan<16>(v, lds, &total);
-        if (b < nblocks) bsum[b] = carry + ex;
-        carry += total;
-    }
+// scan_sums with another ending: the grand total goes to small[0] as 64 bits, and the same launch resets small[1]
+__global__ __launch_bounds__(kScanSumsThreads) void hier_scan_bsum_kernel(unsigned* __restrict__ bsum, unsigned nblocks,
+                                                                          unsigned long long* __restrict__ small) {
+    __shared__ unsigned lds[kScanSumsThreads / 64];
+    const unsigned total = scan_sums_in_place<kScanSumsThreads / 64>(bsum, nblocks, lds);
     if (threadIdx.x == 0) {
-        small[0] = carry;
+        small[0] = total;
         small[1] = 0;                                      // the unsafe-cell counter of this select
-    }
-}
-
-__global__ __launch_bounds__(256) void hier_prefix_kernel(const unsigned long long* __restrict__ words, int64_t nwords,
-                                                          const unsigned* __restrict__ bsum, unsigned* __restrict__ prefix) {
-    __shared__ unsigned lds[4];
-    const int64_t w0 = (int64_t)blockIdx.x * HIER_SCAN_WORDS + threadIdx.x * 8;
-    unsigned pc[8];
-    unsigned c = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        pc[e] = w0 + e < nwords ? (unsigned)__popcll(words[w0 + e]) : 0u;
-        c += pc[e];
-    }
-    unsigned total;
-    unsigned run = bsum[blockIdx.x] + block_exclusive_scan<4>(c, lds, &total);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        if (w0 + e < nwords) prefix[w0 + e] = run;
-        run += pc[e];
     }
 }
 
@@ -247,14 +189,14 @@ size_t hier_workspace_bytes(int nc, HierLayout* lay) {
     l.coarse_pts = (int64_t)nc * nc * nc;
     l.fine_pts = (int64_t)l.nf * l.nf * l.nf;
     l.nwords = (l.fine_pts + 63) / 64;
-    l.nblocks = (int)((l.nwords + HIER_SCAN_WORDS - 1) / HIER_SCAN_WORDS);
+    l.nblocks = (int)((l.nwords + kScanTile - 1) / kScanTile);
     size_t off = 0;
     l.off_small = off; off += 256;
     l.off_cand = off; off += align256((size_t)l.coarse_pts);
     l.off_dil = off; off += align256((size_t)l.coarse_pts);
     l.off_words = off; off += align256((size_t)l.nwords * 8);
     l.off_prefix = off; off += align256((size_t)l.nwords * 4);
-    l.off_bsum = off; off += align256((size_t)l.nblocks * 4);
+    l.off_bsum = off; off += align256(scan_scratch_elems(l.nwords) * 4);
     l.total = off;
     if (lay) *lay = l;
     return off;
@@ -275,9 +217,11 @@ hipError_t hier_select_launch(const float* coarse, double level, double band, in
     if (e) hipLaunchKernelGGL(hier_dilate_kernel, dim3(capped_blocks(lay.coarse_pts, 256)), dim3(256), 0, s, cand, lay.nc, dil);
     hipLaunchKernelGGL(hier_mask_kernel, dim3(capped_blocks(lay.nwords, 4)), dim3(256), 0, s, e ? dil : cand, lay.nc, lay.nf, 2 - e,
                        lay.fine_pts, lay.nwords, words);
-    hipLaunchKernelGGL(hier_popc_kernel, dim3(lay.nblocks), dim3(256), 0, s, words, lay.nwords, bsum);
-    hipLaunchKernelGGL(hier_scan_bsum_kernel, dim3(1), dim3(1024), 0, s, bsum, lay.nblocks, small);
-    hipLaunchKernelGGL(hier_prefix_kernel, dim3(lay.nblocks), dim3(256), 0, s, words, lay.nwords, bsum, prefix);
+    // the scan of scan_device.h over the words' popcounts, with hier_scan_bsum_kernel in the place of scan_sums
+    hipLaunchKernelGGL(scan_tile_sums<PopcLoad>, dim3(lay.nblocks), dim3(kScanThreads), 0, s, PopcLoad{words}, lay.nwords, bsum);
+    hipLaunchKernelGGL(hier_scan_bsum_kernel, dim3(1), dim3(kScanSumsThreads), 0, s, bsum, (unsigned)lay.nblocks, small);
+    hipLaunchKernelGGL(scan_tile_apply<PopcLoad>, dim3(lay.nblocks), dim3(kScanThreads), 0, s, PopcLoad{words}, lay.nwords,
+                       (const unsigned*)bsum, prefix);
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@
 #include "mesh_kernels.h"
 #include "mesh_launch.h"
 #include "prof.h"
+#include "scan_kernels.h"
 
 #pragma clang fp contract(off)
 
@@ -32,78 +33,6 @@
 
 namespace r3g {
 namespace {
-
-constexpr int kItems = 8;                 // per thread in the scan kernels
-constexpr int kTile = kT * kItems;        // 2048 elements per block
-
-// ------------------------------------------------------------------ exclusive scan of 32-bit counts (flags)
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* total) {
-    __shared__ unsigned s_wave[kT / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned n = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += n;
-    }
-    if (lane == 63) s_wave[wid] = incl;
-    __syncthreads();
-    unsigned base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kT / 64; ++w) {
-        const unsigned t = s_wave[w];
-        if (w < wid) base += t;
-        tot += t;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
-
-__global__ __launch_bounds__(kT) void scan_block_sums(const unsigned* __restrict__ in, int64_t n,
-                                                      unsigned* __restrict__ bsum) {
-    const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-    unsigned s = 0;
-#pragma unroll
-    for (int i = 0; i < kItems; ++i)
-        if (base + i < n) s += in[base + i];
-    unsigned tot;
-    (void)block_exclusive_scan(s, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// one workgroup: exclusive scan of the block sums in place; total -> *total_out
-__global__ __launch_bounds__(kT) void scan_of_sums(unsigned* __restrict__ bsum, unsigned nb,
-                                                   unsigned* __restrict__ total_out) {
-    unsigned carry = 0;
-    for (unsigned start = 0; start < nb; start += kT) {
-        const unsigned i = start + threadIdx.x;
-        const unsigned v = i < nb ? bsum[i] : 0u;
-        unsigned tot;
-        const unsigned ex = block_exclusive_scan(v, &tot);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-
-__global__ __launch_bounds__(kT) void scan_apply(const unsigned* __restrict__ in, int64_t n,
-                                                 const unsigned* __restrict__ bsum, unsigned* __restrict__ out) {
-    const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-    unsigned v[kItems], s = 0;
-#pragma unroll
-    for (int i = 0; i < kItems; ++i) {
-        v[i] = base + i < n ? in[base + i] : 0u;
-        s += v[i];
-    }
-    unsigned tot;
-    unsigned ex = bsum[blockIdx.x] + block_exclusive_scan(s, &tot);
-#pragma unroll
-    for (int i = 0; i < kItems; ++i) {
-        if (base + i < n) out[base + i] = ex;
-        ex += v[i];
-    }
-}
 
 // ------------------------------------------------------------------ union-find over face edges
 __device__ __forceinline__ int uf_find(const int* __restrict__ parent, int x) {
@@ -481,18 +410,6 @@ struct Arena {
     }
 };
 
-// out[i] = sum of in[0..i), *d_total = sum of all; scratch: block sums
-hipError_t exclusive_scan(const unsigned* in, int64_t n, unsigned* out, unsigned* bsum, unsigned* d_total,
-                          hipStream_t s) {
-    const unsigned nb = nblocks(n, kTile);
-    hipLaunchKernelGGL(scan_block_sums, dim3(nb), dim3(kT), 0, s, in, n, bsum);
-    hipLaunchKernelGGL(scan_of_sums, dim3(1), dim3(kT), 0, s, bsum, nb, d_total);
-    hipLaunchKernelGGL(scan_apply, dim3(nb), dim3(kT), 0, s, in, n, (const unsigned*)bsum, out);
-    return hipGetLastError();
-}
-
-size_t scan_scratch_elems(int64_t n) { return (size_t)nblocks(n, kTile) + 1; }
-
 }  // namespace
 
 size_t mesh_workspace_bytes(int64_t nv, int64_t nf, int64_t max_cells) {
@@ -546,9 +463,9 @@ static hipError_t compact_mesh(Arena& ar, float* verts, int64_t nv, int32_t* fac
     int32_t* fout = ar.take<int32_t>(3 * nf);
     float* vout = ar.take<float>(3 * nv);
     R3G_HIP(hipMemsetAsync(used, 0, 4 * (size_t)nv, s));
-    R3G_HIP(exclusive_scan(keep, nf, fpos, bsum, d_small + 0, s));
+    R3G_HIP(exclusive_scan_u32(keep, fpos, nf, bsum, d_small + 0, s));
     hipLaunchKernelGGL(mark_used_kernel, dim3(nblocks(nf, kT)), dim3(kT), 0, s, (const int32_t*)faces, nf, keep, used);
-    R3G_HIP(exclusive_scan(used, nv, vpos, bsum, d_small + 1, s));
+    R3G_HIP(exclusive_scan_u32(used, vpos, nv, bsum, d_small + 1, s));
     hipLaunchKernelGGL(scatter_faces_kernel, dim3(nblocks(nf, kT)), dim3(kT), 0, s, (const int32_t*)faces, nf, keep,
                        (const unsigned*)fpos, (const unsigned*)vpos, fout);
     hipLaunchKernelGGL(scatter_verts_kernel, dim3(nblocks(nv, kT)), dim3(kT), 0, s, (const float*)verts, nv,
@@ -693,14 +610,14 @@ hipError_t mesh_cluster_faces(char* ws, size_t ws_bytes, unsigned* h_small, floa
         R3G_HIP(hipMemsetAsync(occ, 0, 4 * (size_t)cells, s));
         R3G_HIP(hipMemsetAsync(table, 0xFF, 4 * (size_t)tsize, s));
         hipLaunchKernelGGL(cluster_key_kernel, dim3(nblocks(nv, kT)), dim3(kT), 0, s, (const float*)verts, nv, g, key, occ);
-        R3G_HIP(exclusive_scan(occ, cells, rank, bsum, d_small + 0, s));
+        R3G_HIP(exclusive_scan_u32(occ, rank, cells, bsum, d_small + 0, s));
         hipLaunchKernelGGL(cluster_assign_kernel, dim3(nblocks(nv, kT)), dim3(kT), 0, s, (const int*)key, nv,
                            (const unsigned*)rank, inv);
         hipLaunchKernelGGL(dedup_insert_kernel, dim3(nblocks(nf, kT)), dim3(kT), 0, s, (const int32_t*)faces, nf,
                            (const int*)inv, table, (unsigned)(tsize - 1));
         hipLaunchKernelGGL(dedup_flag_kernel, dim3(nblocks(nf, kT)), dim3(kT), 0, s, (const int32_t*)faces, nf,
                            (const int*)inv, (const int*)table, (unsigned)(tsize - 1), keep);
-        R3G_HIP(exclusive_scan(keep, nf, fpos, bsum, d_small + 1, s));
+        R3G_HIP(exclusive_scan_u32(keep, fpos, nf, bsum, d_small + 1, s));
         R3G_HIP(hipMemcpyAsync(h_small, d_small, 8, hipMemcpyDeviceToHost, s));
         R3G_HIP(hipStreamSynchronize(s));
         ncl = h_small[0];
@@ -717,7 +634,7 @@ hipError_t mesh_cluster_faces(char* ws, size_t ws_bytes, unsigned* h_small, floa
                        (const int*)inv, sums, ccnt);
     hipLaunchKernelGGL(cluster_faces_kernel, dim3(nblocks(nf, kT)), dim3(kT), 0, s, (const int32_t*)faces, nf,
                        (const int*)inv, (const unsigned*)keep, (const unsigned*)fpos, fout, occ);
-    R3G_HIP(exclusive_scan(occ, ncl, rank, bsum, d_small + 2, s));
+    R3G_HIP(exclusive_scan_u32(occ, rank, ncl, bsum, d_small + 2, s));
     hipLaunchKernelGGL(cluster_mean_kernel, dim3(nblocks(ncl, kT)), dim3(kT), 0, s, (const long long*)sums,
                        (const unsigned*)ccnt, ncl, (const unsigned*)occ, (const unsigned*)rank, vout);
     hipLaunchKernelGGL(remap_faces_kernel, dim3(nblocks(3 * nkeep, kT)), dim3(kT), 0, s, fout, 3 * nkeep,
@@ -770,7 +687,7 @@ struct HipBackend {
     }
     uint32_t scan(const uint32_t* in, int64_t n, uint32_t* out) {
         if (n <= 0) return 0;
-        note(exclusive_scan(in, n, out, bsum, d_small, s));
+        note(exclusive_scan_u32(in, out, n, bsum, d_small, s));
         note(hipMemcpyAsync(h_small, d_small, 4, hipMemcpyDeviceToHost, s));
         note(hipStreamSynchronize(s));
         return h_small[0];

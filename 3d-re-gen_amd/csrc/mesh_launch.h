@@ -1,5 +1,6 @@
-// mesh_launch.h -- what the mesh .hip files (mesh, meshdist, meshinside, meshfit, meshtopo, meshfill, grid_csr) share around a launch:
+// mesh_launch.h -- what the mesh .hip files (mesh, meshdist, meshinside, meshfit, meshtopo, meshfill) share around a launch:
 // the block size, grid sizes, the integer wave sum and the early return on a HIP error.  Internal to each translation unit.
+// The prefix sums they share live in scan_device.h.
 #ifndef R3G_MESH_LAUNCH_H
 #define R3G_MESH_LAUNCH_H
 #include <hip/hip_runtime.h>

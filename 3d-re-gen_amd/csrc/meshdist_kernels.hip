@@ -72,7 +72,6 @@ std::atomic<int64_t> g_tests{0};
 }  // namespace
 
 static_assert(sizeof(Tri) == 48, "triangle records are three 16-byte loads");
-static_assert(r3g_grid::cells<3>(r3g_md::kMaxRes) + 1 <= kCsrScanMax, "one block scans the tile sums");
 
 hipError_t meshdist_records(char* ws, const GridCsrLayout& lay, const float* verts, int64_t nv, const int32_t* faces,
                             int64_t nf, hipStream_t s) {

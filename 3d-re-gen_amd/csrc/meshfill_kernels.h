@@ -25,7 +25,7 @@ struct MeshfillLayout {
     size_t off_outc;         // int32 [V]: the slot that leaves the vertex, where nout = 1
     size_t off_tilecnt;      // uint32 [half-edge tiles + 1]: boundary half-edges per tile
     size_t off_tilestart;    // uint32 [half-edge tiles + 1]: their exclusive scan
-    size_t off_scratch;      // uint32: the tile sums of csr_exclusive_scan
+    size_t off_scratch;      // uint32: the tile sums of exclusive_scan_u32
     size_t off_bh;           // int32 [B]: the half-edge id of every slot, ascending
     size_t off_succ;         // int32 [B]
     size_t off_lead;         // int32 [B]: the leader's slot, -1 for a tangled slot

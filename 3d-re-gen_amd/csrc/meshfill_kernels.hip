@@ -1,6 +1,6 @@
 // meshfill_kernels.hip -- boundary loops of a triangle mesh and the faces that close them.
 //
-// compact (the boundary half-edges of the mate table into B slots by ascending id: tile counts, the scan of grid_csr_kernels,
+// compact (the boundary half-edges of the mate table into B slots by ascending id: tile counts, exclusive_scan_u32 of scan_kernels,
 // tile write) -> vertex pass (one 64-bit add per endpoint) -> link (the slot that leaves each vertex of nout = 1) -> succ ->
 // minimum / open by pointer doubling -> rank by Wyllie doubling -> allocate (four scans over the leaders) -> loop vertices ->
 // centroids -> emit.  Every doubling round reads the previous round's arrays and writes the other pair, so no round races;
@@ -12,9 +12,9 @@
 #pragma clang fp contract(off)
 
 #define R3G_MF_HD static __host__ __device__ __forceinline__
-#include "grid_csr_kernels.h"
 #include "mesh_launch.h"
 #include "meshfill_kernels.h"
+#include "scan_kernels.h"
 
 namespace r3g {
 namespace {
@@ -22,29 +22,6 @@ namespace {
 using r3g_mf::Small;
 
 constexpr int kItems = kFillTile / kT;      // consecutive slots per thread, so that a tile keeps its order
-
-// exclusive prefix of v over the block's threads; *total = the block's sum.  sh: 4 words; ends with a barrier (sh is free again).
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* sh, unsigned* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    unsigned off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < kT / 64; ++i) {
-        const unsigned w = sh[i];
-        off += i < wave ? w : 0u;
-        tot += w;
-    }
-    __syncthreads();
-    *total = tot;
-    return off + x - v;
-}
 
 // WRITE = false: tilecnt[tile] = boundary half-edges of the tile.  WRITE = true: bh[tilestart[tile] + ...] = their ids.
 template <bool WRITE>
@@ -61,7 +38,7 @@ __global__ __launch_bounds__(kT) void mf_compact(const int32_t* __restrict__ mat
             cnt += b;
         }
         unsigned total;
-        const unsigned off = block_excl_scan(cnt, sh, &total);
+        const unsigned off = block_exclusive_scan<kT / 64>(cnt, sh, &total);
         if (!WRITE) {
             if (threadIdx.x == 0) tilecnt[tile] = total;
         } else {
@@ -176,7 +153,7 @@ __global__ __launch_bounds__(kT) void mf_allocate(int64_t slots, int64_t tiles, 
         }
         unsigned off[4], total[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) off[k] = block_excl_scan(sum[k], sh, &total[k]);
+        for (int k = 0; k < 4; ++k) off[k] = block_exclusive_scan<kT / 64>(sum[k], sh, &total[k]);
         if (!WRITE) {
             if (threadIdx.x == 0) {
 #pragma unroll
@@ -325,7 +302,7 @@ size_t meshfill_workspace_bytes(int64_t nv, int64_t nf, int64_t boundary, Meshfi
     lay->off_outc = o, o += up(4 * V);
     lay->off_tilecnt = o, o += up(4 * ht1);
     lay->off_tilestart = o, o += up(4 * ht1);
-    lay->off_scratch = o, o += up(4 * ((ht1 > st1 ? ht1 : st1) / kCsrScanTile + 1));
+    lay->off_scratch = o, o += up(4 * scan_scratch_elems((int64_t)(ht1 > st1 ? ht1 : st1)));
     lay->off_bh = o, o += up(4 * B);
     lay->off_succ = o, o += up(4 * B);
     lay->off_lead = o, o += up(4 * B);
@@ -362,7 +339,7 @@ hipError_t meshfill_plan(char* ws, MeshfillLayout* layp, const int32_t* mate, co
     R3G_HIP(hipMemsetAsync(tilecnt + lay.he_tiles, 0, 4, s));
     hipLaunchKernelGGL(mf_compact<false>, dim3(tile_grid(lay.he_tiles)), dim3(kT), 0, s, mate, lay.n3, lay.he_tiles, tilecnt,
                        (const unsigned*)nullptr, (int32_t*)nullptr, B);
-    R3G_HIP(csr_exclusive_scan(tilecnt, tilestart, lay.he_tiles + 1, scratch, s));
+    R3G_HIP(exclusive_scan_u32(tilecnt, tilestart, lay.he_tiles + 1, scratch, nullptr, s));
     hipLaunchKernelGGL(mf_compact<true>, dim3(tile_grid(lay.he_tiles)), dim3(kT), 0, s, mate, lay.n3, lay.he_tiles, (unsigned*)nullptr,
                        (const unsigned*)tilestart, bh, B);
     hipLaunchKernelGGL(mf_vertex, dim3(gs), dim3(kT), 0, s, (const int32_t*)bh, faces, B, deg);
@@ -388,7 +365,7 @@ hipError_t meshfill_plan(char* ws, MeshfillLayout* layp, const int32_t* mate, co
     }
     hipLaunchKernelGGL(mf_allocate<false>, dim3(tile_grid(lay.slot_tiles)), dim3(kT), 0, s, B, lay.slot_tiles, (const int32_t*)lead,
                        (const int32_t*)succ, (const int32_t*)y[cur], max_loop, mode, tsum, scan, sm);
-    for (int k = 0; k < 4; ++k) R3G_HIP(csr_exclusive_scan(tsum.a[k], tsum.a[k], lay.slot_tiles + 1, scratch, s));
+    for (int k = 0; k < 4; ++k) R3G_HIP(exclusive_scan_u32(tsum.a[k], tsum.a[k], lay.slot_tiles + 1, scratch, nullptr, s));
     hipLaunchKernelGGL(mf_allocate<true>, dim3(tile_grid(lay.slot_tiles)), dim3(kT), 0, s, B, lay.slot_tiles, (const int32_t*)lead,
                        (const int32_t*)succ, (const int32_t*)y[cur], max_loop, mode, tsum, scan, sm);
     const Plan pl = plan_of(ws, lay);

@@ -67,7 +67,6 @@ std::atomic<int64_t> g_tests{0};
 }  // namespace
 
 static_assert(sizeof(Rec) == 48, "face records are three 16-byte loads");
-static_assert(r3g_grid::cells<2>(r3g_mi::kMaxRes) + 1 <= kCsrScanMax, "one block scans the tile sums");
 
 hipError_t meshinside_records(char* ws, const GridCsrLayout& lay, const float* verts, int64_t nv, const int32_t* faces,
                               int64_t nf, int axis, hipStream_t s) {
