@@ -24,6 +24,7 @@
 #include "mesh_launch.h"
 #include "prof.h"
 #include "scan_kernels.h"
+#include "uf_device.h"
 
 #pragma clang fp contract(off)
 
@@ -35,39 +36,6 @@ namespace r3g {
 namespace {
 
 // ------------------------------------------------------------------ union-find over face edges
-__device__ __forceinline__ int uf_find(const int* __restrict__ parent, int x) {
-    int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        x = p;
-        p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return x;
-}
-
-// find with path halving: a non-root slot is re-pointed at its grandparent (still an ancestor with a smaller id, so
-// concurrent finds and links stay correct; a root's slot is only ever changed by the CAS in uf_union)
-__device__ __forceinline__ int uf_find_halving(int* __restrict__ parent, int x) {
-    int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        const int gp = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void uf_union(int* __restrict__ parent, int a, int b) {
-    for (;;) {
-        a = uf_find_halving(parent, a);
-        b = uf_find_halving(parent, b);
-        if (a == b) return;
-        const int hi = a > b ? a : b, lo = a > b ? b : a;
-        // the larger root goes under the smaller one; only a root's own slot is ever CASed
-        if (atomicCAS(&parent[hi], hi, lo) == hi) return;
-    }
-}
-
 __global__ void iota_kernel(int* __restrict__ p, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = (int)i;

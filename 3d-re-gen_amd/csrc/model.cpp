@@ -1517,6 +1517,8 @@ int r3g_get_counter(const char* name, int64_t* value) {
     else if (!strcmp(name, "meshfill_rounds")) *value = meshfill_rounds_total();
     else if (!strcmp(name, "cloud_tests")) *value = cloud_tests_total();
     else if (!strcmp(name, "orient_rounds")) *value = orient_rounds_total();
+    else if (!strcmp(name, "dbscan_launches")) *value = dbscan_launches_total();
+    else if (!strcmp(name, "dbscan_tests")) *value = dbscan_tests_total();
     else if (!strcmp(name, "recon_solves")) *value = recon_solves_total();
     else if (!strcmp(name, "recon_cycles")) *value = recon_cycles_total();
     else {

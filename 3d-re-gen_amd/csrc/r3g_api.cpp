@@ -313,6 +313,9 @@ void r3g_destroy(r3g_ctx* ctx) {
     if (c->recon.channels) (void)hipFree(c->recon.channels);
     if (c->recon.levels) (void)hipFree(c->recon.levels);
     if (c->orient_ws) (void)hipFree(c->orient_ws);
+    if (c->dbscan_ws) (void)hipFree(c->dbscan_ws);
+    if (c->dbscan_ev_made)
+        for (hipEvent_t e : c->dbscan_ev) (void)hipEventDestroy(e);
     if (c->meshtopo_ws) (void)hipFree(c->meshtopo_ws);
     if (c->h_topo) (void)hipHostFree(c->h_topo);
     if (c->meshfill_ws) (void)hipFree(c->meshfill_ws);
@@ -566,6 +569,97 @@ int r3g_cloud_orient(r3g_ctx* ctx, const float* d_points, const float* d_normals
     if (report) {
         const int64_t r[r3g_or::kReport] = {(int64_t)sm.usable, (int64_t)sm.trees, (int64_t)sm.flipped, rounds, (int64_t)sm.frustrated, 0, 0, 0};
         memcpy(report, r, sizeof r);
+    }
+    return R3G_OK;
+}
+
+// ---- DBSCAN on a point cloud ---------------------------------------------------------------------------
+int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, double eps, int min_samples, int resolution, int32_t* d_label,
+                     uint32_t* d_count, int64_t* report, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    GridCsrState<3>* st = &c->cloud;
+    hipStream_t s = (hipStream_t)stream;
+    if (!(eps > 0.0) || !(eps - eps == 0.0)) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: eps must be finite and > 0");
+    if (min_samples < 1) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: min_samples must be >= 1");
+    if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: n_points outside [0, 2^31 - 1]");
+    if (resolution < 0 || resolution > r3g_cl::kMaxRes)
+        return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: resolution outside [0, %d] (0 = automatic)", r3g_cl::kMaxRes);
+    int64_t rep[r3g_db::kReport] = {0, 0, 0, 0, 0, -1, 0, 0};
+    auto done = [&]() {
+        if (report) memcpy(report, rep, sizeof rep);
+        return R3G_OK;
+    };
+    st->built = false;              // the call replaces the context's cloud
+    c->dbscan_timed = false;
+    if (n_points == 0) return done();
+    if (!d_points || !d_label) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: null buffer");
+    if (!c->dbscan_ev_made) {
+        for (hipEvent_t& e : c->dbscan_ev) {
+            hipError_t he = hipEventCreate(&e);
+            if (he != hipSuccess) return hip_fail(he, "hipEventCreate(dbscan)");
+        }
+        c->dbscan_ev_made = true;
+    }
+    DbscanLayout dl;
+    int rc = c->reserve(&c->dbscan_ws, &c->dbscan_ws_bytes, dbscan_workspace_bytes(n_points, &dl), "hipMalloc(dbscan workspace)");
+    if (rc) return rc;
+    // the automatic resolution can only fall when points are skipped: the workspace sized for all of them is enough
+    const int res_most = resolution ? resolution : r3g_db::auto_resolution_most(n_points);
+    GridCsrLayout lay;
+    const size_t need = grid_csr_workspace_bytes(n_points, sizeof(r3g_cl::Pt), r3g_grid::cells<3>(res_most), &lay);
+    if ((rc = c->reserve(&st->ws, &st->ws_bytes, need, "hipMalloc(cloud workspace)"))) return rc;
+    st->lay = lay;
+    int64_t launches = 0;
+    hipError_t e = hipEventRecord(c->dbscan_ev[0], s);
+    if (e != hipSuccess) return hip_fail(e, "hipEventRecord(dbscan)");
+    if ((e = dbscan_begin(c->dbscan_ws, dl, n_points, d_label, d_count, s)) != hipSuccess) return hip_fail(e, "dbscan_begin");
+    if ((e = cloud_records(st->ws, lay, d_points, n_points, s)) != hipSuccess) return hip_fail(e, "cloud_records");
+    launches += 2;
+    GridCsrSmall sm;
+    if ((rc = grid_small(c, st->ws, lay, "dbscan", s, &sm))) return rc;
+    const int64_t usable = n_points - (int64_t)sm.skipped;
+    if (usable <= 0) {              // nothing to cluster: every label is -1 already
+        dbscan_add_launches(launches);
+        return done();
+    }
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) lo[a] = r3g_grid::dec_float(sm.box[a]), hi[a] = r3g_grid::dec_float(sm.box[3 + a]);
+    const int res = resolution ? resolution : r3g_db::auto_resolution(lo, hi, eps, usable);
+    const r3g_cl::Grid g = r3g_grid::make_grid(lo, hi, res);
+    if ((rc = c->reserve(&st->pairs, &st->pairs_bytes, sizeof(r3g_cl::Pt) * (size_t)usable, "hipMalloc(cloud points)"))) return rc;
+    if ((e = cloud_fill(st->ws, lay, n_points, g, (r3g_cl::Pt*)st->pairs, s)) != hipSuccess) return hip_fail(e, "cloud_fill");
+    launches += 5;                  // count, the scan's three, fill
+    int run = 0;
+    e = dbscan_run(c->dbscan_ws, dl, g, (const r3g_cl::Pt*)st->pairs, (const unsigned*)(st->ws + lay.off_starts), usable, n_points, eps,
+                   (uint32_t)min_samples, d_label, d_count, c->dbscan_ev + 1, &run, s);
+    if (e != hipSuccess) return hip_fail(e, "dbscan_run");
+    launches += run;
+    static_assert(sizeof(DbscanSmall) <= 64, "the pinned read-back buffer");
+    e = hipMemcpyAsync(c->h_small, c->dbscan_ws + dl.off_small, sizeof(DbscanSmall), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);      // the caller may free its points, and a fault would surface here
+    if (e != hipSuccess) return hip_fail(e, "r3g_cloud_dbscan: read-back");
+    DbscanSmall ds;
+    memcpy(&ds, c->h_small, sizeof ds);
+    st->grid = g;
+    st->built = true;
+    c->dbscan_timed = true;
+    dbscan_add_launches(launches);
+    dbscan_add_tests((int64_t)ds.tests);
+    rep[0] = usable, rep[1] = (int64_t)ds.n_core, rep[2] = (int64_t)ds.n_border, rep[3] = usable - rep[1] - rep[2];
+    rep[4] = (int64_t)ds.n_clusters, rep[5] = r3g_db::best_label(ds.best), rep[6] = r3g_db::best_size(ds.best), rep[7] = g.res;
+    return done();
+}
+
+int r3g_cloud_dbscan_times(r3g_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan_times: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->dbscan_timed) return fail(R3G_ERR_STATE, "r3g_cloud_dbscan_times: no complete r3g_cloud_dbscan on this context");
+    for (int p = 0; p <= kDbscanPasses; ++p) {
+        float t = 0.0f;
+        hipError_t e = hipEventElapsedTime(&t, c->dbscan_ev[p], c->dbscan_ev[p + 1]);
+        if (e != hipSuccess) return hip_fail(e, "hipEventElapsedTime(dbscan)");
+        ms[p] = (double)t;
     }
     return R3G_OK;
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "cloud_kernels.h"
+#include "dbscan_kernels.h"
 #include "dmc_kernels.h"
 #include "hier_kernels.h"
 #include "kernels.h"
@@ -50,6 +51,13 @@ struct Ctx {
     // normal orientation: the rows, labels and parities of one r3g_cloud_orient (nothing is kept between calls but the buffer)
     char* orient_ws = nullptr;
     size_t orient_ws_bytes = 0;
+    // DBSCAN: the flags, roots, numbers and sizes of one r3g_cloud_dbscan (nothing is kept between calls but the buffer), and the
+    // events around the passes of the last call (made on first use; dbscan_timed: they bracket a complete run)
+    char* dbscan_ws = nullptr;
+    size_t dbscan_ws_bytes = 0;
+    hipEvent_t dbscan_ev[kDbscanPasses + 2] = {};
+    bool dbscan_ev_made = false;
+    bool dbscan_timed = false;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
     // fit h_small), made on first use

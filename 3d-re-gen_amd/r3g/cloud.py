@@ -5,7 +5,8 @@ The primitive is `knn`: for every query point the k smallest (d2, index) pairs o
 (py-qy)^2) + (pz-qz)^2 in float32, by the uniform-grid kernels of csrc/cloud_kernels.hip.  Everything else here is thin
 device-side tensor arithmetic on its output: the scores of the reference's src/evaluation/run_eval.py (`evaluate`), the
 normals that stand in front of its Poisson step (`estimate_normals`) and its cloud ICP (`icp`).  Means and sums are taken
-in float64 on the device.  CUDA tensors in and out; there is no CPU path.  `PointCloud`, `load_ply` and `save_ply` are the
+in float64 on the device.  `dbscan` (section 4m, csrc/dbscan_kernels.hip) is the second primitive: scikit-learn's DBSCAN
+labels, on which the reference's cloud cleaning rests (`filter_dbscan`, beside `filter_points_by_quantile`).  CUDA tensors in and out; there is no CPU path.  `PointCloud`, `load_ply` and `save_ply` are the
 host-side file layer (numpy) behind compat/trimesh.
 """
 import ctypes
@@ -243,6 +244,65 @@ def estimate_normals(points, k=30, orient=False, k_orient=30):
     return n.to(torch.float32)
 
 
+# ---- cleaning: DBSCAN and the reference's two filters ----------------------------------------------------------------------------
+DBSCAN_REPORT = ("n_usable", "n_core", "n_border", "n_noise", "n_clusters", "largest", "largest_size", "resolution")
+DBSCAN_PASSES = ("build", "count", "link", "border", "number")
+
+
+def dbscan(points, eps=0.05, min_samples=10, resolution=None, counts=False):
+    """sklearn.cluster.DBSCAN(eps, min_samples).fit(points).labels_ on the GPU (r3g_cloud_dbscan)
+    -> (labels int32 [N], report dict), or (labels, counts int32 [N], report) with counts=True.  q is a neighbour of p iff
+    ((dx*dx) + dy*dy) + dz*dz <= eps*eps in float64 on the float32 coordinates; counts[i] = neighbours of i, itself included;
+    clusters are numbered in ascending order of their smallest core index, a border point takes the smallest number among its
+    core neighbours, noise and points with a non-finite coordinate get -1.  report: n_usable, n_core, n_border, n_noise,
+    n_clusters, largest (most points, the lowest number on a tie, -1 without a cluster), largest_size, resolution.  The call
+    replaces the cloud of `build` on the device's shared context by the usable points (built at `resolution` cells per axis,
+    None: about eps a cell; the result does not depend on it)."""
+    p = _cloud_arg(points)
+    dev = p.device.index or 0
+    n = p.shape[0]
+    labels = torch.full((n,), -1, dtype=torch.int32, device=p.device)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=p.device) if counts else None
+    rep = (ctypes.c_int64 * 8)()
+    with ffi.device_lock(dev), torch.cuda.device(p.device):
+        ffi.check(ffi.lib().r3g_cloud_dbscan(ffi.context(dev), ctypes.c_void_p(p.data_ptr() if n else None), n, float(eps), int(min_samples),
+                                             int(resolution or 0), ctypes.c_void_p(labels.data_ptr() if n else None),
+                                             ctypes.c_void_p(cnt.data_ptr()) if counts and n else None, rep, ffi.stream_ptr()))
+    report = dict(zip(DBSCAN_REPORT, (int(v) for v in rep)))
+    return (labels, cnt, report) if counts else (labels, report)
+
+
+def dbscan_times(device=0):
+    """milliseconds of the passes of the last complete `dbscan` on the device's context (HIP events on its stream)
+    -> dict over DBSCAN_PASSES"""
+    ms = (ctypes.c_double * 5)()
+    with ffi.device_lock(device):
+        ffi.check(ffi.lib().r3g_cloud_dbscan_times(ffi.context(device), ms))
+    return dict(zip(DBSCAN_PASSES, (float(v) for v in ms)))
+
+
+def filter_dbscan(points, eps=0.05, min_samples=10):
+    """The reference's pc_utils.filter_dbscan without its trip to the host: the points of the largest DBSCAN cluster, in
+    their order; the input itself when there is no cluster (or no point)."""
+    if points.numel() == 0:
+        return points
+    labels, report = dbscan(points, eps, min_samples)
+    if report["n_clusters"] == 0:
+        return points
+    return points[labels == report["largest"]]
+
+
+def filter_points_by_quantile(points, q=0.02):
+    """The reference's pc_utils.filter_points_by_quantile: the points inside the [q, 1 - q] quantiles (torch.quantile, linear
+    interpolation) of all three axes, bounds included; the input itself when it is empty or nothing would remain."""
+    if points.numel() == 0:
+        return points
+    lower = torch.quantile(points, q, dim=0)
+    upper = torch.quantile(points, 1 - q, dim=0)
+    kept = points[((points >= lower) & (points <= upper)).all(dim=1)]
+    return points if kept.numel() == 0 else kept
+
+
 # ---- cloud ICP -------------------------------------------------------------------------------------------------------------------
 def rigid_transform(a, b):
     """metrics.py::compute_rigid_transform: the rotation R and translation t that minimise sum |R a_i + t - b_i|^2 (Kabsch,
@@ -322,6 +382,20 @@ class PointCloud:
         out = recon.trim(mesh, densities, quantile)
         out.metadata["recon"] = {k: info[k] for k in ("depth", "level", "residual", "usable")}
         return out
+
+    def dbscan(self, eps=0.05, min_samples=10, device="cuda"):
+        """`dbscan` of the vertices on the GPU -> (labels int32 [N] numpy, report dict)"""
+        p = torch.from_numpy(np.ascontiguousarray(self.vertices, np.float32)).to(device)
+        labels, report = dbscan(p, eps, min_samples)
+        return labels.cpu().numpy(), report
+
+    def largest_cluster(self, eps=0.05, min_samples=10, device="cuda"):
+        """The reference's filter_dbscan as a PointCloud: the rows of the largest DBSCAN cluster (vertices, colours and normals),
+        all rows when there is no cluster"""
+        labels, report = self.dbscan(eps, min_samples, device)
+        keep = np.ones(len(labels), bool) if report["n_clusters"] == 0 else labels == report["largest"]
+        return PointCloud(self.vertices[keep], None if self.colors is None else self.colors[keep],
+                          None if self.normals is None else self.normals[keep])
 
     def export(self, path=None, file_type="ply"):
         if file_type != "ply" or (path is not None and not str(path).lower().endswith(".ply")):

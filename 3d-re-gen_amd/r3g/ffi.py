@@ -61,6 +61,8 @@ SYMBOLS = {
     "r3g_cloud_build": (_I, [_P, _P, ctypes.c_int64, _I, ctypes.POINTER(_I), _I64P, _P]),
     "r3g_cloud_knn": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _P]),
     "r3g_cloud_orient": (_I, [_P, _P, _P, ctypes.c_int64, _I, _I, _P, _P, _I64P, _P]),
+    "r3g_cloud_dbscan": (_I, [_P, _P, ctypes.c_int64, _D, _I, _I, _P, _P, _I64P, _P]),
+    "r3g_cloud_dbscan_times": (_I, [_P, ctypes.POINTER(_D)]),
     "r3g_recon_splat": (_I, [_P, _P, _P, ctypes.c_int64, _I, _P, _D, _P, _I64P, _P]),
     "r3g_recon_solve": (_I, [_P, _I, _P, _P, _P]),
     "r3g_recon_sample": (_I, [_P, _I, _P, _P, ctypes.c_int64, _P, _I64P, _I64P, _P]),
@@ -205,7 +207,7 @@ def option(name):
 
 def counter(name):
     """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "dit_evals", "geo_q_cache_builds",
-    "geo_kv_groups", "geo_narrow_passes", "meshdist_tests", "meshinside_tests", "meshfit_steps", "meshtopo_builds", "meshtopo_rounds", "meshfill_plans", "meshfill_rounds", "cloud_tests", "orient_rounds", "recon_solves", "recon_cycles", ...: the list is in include/r3g.h)"""
+    "geo_kv_groups", "geo_narrow_passes", "meshdist_tests", "meshinside_tests", "meshfit_steps", "meshtopo_builds", "meshtopo_rounds", "meshfill_plans", "meshfill_rounds", "cloud_tests", "orient_rounds", "dbscan_launches", "dbscan_tests", "recon_solves", "recon_cycles", ...: the list is in include/r3g.h)"""
     v = ctypes.c_int64(0)
     check(lib().r3g_get_counter(name.encode(), ctypes.byref(v)))
     return int(v.value)

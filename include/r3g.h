@@ -348,6 +348,34 @@ int r3g_cloud_knn(r3g_ctx* ctx, const float* d_queries, int64_t n_queries, int k
 int r3g_cloud_orient(r3g_ctx* ctx, const float* d_points, const float* d_normals, int64_t n_points, int k, int resolution, int8_t* d_sign,
                      int32_t* d_tree, int64_t* report, void* stream);
 
+/* ---- point clouds: DBSCAN ---------------------------------------------------------------------
+ * The clustering that the reference's filter_dbscan asks of scikit-learn, with scikit-learn's labels.  A point is usable when its
+ * three coordinates are finite; an unusable point is nobody's neighbour.  q is a neighbour of p iff d2 = ((dx*dx) + dy*dy) + dz*dz
+ * <= eps*eps with every coordinate widened to float64 first, one rounding per operation, left to right, no contraction, eps*eps
+ * computed once in float64 (csrc/dbscan_core.h; tests/emu/dbscan_emu.cpp reproduces it exactly on the host).  A point is its own
+ * neighbour; equal coordinates under distinct indices are distinct neighbours.  count[i] = the neighbours of i, itself included;
+ * i is a core point iff count[i] >= min_samples.  Clusters are the connected components of the core points under the neighbour
+ * relation, numbered 0, 1, ... in ascending order of their smallest core index.  label[i]: a core point's cluster; for a
+ * non-core point with a core neighbour (a border point) the smallest cluster number among its core neighbours; otherwise -1.
+ *
+ * r3g_cloud_dbscan: d_points float32 [n_points][3] -> d_label int32 [n_points] and, where d_count is not NULL, d_count uint32
+ *   [n_points] (0 for an unusable point; without d_count a point stops counting at min_samples, which changes no label).
+ *   report (int64 [8], may be NULL): usable points, core points, border points, noise points (usable, label -1), clusters, the
+ *   largest cluster (most points, the lowest number on a tie, -1 without a cluster), its size, the resolution used.
+ *   The call REPLACES the cloud of r3g_cloud_build on this context by the usable points (r3g_cloud_knn may follow it), built at
+ *   `resolution` cells per axis; 0 = automatic: floor(longest box extent / eps), at least 1, at most 256 and at most the largest
+ *   r with r^3 <= 8 * usable.  The grid only prunes, the result does not depend on it.  The number of kernel launches does not
+ *   depend on the data (counter "dbscan_launches"; "dbscan_tests" counts the evaluations of the neighbour predicate).
+ *   eps not finite or <= 0, min_samples < 1, n_points < 0 or above 2^31 - 1, a resolution outside [0, 256], a null buffer with
+ *   n_points > 0: R3G_ERR_INVALID before any launch.  n_points == 0 and a cloud without a usable point succeed, every label -1
+ *   and the report zero but for largest = -1; they leave the context without a cloud.  Synchronises `stream`.
+ * r3g_cloud_dbscan_times: milliseconds of the last complete r3g_cloud_dbscan on this context between HIP events on its stream,
+ *   ms double [5]: grid build, count pass, link pass (with its flatten), border pass, numbering (with sizes and the largest
+ *   cluster).  Without such a call: R3G_ERR_STATE. */
+int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, double eps, int min_samples, int resolution, int32_t* d_label,
+                     uint32_t* d_count, int64_t* report, void* stream);
+int r3g_cloud_dbscan_times(r3g_ctx* ctx, double* ms);
+
 /* ---- point clouds: Poisson surface on a uniform lattice -----------------------------------------
  * Oriented points -> an implicit function chi whose level set is the surface (r3g/recon.py runs marching cubes on it).  The
  * lattice has n = 2^depth + 1 nodes per axis over the cube (centre, side), node (i0, i1, i2) stored [i0][i1][i2].  Every value is
@@ -937,6 +965,8 @@ int r3g_get_option(const char* name, int* value);
  * "meshfill_rounds": pointer-doubling rounds those plans launched so far (twice the report's `rounds` each).
  * "cloud_tests": point-point distance tests made by r3g_cloud_knn so far.
  * "orient_rounds": Boruvka rounds launched by r3g_cloud_orient so far.
+ * "dbscan_launches": kernels launched by r3g_cloud_dbscan so far (per call: a number that does not depend on the data).
+ * "dbscan_tests": evaluations of the neighbour predicate made by r3g_cloud_dbscan so far.
  * "recon_solves": successful r3g_recon_solve calls so far; "recon_cycles": the V-cycles they ran.
  * "geo_lnf_passes" / "geo_lnd_passes": geo decoder passes that took the folded ln_3 ("geo_ln3_fold") / ln_post + output_proj
  * ("geo_lnd_fused") epilogues.
