@@ -1044,8 +1044,10 @@ __global__ __launch_bounds__(NW * 64, (PIPE || NW == 8) ? 2 : 3) void attn2_kern
 // barriers between the MFMA gaps: the step's inputs are not available before the first one and its results are complete at
 // the second, so the step stays in the gap it is written in (left alone the compiler gathers the exponentials of a block
 // behind its last score MFMA again).  st: {even sum, odd sum, the pair in flight}.
+// TAIL = false (the skewed pass): step 7 leaves its own pair in flight as the other steps do, and softmax_tail packs and adds it in
+// the next gap, which step 0 of the next block leaves two exponentials wide.
 struct SoftmaxRun { float ps0, ps1, ea, eb; };
-template <int J>
+template <int J, bool TAIL = true>
 __device__ __forceinline__ void softmax_step(f32x8& half, uint32_t (&pk)[8], SoftmaxRun& st) {
     asm volatile("" : "+v"(half));   // (the half block: a pin on the two scores alone copies one of them out of the tuple)
     const float a = __builtin_amdgcn_exp2f(half[2 * (J & 3)]);
@@ -1058,13 +1060,19 @@ __device__ __forceinline__ void softmax_step(f32x8& half, uint32_t (&pk)[8], Sof
     }
     st.ea = a;
     st.eb = b;
-    if (J == 7) {
+    if (J == 7 && TAIL) {
         pk[7] = pack_bf16(a, b);
         st.ps0 += a;
         st.ps1 += b;
         asm volatile("" : "+v"(pk[7]));
     }
     asm volatile("" : "+v"(st.ps0), "+v"(st.ps1), "+v"(st.ea), "+v"(st.eb));
+}
+__device__ __forceinline__ void softmax_tail(uint32_t (&pk)[8], SoftmaxRun& st) {
+    pk[7] = pack_bf16(st.ea, st.eb);
+    st.ps0 += st.ea;
+    st.ps1 += st.eb;
+    asm volatile("" : "+v"(pk[7]), "+v"(st.ps0), "+v"(st.ps1));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1085,6 +1093,19 @@ __device__ __forceinline__ void softmax_step(f32x8& half, uint32_t (&pk)[8], Sof
 // instead of 16, which keeps 32 registers free).
 // VAR bit 2 (option "attn_async_stage"; the same bit of attn2_kernel's VAR): the K / V^T tiles' LDS-DMA is issued unseen by the compiler,
 // comment at lds_dma16_unseen.
+// VAR bit 3 (option "attn_interleave" 2, profiles/attention_skew.md): the skew of tools/ubench/attn_skeleton.hip ACROSS key blocks, in
+// steady state.  With key blocks j of 32 keys, iteration j enters with the raw scores S(q1, j), the bf16 probabilities P(q0, j) and
+// the K fragments of block j + 1 in registers and issues four groups of four MFMAs, each MFMA followed by one softmax_step:
+//     G1: QK(q0, j + 1) || softmax(q1, j) steps 0-3       reads the four V^T fragments of block j
+//     G2: PV(q0, j)     || softmax(q1, j) steps 4-7
+//     G3: QK(q1, j + 1) || softmax(q0, j + 1) steps 0-3
+//     G4: PV(q1, j)     || softmax(q0, j + 1) steps 4-7   reads the four K fragments of block j + 2
+// Every gap is filled, every fragment is read once (16 ds_read_b128 per tile) a whole group ahead of its use, and every accumulator
+// sees the clustered body's MFMAs in the clustered body's order: bit-identical.  An iteration reads K of block j + 2 BEFORE the next
+// one reads V^T of block j + 1, so no single point separates "tile t is read" from "tile t + 1 is first read"; the two-stage ring
+// still does, with one barrier per tile, once the K half of a stage runs one tile ahead of its V^T half (comment at the loop).
+// Key block 0, a masked last tile and the safe pass stay on the clustered code.
+// VAR bit 4: the safe pass is voted per aligned 128 queries instead of per workgroup, comment at the vote.
 template <int NW, int VAR = 0>
 __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_B];
@@ -1162,26 +1183,55 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
         voff[i] = ((uint32_t)row * (uint32_t)p.Lk_pad + (uint32_t)(kc * 8)) * 2u;
     }
     const uint32_t smem_lds = lds_address(smem);
+    auto piece = [&](const char* base, uint32_t lane_off, char* dst) {
+        if constexpr ((VAR & 4) != 0)       // option "attn_async_stage": comment at lds_dma16_unseen
+            lds_dma16_unseen(base, lane_off, smem_lds + (uint32_t)(dst - smem));
+        else
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + (size_t)lane_off),
+                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+    };
     auto stage = [&](int t, char* dst) {
         const char* kt = reinterpret_cast<const char*>(Kg + (int64_t)t * (KV_TILE * 64));
         const char* vt = reinterpret_cast<const char*>(Vtg + (int64_t)t * KV_TILE);
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
-            if constexpr ((VAR & 4) != 0) {     // option "attn_async_stage": comment at lds_dma16_unseen
-                lds_dma16_unseen(kt, koff[i], smem_lds + (uint32_t)(dst - smem) + (wid * PPW + i) * 1024);
-                lds_dma16_unseen(vt, voff[i], smem_lds + (uint32_t)(dst - smem) + TILE_B + (wid * PPW + i) * 1024);
-                continue;
-            }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kt + (size_t)koff[i]),
-                                             (__attribute__((address_space(3))) void*)(dst + (wid * PPW + i) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vt + (size_t)voff[i]),
-                                             (__attribute__((address_space(3))) void*)(dst + TILE_B + (wid * PPW + i) * 1024),
-                                             16, 0, 0);
+            piece(kt, koff[i], dst + (wid * PPW + i) * 1024);
+            piece(vt, voff[i], dst + TILE_B + (wid * PPW + i) * 1024);
         }
     };
+    // the two halves of a stage on their own (VAR bit 3: the K tiles run one tile ahead of the V^T tiles)
+    auto stage_k = [&](int t, char* dst) {
+        const char* kt = reinterpret_cast<const char*>(Kg + (int64_t)t * (KV_TILE * 64));
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) piece(kt, koff[i], dst + (wid * PPW + i) * 1024);
+    };
+    auto stage_v = [&](int t, char* dst) {
+        const char* vt = reinterpret_cast<const char*>(Vtg + (int64_t)t * KV_TILE);
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) piece(vt, voff[i], dst + TILE_B + (wid * PPW + i) * 1024);
+    };
     const bool pad_tail = ntiles * KV_TILE > Lk;
+    // helpers of the two interleaved bodies (VAR bits 1 and 3): the B operand of a P V MFMA from the packed probabilities, the
+    // end of a block's softmax (row sum into l_run, the sticky sum test), and the fence between two MFMA gaps
+    auto pfrag = [&](const uint32_t (&pk)[8], int ks2) {
+        union { uint32_t u[4]; bf16x8 v; } pf;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pf.u[e] = pk[4 * ks2 + e];
+        return pf.v;
+    };
+    auto finish = [&](int qb, const SoftmaxRun& ps) {
+        const float psum = ps.ps0 + ps.ps1;
+        l_run[qb] += psum;
+        sticky |= __ballot(!(psum <= PSUM_LIMIT2)) & valid_lanes[qb];
+    };
+#define R3G_GAP() __builtin_amdgcn_sched_barrier(0)
+    // VAR bit 4: whether this wave takes the safe pass's results (it stages and meets the barriers either way), comment at the vote
+    bool safe_active = true;
     auto pass = [&](auto FAST) __attribute__((always_inline)) {
     constexpr bool kFast = decltype(FAST)::value;
+    bool computes = true;
+    if constexpr (!kFast && (VAR & 16) != 0) computes = safe_active;
+    if (computes) {
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
 #pragma unroll
@@ -1189,33 +1239,23 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
         m_run[qb] = 0.f;
         l_run[qb] = 0.f;
     }
-    stage(0, smem);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    auto tile = [&](auto masked, auto first, const int t) {
+    }
+    // part: 0 the whole tile with the prefetch of the next one in front and the wait + barrier behind | the skewed pass stages for
+    // itself and runs 1 = key block 0 alone, nothing in front or behind, and 2 = the whole (masked last) tile without the prefetch
+    auto tile = [&](auto masked, auto first, const int t, auto part) {
+        constexpr int kPart = decltype(part)::value;
         const char* cur = smem + (t & 1) * STAGE_B;
+        if constexpr (kPart == 0) {
         // (a wait the compiler KNOWS, where nothing of the loop is in flight: whatever it loaded ahead of the loop -- a spilled Q fragment --
         // is then complete for it, and it puts no wait of its own behind the transfers it cannot see)
         if constexpr ((VAR & 4) != 0) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
         if (t + 1 < ntiles) stage(t + 1, smem + ((t + 1) & 1) * STAGE_B);
+        }
         if constexpr ((VAR & 2) != 0 && kFast && !decltype(masked)::value && !decltype(first)::value) {
             auto ldk = [&](int kb, int ks) { return *reinterpret_cast<const bf16x8*>(cur + (off[kb] ^ (ks << 5))); };
             auto ldv = [&](int kb, int i) {   // i: the group's MFMA, (ks2, db) = (i >> 1, i & 1)
                 return *reinterpret_cast<const bf16x8*>(cur + TILE_B + (off[i & 1] ^ ((2 * kb + (i >> 1)) << 5)));
             };
-            auto pfrag = [&](const uint32_t (&pk)[8], int ks2) {
-                union { uint32_t u[4]; bf16x8 v; } pf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pf.u[e] = pk[4 * ks2 + e];
-                return pf.v;
-            };
-            auto finish = [&](int qb, const SoftmaxRun& ps) {
-                const float psum = ps.ps0 + ps.ps1;
-                l_run[qb] += psum;
-                sticky |= __ballot(!(psum <= PSUM_LIMIT2)) & valid_lanes[qb];
-            };
-#define R3G_GAP() __builtin_amdgcn_sched_barrier(0)
             f32x16 s00, s10, s01, s11;
             uint32_t pk00[8], pk10[8], pk01[8], pk11[8];
             SoftmaxRun ps;
@@ -1268,10 +1308,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
             o[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[1], pfrag(pk11, 0), o[1][1], 0, 0, 0);
             o[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[2], pfrag(pk11, 1), o[1][0], 0, 0, 0);
             o[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ff[3], pfrag(pk11, 1), o[1][1], 0, 0, 0);
-#undef R3G_GAP
-        } else {
+        } else if (computes) {
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
+        for (int kb = 0; kb < (kPart == 1 ? 1 : 2); ++kb) {
             constexpr bool kFirst = decltype(first)::value;
             const bool first_block = kFirst && kb == 0;
             // ---- scores of 32 keys for both query blocks from one set of K fragments
@@ -1356,24 +1395,178 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
             }
         }
         }   // clustered body
+        if constexpr (kPart == 1) return;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     };
+    constexpr std::integral_constant<int, 0> whole{};
+
+    constexpr bool kSkewed = (VAR & 8) != 0 && kFast;
+    if constexpr (kSkewed) if (ntiles >= 2) {
+        // ---- the skewed fast pass.  Key blocks of 32 keys are numbered j; tile t holds blocks 2t and 2t + 1.  Block 0 runs clustered
+        // (lane maximum, stabiliser), the masked last tile too; blocks 1 .. L (L = the last unmasked block, always odd) go through
+        // the pipeline: FILL makes S(q0, 1), S(q1, 1) and P(q0, 1); ITERATION j = 1 .. L - 1 is the four groups above; DRAIN
+        // finishes block L.  Staging: K(t) / V(t) = the K / V^T half of tile t, into the halves of stage t & 1.  Wave-uniform trip
+        // counts (ntiles, pad_tail): every wave meets the same barriers.
+        auto ldk = [&](const char* st, int kb, int ks) { return *reinterpret_cast<const bf16x8*>(st + (off[kb] ^ (ks << 5))); };
+        auto ldv = [&](const char* st, int kb, int i) {   // i: the group's MFMA, (ks2, db) = (i >> 1, i & 1)
+            return *reinterpret_cast<const bf16x8*>(st + TILE_B + (off[i & 1] ^ ((2 * kb + (i >> 1)) << 5)));
+        };
+        auto landed = [&]() {     // the source's wait for every transfer in flight, then the workgroup's barrier
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if constexpr ((VAR & 4) != 0) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), known to the compiler: comment in tile()
+        };
+        char* const st0 = smem;
+        char* const st1 = smem + STAGE_B;
+        stage_k(0, st0); stage_v(0, st0); stage_k(1, st1);
+        landed();
+        stage_v(1, st1);
+        tile(std::false_type{}, std::true_type{}, 0, std::integral_constant<int, 1>{});     // block 0
+
+        f32x16 s0, s1;               // raw scores: s1 = S(q1, j) lives across iterations, s0 = S(q0, j + 1) inside one
+        uint32_t pk0[8], pk1[8];     // bf16 probabilities P(q0, .), P(q1, .)
+        bf16x8 kf[4], vf[4];         // K fragments of block j + 1 (across iterations), V^T fragments of block j
+        SoftmaxRun ps;
+        f32x8 h;
+        // FILL: scores of block 1 for both query blocks, the softmax of query block 0 in the open
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) kf[ks] = ldk(st0, 1, ks);
+        s0 = mfma_32x32x16_fresh(kf[0], qf[0][0], negm[0]);
+        s1 = mfma_32x32x16_fresh(kf[0], qf[1][0], negm[1]);
+#pragma unroll
+        for (int ks = 1; ks < 4; ++ks) {
+            s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[0][ks], s0, 0, 0, 0);
+            s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[1][ks], s1, 0, 0, 0);
+        }
+        __syncthreads();             // every wave has read K(0) (its fragments fed the MFMAs above): K(2) may replace it
+        if (2 < ntiles) stage_k(2, st0);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) kf[ks] = ldk(st1, 0, ks);
+        h = s0.lo; softmax_step<0>(h, pk0, ps); softmax_step<1>(h, pk0, ps); softmax_step<2>(h, pk0, ps); softmax_step<3>(h, pk0, ps);
+        h = s0.hi; softmax_step<4>(h, pk0, ps); softmax_step<5>(h, pk0, ps); softmax_step<6>(h, pk0, ps); softmax_step<7, false>(h, pk0, ps);
+
+        // ITERATION j: V^T of block j is block VKB of stage VS, K of block j + 2 is block KKB of stage KS (compile-time: the fragment
+        // reads differ in their immediate offsets only).  A gap = the MFMA, then its fillers, fenced on both sides: five vector
+        // instructions, six where finish() stands.  The last pair of a block's softmax stays in flight across the group boundary:
+        // softmax_tail and finish() stand in gaps 0 and 1 of the NEXT block's softmax, which are two and three instructions wide.
+        auto iteration = [&](auto VS, auto VKB, auto KS, auto KKB) {
+            const char* const vst = smem + decltype(VS)::value * STAGE_B;
+            const char* const kst = smem + decltype(KS)::value * STAGE_B;
+            constexpr int vkb = decltype(VKB)::value, kkb = decltype(KKB)::value;
+            R3G_GAP();
+            // ---- G1: QK(q0, j + 1) || softmax(q1, j) steps 0-3 (and the end of softmax(q0, j)); reads V^T of block j
+            s0 = mfma_32x32x16_fresh(kf[0], qf[0][0], negm[0]); R3G_GAP();
+            softmax_tail(pk0, ps); h = s1.lo; softmax_step<0>(h, pk1, ps); vf[0] = ldv(vst, vkb, 0); R3G_GAP();
+            s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[1], qf[0][1], s0, 0, 0, 0); R3G_GAP();
+            finish(0, ps); softmax_step<1>(h, pk1, ps); vf[1] = ldv(vst, vkb, 1); R3G_GAP();
+            s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[2], qf[0][2], s0, 0, 0, 0); R3G_GAP();
+            softmax_step<2>(h, pk1, ps); vf[2] = ldv(vst, vkb, 2); R3G_GAP();
+            s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[3], qf[0][3], s0, 0, 0, 0); R3G_GAP();
+            softmax_step<3>(h, pk1, ps); vf[3] = ldv(vst, vkb, 3); R3G_GAP();
+            // ---- G2: PV(q0, j) || softmax(q1, j) steps 4-7
+            o[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[0], pfrag(pk0, 0), o[0][0], 0, 0, 0); R3G_GAP();
+            h = s1.hi; softmax_step<4>(h, pk1, ps); R3G_GAP();
+            o[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[1], pfrag(pk0, 0), o[0][1], 0, 0, 0); R3G_GAP();
+            softmax_step<5>(h, pk1, ps); R3G_GAP();
+            o[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[2], pfrag(pk0, 1), o[0][0], 0, 0, 0); R3G_GAP();
+            softmax_step<6>(h, pk1, ps); R3G_GAP();
+            o[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[3], pfrag(pk0, 1), o[0][1], 0, 0, 0); R3G_GAP();
+            softmax_step<7, false>(h, pk1, ps); R3G_GAP();
+            // ---- G3: QK(q1, j + 1) || softmax(q0, j + 1) steps 0-3 (and the end of softmax(q1, j))
+            s1 = mfma_32x32x16_fresh(kf[0], qf[1][0], negm[1]); R3G_GAP();
+            softmax_tail(pk1, ps); h = s0.lo; softmax_step<0>(h, pk0, ps); R3G_GAP();
+            s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[1], qf[1][1], s1, 0, 0, 0); R3G_GAP();
+            finish(1, ps); softmax_step<1>(h, pk0, ps); R3G_GAP();
+            s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[2], qf[1][2], s1, 0, 0, 0); R3G_GAP();
+            softmax_step<2>(h, pk0, ps); R3G_GAP();
+            s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[3], qf[1][3], s1, 0, 0, 0); R3G_GAP();
+            softmax_step<3>(h, pk0, ps); R3G_GAP();
+            // ---- G4: PV(q1, j) || softmax(q0, j + 1) steps 4-7; reads K of block j + 2
+            o[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[0], pfrag(pk1, 0), o[1][0], 0, 0, 0); R3G_GAP();
+            h = s0.hi; softmax_step<4>(h, pk0, ps); kf[0] = ldk(kst, kkb, 0); R3G_GAP();
+            o[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[1], pfrag(pk1, 0), o[1][1], 0, 0, 0); R3G_GAP();
+            softmax_step<5>(h, pk0, ps); kf[1] = ldk(kst, kkb, 1); R3G_GAP();
+            o[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[2], pfrag(pk1, 1), o[1][0], 0, 0, 0); R3G_GAP();
+            softmax_step<6>(h, pk0, ps); kf[2] = ldk(kst, kkb, 2); R3G_GAP();
+            o[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[3], pfrag(pk1, 1), o[1][1], 0, 0, 0); R3G_GAP();
+            softmax_step<7, false>(h, pk0, ps); kf[3] = ldk(kst, kkb, 3); R3G_GAP();
+        };
+        // One trip = iterations 2T + 1 and 2T + 2 with the tile's one barrier between them.  At that barrier every wave has read
+        // V(T) (block 2T + 1 in G1 just now) and K(T + 1) (block 2T + 3 in G4 just now; the barrier's own lgkmcnt(0) completes the
+        // reads), so V(T + 2) and K(T + 3) are issued into their places; what the wait in front of it retired, V(T + 1) and K(T + 2),
+        // was issued one trip earlier and is first read behind it, by iteration 2T + 2.  The K tiles run one tile ahead of the V^T
+        // tiles because an iteration reads K of block j + 2 before the next one reads V^T of block j + 1.  The last trip's K read
+        // goes past block L: into a landed or stale tile, and nothing uses it.  P = T & 1 is compile-time: the loop takes two trips.
+        auto trip = [&](auto P, const int T) {
+            constexpr std::integral_constant<int, decltype(P)::value> a{};         // the stage of tiles T and T + 2
+            constexpr std::integral_constant<int, 1 - decltype(P)::value> b{};     // the stage of tiles T + 1 and T + 3
+            constexpr std::integral_constant<int, 0> kb0{};
+            constexpr std::integral_constant<int, 1> kb1{};
+            iteration(a, kb1, b, kb1);
+            landed();
+            if (T + 3 < ntiles) stage_k(T + 3, smem + b.value * STAGE_B);
+            if (T + 2 < ntiles) stage_v(T + 2, smem + a.value * STAGE_B);
+            iteration(b, kb0, a, kb0);
+        };
+        const int ntrips = pad_tail ? ntiles - 2 : ntiles - 1;
+        int T = 0;
+        for (; T + 2 <= ntrips; T += 2) {
+            trip(std::integral_constant<int, 0>{}, T);
+            trip(std::integral_constant<int, 1>{}, T + 1);
+        }
+        if (T < ntrips) trip(std::integral_constant<int, 0>{}, T);
+        // DRAIN: the end of softmax(q0, L), the softmax of query block 1 in the open, P V of block L for both query blocks
+        {
+            const char* sl = smem + (ntrips & 1) * STAGE_B;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) vf[i] = ldv(sl, 1, i);
+            softmax_tail(pk0, ps);
+            finish(0, ps);
+            h = s1.lo; softmax_step<0>(h, pk1, ps); softmax_step<1>(h, pk1, ps); softmax_step<2>(h, pk1, ps); softmax_step<3>(h, pk1, ps);
+            h = s1.hi; softmax_step<4>(h, pk1, ps); softmax_step<5>(h, pk1, ps); softmax_step<6>(h, pk1, ps); softmax_step<7>(h, pk1, ps);
+            finish(1, ps);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                o[0][i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[i], pfrag(pk0, i >> 1), o[0][i & 1], 0, 0, 0);
+                o[1][i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[i], pfrag(pk1, i >> 1), o[1][i & 1], 0, 0, 0);
+            }
+        }
+        if (pad_tail) {     // K(ntiles - 1) and V(ntiles - 1) are in flight or landed: wait, then the masked tile as it always ran
+            landed();
+            tile(std::true_type{}, std::false_type{}, ntiles - 1, std::integral_constant<int, 2>{});
+        }
+        return;
+    }
+
+    stage(0, smem);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     if (ntiles == 1) {
-        if (pad_tail) tile(std::true_type{}, std::true_type{}, 0);
-        else tile(std::false_type{}, std::true_type{}, 0);
-    } else {
-        tile(std::false_type{}, std::true_type{}, 0);
-        for (int t = 1; t < ntiles - 1; ++t) tile(std::false_type{}, std::false_type{}, t);
-        if (pad_tail) tile(std::true_type{}, std::false_type{}, ntiles - 1);
-        else tile(std::false_type{}, std::false_type{}, ntiles - 1);
+        if (pad_tail) tile(std::true_type{}, std::true_type{}, 0, whole);
+        else tile(std::false_type{}, std::true_type{}, 0, whole);
+    } else if constexpr (!kSkewed) {
+        tile(std::false_type{}, std::true_type{}, 0, whole);
+        for (int t = 1; t < ntiles - 1; ++t) tile(std::false_type{}, std::false_type{}, t, whole);
+        if (pad_tail) tile(std::true_type{}, std::false_type{}, ntiles - 1, whole);
+        else tile(std::false_type{}, std::false_type{}, ntiles - 1, whole);
     }
     };   // pass
     if constexpr ((VAR & 1) != 0) {
         pass(std::true_type{});
         // (the last tile's closing barrier has passed: every wave is done with the LDS tiles; the vote is workgroup-uniform
         // because all four waves stage the tiles of the second pass and meet at its barriers)
-        if (__syncthreads_or(sticky != 0)) pass(std::false_type{});
+        if constexpr ((VAR & 16) != 0) {
+            // VAR bit 4: the vote per aligned 128 queries -- the workgroup of the 32-query kernel -- for launches that generation 7
+            // sends here instead of there: the waves of a half that set no flag keep their fast pass, as that kernel's workgroup
+            // would, and every output keeps generation 2's bits (where the two passes round P at different scales it matters which
+            // queries ran again).  Both votes and the whole second pass are workgroup-uniform.
+            const int lo = __syncthreads_or(sticky != 0 && wid < NW / 2), hi = __syncthreads_or(sticky != 0 && wid >= NW / 2);
+            if (lo | hi) {
+                safe_active = __builtin_amdgcn_readfirstlane(wid < NW / 2 ? lo : hi) != 0;
+                pass(std::false_type{});
+            }
+        } else if (__syncthreads_or(sticky != 0)) pass(std::false_type{});
     } else {
         pass(std::false_type{});
     }
@@ -1402,6 +1595,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs p) {
             }
     }
 }
+#undef R3G_GAP
 
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1683,8 +1877,11 @@ void attn_set_pipelined(bool on) { g_attn_pipelined = on; }
 static int g_attn_gen = 7;
 static int g_attn_variant = 1;     // option "attn_variant" (round 6): 1 = fast pass without a maximum + sticky sum test (default) | 0 = rounds 2-5 (generations 2 / 6 / 7)
 void attn_set_variant(int v) { if (v >= 0 && v <= 1) g_attn_variant = v; }
-static int g_attn_interleave = 0;  // option "attn_interleave" (opt-in: measured 2-3 % slower, profiles/attention_interleave.md): the 64-query kernel's fast pass with the softmax inside its MFMA gaps (attn3_kernel VAR bit 1); 0 = clustered
-void attn_set_interleave(int v) { g_attn_interleave = v != 0; }
+// option "attn_interleave": where the 64-query kernel's fast pass puts its softmax.  0 = automatic (attn3_body) | 1 = inside the MFMA gaps of
+// one key tile (attn3_kernel VAR bit 1; measured 2-3 % slower, profiles/attention_interleave.md) | 2 = skewed across key blocks in steady
+// state (VAR bit 3, profiles/attention_skew.md) | 3 = clustered.  Every value computes the same bits.
+static int g_attn_interleave = 0;
+void attn_set_interleave(int v) { if (v >= 0 && v <= 3) g_attn_interleave = v; }
 static int g_attn_async_stage = 1; // option "attn_async_stage": the variant-1 kernels issue their LDS-DMA unseen by the compiler's wait counts (VAR bit 2); 0 = through the builtin
 void attn_set_async_stage(int v) { g_attn_async_stage = v != 0; }
 // generation 7 takes the 64-query-per-wave kernel where its 256-query workgroups make at least four full rounds of the
@@ -1717,6 +1914,22 @@ bool attn_get_option(const char* name, int* value) {
 // reject a pre-scaled Q: producers must then leave q plain)
 float attn_q_scale(float scale) { return (g_attn_gen >= 2 && !g_attn_pipelined) ? scale * 1.4426950408889634f : 1.0f; }
 
+// The launch classes on which the skewed body of the 64-query kernel won the pipeline A/B (profiles/attention_skew.md), in work items
+// of 256 queries: the geo decoder's passes (8 192 and 4 160 work items: what generation 7 sends to this kernel by default), and the
+// DiT's ragged launches of three and four objects (1 488 and 1 984; two objects, 992, were not measured).
+constexpr int kSkewMinItems = 2048, kSkewMinItemsRagged = 1024;
+static bool attn3_skew_pays(const AttnArgs& p, int items) { return items >= kSkewMinItems || (p.ragged && items >= kSkewMinItemsRagged); }
+// attn3_kernel's VAR bits 1 and 3 for a launch of `items` work items: which body the unmasked middle of the fast pass runs
+// ("attn_interleave"; automatic = skewed where that was measured faster, clustered for whatever else is sent to this kernel)
+static int attn3_body(const AttnArgs& p, int items) {
+    switch (g_attn_interleave) {
+        case 0: return attn3_skew_pays(p, items) ? 8 : 0;
+        case 1: return 2;
+        case 2: return 8;
+        default: return 0;
+    }
+}
+
 hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
     if (p.ragged) {
         if (p.B < 1 || p.B > kAttnMaxEntries) return hipErrorInvalidValue;
@@ -1746,7 +1959,15 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
             return n * p.H;
         };
         int gen = g_attn_gen;
-        if (gen == 7) gen = (g_attn_glds && count(256) >= g_wide6_min_items) ? 6 : 2;
+        bool moved = false;     // a launch that only the skewed body brings to the 64-query kernel: it keeps generation 2's safe-pass vote (VAR bit 4)
+        if (gen == 7) {
+            // (the second term: with its skewed body the 64-query kernel is the faster one on the DiT's larger ragged launches too;
+            // it holds while "attn_interleave" is automatic, so that forcing a body does not move a launch to another kernel)
+            const int wide_items = count(256);
+            const bool wide = wide_items >= g_wide6_min_items;
+            moved = !wide && p.ragged && g_attn_interleave == 0 && g_attn_variant == 1 && wide_items >= kSkewMinItemsRagged;
+            gen = (g_attn_glds && (wide || moved)) ? 6 : 2;
+        }
         const int qtile = (g_attn_glds && gen == 9) ? 384 : (g_attn_glds && gen >= 4) ? 256 : 128;
         const int items = count(qtile);
         if (!g_attn_glds) launch_count(LC_ATTN_REGISTER_STAGED);
@@ -1802,7 +2023,11 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
         else if (gen == 5) hipLaunchKernelGGL((attn2_kernel<true, false, 8>), dim3(items), dim3(512), 0, s, p);
         else if (gen == 6) {
             if (g_attn_variant == 1) {
-                switch ((g_attn_interleave ? 2 : 0) | (g_attn_async_stage ? 4 : 0)) {
+                switch (attn3_body(p, items) | (g_attn_async_stage ? 4 : 0) | (moved && g_attn_glds ? 16 : 0)) {
+                    case 28: hipLaunchKernelGGL((attn3_kernel<4, 29>), dim3(items), dim3(256), 0, s, p); break;
+                    case 24: hipLaunchKernelGGL((attn3_kernel<4, 25>), dim3(items), dim3(256), 0, s, p); break;
+                    case 12: hipLaunchKernelGGL((attn3_kernel<4, 13>), dim3(items), dim3(256), 0, s, p); break;
+                    case 8: hipLaunchKernelGGL((attn3_kernel<4, 9>), dim3(items), dim3(256), 0, s, p); break;
                     case 6: hipLaunchKernelGGL((attn3_kernel<4, 7>), dim3(items), dim3(256), 0, s, p); break;
                     case 4: hipLaunchKernelGGL((attn3_kernel<4, 5>), dim3(items), dim3(256), 0, s, p); break;
                     case 2: hipLaunchKernelGGL((attn3_kernel<4, 3>), dim3(items), dim3(256), 0, s, p); break;

@@ -146,7 +146,7 @@ void gemm_set_glds(bool on);  // staging path: LDS-DMA (default) or register-sta
 void attn_set_glds(bool on);
 void attn_set_ablate(int mask);   // timing-only ablation builds of the attention kernel (tools/bench_attn.py)
 void attn_set_variant(int v);       // round 6: 1 (default) fast pass with the re-stabilise test on the sum of the exponentials | 0 rounds 2-5 (generations 2 / 6 / 7)
-void attn_set_interleave(int v);    // 1: the 64-query kernel's fast pass interleaves its softmax with its MFMAs (opt-in, measured slower) | 0 (default): clustered
+void attn_set_interleave(int v);    // the 64-query kernel's fast pass: 0 (default) automatic | 1 softmax inside the MFMA gaps of one key tile (measured slower) | 2 skewed across key blocks in steady state | 3 clustered
 void attn_set_async_stage(int v);   // 1 (default): the variant-1 kernels issue their LDS-DMA from inline asm, unseen by the compiler's wait counts | 0: through the builtin
 void attn_set_pipelined(bool on);  // software-pipelined attention kernel (off by default: slower) vs the plain one
 void gemm_set_config(int waves);   // tile kernel: 0 automatic | 4 | 8 | 9 | 10 | 11 | 12 | 13 | 16 | 32 (include/r3g.h)

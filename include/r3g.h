@@ -881,7 +881,7 @@ int r3g_prof_read_bytes(double* bytes, int n);
  * rasterised tile order (consecutive steps touch neighbouring A rows) -- geo c_fc 1 109 -> 1 045 us, L2 <-> fabric bytes unchanged; bit-identical | 0: rounds 2-4's walk), "gemm_persistent_resid" (0 | bit 0: the fp32, bit 1: the bf16 read-modify-write epilogue on the persistent form as well), "gemm_num_cu" (CUs the tile rules assume, default 256), "gemm_auto_rule" (2: the current
  * tile-choice rule | 1: round 2's | 0: round 1's first version), "attn_generation" (7 default: 6 where its
  * 256-query workgroups make four rounds of the device, otherwise 2 | 2 = four waves of 32 queries | 6 = four waves of 64
- * queries, bit-identical to 2 | 1 = the first-round kernel | 3, 4, 5 = pipelined / 8-wave variants), "attn_wide_min" (2048: work items of 256 queries from which attn_generation 7 takes generation 6), "ln_rows" (0 automatic | 1 | 4 rows per wave in the
+ * queries, bit-identical to 2 | 1 = the first-round kernel | 3, 4, 5 = pipelined / 8-wave variants), "attn_wide_min" (2048: work items of 256 queries from which attn_generation 7 takes generation 6; while "attn_interleave" is automatic and "attn_variant" 1, ragged launches -- the DiT's joint attention -- take it from 1024 on whatever this value, because the skewed body makes it the faster kernel there; such a launch votes on its safe pass per 128 queries as generation 2 does and keeps generation 2's bits, profiles/attention_skew.md), "ln_rows" (0 automatic | 1 | 4 rows per wave in the
  * LayerNorm / ln_dot row kernels), "ln_rows4_min" (65536: launches of at least this many rows take 4 rows per wave under the automatic rule), "ln_fixed" (1: their instantiations with a compile-time row length for C = 1024 / 1536), "ln_modes" (1, round 6: for C = 1024 the affine-only and the modulation-only launches take instantiations with that decided at compile time -- bit-identical | 0: the generic kernel), "attn_pipelined" (0 default | 1: the software-pipelined form of the first-round kernel, other rounding points inside the softmax like
  * attn_generation 1), "attn_ablate"
  * (timing-only masks, results are garbage), "floater_by_vertex" (0), "mc_rows" (4 | 8 | 16 | 32 node rows per wave in the marching-cubes row
@@ -909,9 +909,13 @@ int r3g_prof_read_bytes(double* bytes, int n);
  * the sum of a lane's 16 exponentials against 2^16 into a sticky flag; a workgroup whose valid queries set it runs its query tile
  * again with variant 0's body | 0 = rounds 2-5.  Bit-identical to variant 0 unless variant 0 would have moved its stabiliser where
  * the fast pass does not: then equal within the bf16 rounding of P),
- * "attn_interleave" (0 default | 1, opt-in: where "attn_variant" 1 runs the 64-query-per-wave kernel, the unmasked key tiles of its fast
- * pass issue the softmax of one score block between the MFMAs of another instead of behind them; bit-identical either way and
- * measured 2-3 % slower in this form, profiles/attention_interleave.md),
+ * "attn_interleave" (where "attn_variant" 1 runs the 64-query-per-wave kernel, the order in which the unmasked key blocks of its fast
+ * pass issue their softmax; every value computes the same bits.  0 default: automatic -- the form the pipeline A/B of
+ * profiles/attention_skew.md found faster for the launch's class: the skewed one (value 2) for launches of at least 2048 work items
+ * of 256 queries and ragged launches of at least 1024, the clustered one (value 3) for the rest | 1: the softmax of one
+ * score block between the MFMAs of another INSIDE a key tile, measured 2-3 % slower, profiles/attention_interleave.md | 2: the same
+ * skew ACROSS key blocks in steady state, every MFMA gap filled, the K half of the staging ring one tile ahead of the V^T half,
+ * profiles/attention_skew.md | 3: clustered, the softmax behind the score MFMAs; other values are ignored),
  * "attn_async_stage" (1 default | 0: the "attn_variant" 1 kernels issue the LDS-DMA of the next K / V^T tile through the compiler's
  * builtin, which makes it wait for the transfer in front of the current tile's first fragment read instead of at the tile's end;
  * bit-identical either way, profiles/attention_interleave.md),
