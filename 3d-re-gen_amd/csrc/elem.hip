@@ -26,6 +26,8 @@ __device__ __forceinline__ uint16_t f2bf(float f) {  // v_cvt_pk_bf16_f32, round
 __device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
 // wave_sum: csrc/wave_sum.h (round 6: the xor butterfly on DPP / permlane swaps instead of six ds_bpermute round trips; same bits)
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
+// floor of the per-row e4m3 scale (quant_fp8_rows_kernel, the e4m3 output of layernorm_kernel): the smallest normal fp32, 2^-126
+constexpr float kFp8ScaleFloor = 1.17549435e-38f;
 
 // ---------------------------------------------------------------- LayerNorm (+affine) (+adaLN modulate) -> bf16
 constexpr int LN_MAX_V4 = 8;  // up to C = 64*4*8 = 2048
@@ -175,10 +177,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
                 *reinterpret_cast<uint2*>(y + c) = pk;
             }
         if (to_fp8) {
-            // e4m3 operand of an fp8 GEMM: q = round(o / scale), scale = amax / 448 (one per row: the row is all here)
+            // e4m3 operand of an fp8 GEMM: q = round(o / scale), scale = amax / 448 (one per row: the row is all here), floored as
+            // in quant_fp8_rows_kernel
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));
-            const float qs = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+            const float qs = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), kFp8ScaleFloor) : 1.0f;
             const float inv = 1.0f / qs;
             if (lane == 0) p.y_scale[row] = qs;
             uint8_t* y8 = p.y8 + (int64_t)row * p.ldy8;
@@ -1000,7 +1003,12 @@ hipError_t ln_dot_launch(const float* x, int64_t ldx, int rows, int C, int do_ln
 
 // bf16 [rows][K] -> fp8 e4m3 (OCP) [rows][K] with one fp32 scale per row: q = round(x / scale), scale = amax / 448.
 // One wave per row, 8 elements per lane and step (K % 8 == 0): one pass for the maximum, one for the conversion (the row
-// stays in L2 between them).  v_cvt_pk_fp8_f32 saturates and rounds to nearest even.
+// stays in L2 between them).  v_cvt_pk_fp8_f32 rounds to nearest even; it does NOT saturate (a value that rounds past 448 becomes
+// the NaN code), which cannot happen here: |x / scale| <= 448 (1 + 3 * 2^-24) after the three roundings of scale, 1 / scale and the
+// product, far below the midpoint 464.
+// The scale is floored at the smallest normal fp32 (kFp8ScaleFloor): below amax = 448 * 2^-128 the quotient amax / 448 is a
+// subnormal whose reciprocal is +inf, which turned every zero of such a row into 0 * inf = NaN (code 0x7F).  With the floor
+// 1 / scale <= 2^126 and |x / scale| < 448 for every finite row; rows with amax >= 448 * 2^-126 keep their bits.
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const uint16_t* __restrict__ x, int64_t ldx, int rows, int K,
                                                              uint8_t* __restrict__ q, int64_t ldq, float* __restrict__ scale) {
     const int lane = threadIdx.x & 63;
@@ -1019,7 +1027,7 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const uint16_t* __r
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));
-    const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    const float sc = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), kFp8ScaleFloor) : 1.0f;
     const float inv = 1.0f / sc;
     if (lane == 0) scale[row] = sc;
     uint8_t* qr = q + (int64_t)row * ldq;

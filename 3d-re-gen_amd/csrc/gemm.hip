@@ -437,7 +437,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[4]
             if (p.bias) bj = *reinterpret_cast<const f32x4*>(p.bias + (n < p.N ? n : p.N - 4));
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
-                const f32x4 v = gelu_erf4<false>(acc[j][i] + bj) * inv;
+                f32x4 v = gelu_erf4<false>(acc[j][i] + bj) * inv;
+                // v_cvt_pk_fp8_f32 does not saturate: a value that rounds past 448 comes back as the NaN code 0x7F
+                // (tests/test_fp8_edges_gpu.py), and one NaN in the hidden poisons a whole row of the GEMM that follows.
+                // Clamp here; the comparison is false for a NaN, which stays one.
+#pragma unroll
+                for (int c = 0; c < 4; ++c) v[c] = __builtin_fabsf(v[c]) > 448.f ? __builtin_copysignf(448.f, v[c]) : v[c];
                 int w = 0;
                 w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], w, false);
                 w = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
@@ -1688,6 +1693,7 @@ hipError_t launch_gemm8_fp8(const GemmArgs& p, const float* scale_a, const float
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     GemmArgs none{};
+    launch_count(LC_GEMM_FP8);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, s, p, none, scale_a, scale_w);
     return hipGetLastError();
 }
@@ -2339,7 +2345,7 @@ std::atomic<int64_t> g_launch_counters[LC_COUNT];
 const char* launch_counter_name(int which) {
     static const char* const names[LC_COUNT] = {
         "gemm_w4_128", "gemm_w8_128", "gemm_w16_256", "gemm_two_stage_256", "gemm_256x128", "gemm_phased", "gemm_phased_persistent",
-        "gemm_mixed", "gemm_splitk2", "gemm_splitk128", "gemm_deep_ring", "gemm_conv_implicit", "gemm_register_staged",
+        "gemm_mixed", "gemm_splitk2", "gemm_splitk128", "gemm_deep_ring", "gemm_conv_implicit", "gemm_register_staged", "gemm_fp8",
         "attn_gen1", "attn_pipelined", "attn_gen2", "attn_gen3", "attn_gen4", "attn_gen5", "attn_gen6", "attn_gen9", "attn_register_staged",
         "ln_rows1", "ln_rows4", "ln_fixed_count", "ln_mode_inst", "mc_rows4", "mc_rows8", "mc_rows16", "mc_rows32", "mc_deferred_rows"};
     return which >= 0 && which < LC_COUNT ? names[which] : nullptr;
@@ -2600,6 +2606,8 @@ hipError_t gemm_launch_qkv_mlp(const GemmArgs& pq_in, const GemmArgs& pm_in, hip
 // FP8 operands: A8 [M][K] and W8 [N][K] bytes (e4m3), one fp32 scale per row of each.  K % 256 == 0, lda / ldw in bytes.
 hipError_t gemm_fp8_launch(const GemmArgs& p_in, const float* scale_a, const float* scale_w, hipStream_t s) {
     GemmArgs p = p_in;
+    if (p.M < 0 || p.N < 0) return hipErrorInvalidValue;
+    if (p.M == 0 || p.N == 0) return hipSuccess;     // a grid of no workgroups is a launch error
     if (p.K % 256 || p.K < 256 || (p.lda & 15) || (p.ldw & 15) || (p.N & 3) || !scale_a || !scale_w) return hipErrorInvalidValue;
     if ((int64_t)p.M * p.lda >= (1ll << 32) || (int64_t)p.N * p.ldw >= (1ll << 32)) return hipErrorInvalidValue;   // 32-bit staging offsets
     p.batch = 1;

@@ -24,6 +24,7 @@ enum LaunchCounter {
     LC_GEMM_DEEP_RING,         // deep-ring 256 x 256 x 32 kernel ("gemm_waves" 32)
     LC_GEMM_CONV_IMPLICIT,     // implicit-GEMM 3 x 3 convolution
     LC_GEMM_REGISTER_STAGED,   // any of the launch_cfg forms with register staging instead of LDS-DMA
+    LC_GEMM_FP8,               // fp8 (e4m3 operands) form of the phased kernel, one tile per workgroup
     LC_ATTN_GEN1,              // first-round attention kernel
     LC_ATTN_PIPELINED,         // ... its software-pipelined form ("attn_pipelined")
     LC_ATTN_GEN2, LC_ATTN_GEN3, LC_ATTN_GEN4, LC_ATTN_GEN5, LC_ATTN_GEN6, LC_ATTN_GEN9,

@@ -1677,7 +1677,7 @@ int r3g_op_gemm(const uint16_t* d_a, int64_t lda, const uint16_t* d_w, int64_t l
     const bool f32_out = epilogue == EPI_RESID_F32 || epilogue == EPI_F32;
     const bool b16_out = epilogue == EPI_BF16 || epilogue == EPI_BF16_GELU_TANH || epilogue == EPI_BF16_GELU_ERF ||
                          epilogue == EPI_RESID_BF16 || epilogue == EPI_RESID_F16;
-    if (!f32_out && !b16_out)     // 5 and 9-11 need operands this entry point cannot carry, 7 belongs to r3g_op_gemm_fp8
+    if (!f32_out && !b16_out)     // 5 and 9-11 need operands this entry point cannot carry, 7 belongs to r3g_op_gemm_fp8_e4m3
         return fail(R3G_ERR_INVALID, "r3g_op_gemm: epilogue %d is not one of 0, 1, 2, 3, 4, 6, 8", epilogue);
     if (m_ < 0 || n_ < 0 || k_ <= 0 || k_ % 64 || (n_ & 3)) return fail(R3G_ERR_INVALID, "r3g_op_gemm: needs k %% 64 == 0, n %% 4 == 0");
     if (m_ > 0 && n_ > 0) {
@@ -1723,16 +1723,59 @@ int r3g_op_quant_fp8(const uint16_t* d_x, int64_t ldx, int rows, int k_, uint8_t
     return R3G_OK;
 }
 
+// The contract of include/r3g.h for both fp8 entry points, checked here and not in gemm_fp8_launch (the model's own launches meet it
+// by construction).  c_elem: bytes per element of C; ldc in elements.  *launch = false: m == 0 or n == 0, nothing to do.
+static int op_gemm_fp8_args(const char* who, const uint8_t* d_a8, int64_t lda, const float* d_scale_a, const uint8_t* d_w8, int64_t ldw,
+                            const float* d_scale_w, const float* d_bias, const void* d_c, int64_t ldc, int c_elem, const float* d_gate,
+                            int m_, int n_, int k_, bool* launch) {
+    *launch = false;
+    if (m_ < 0 || n_ < 0 || k_ < 256 || k_ % 256 || (n_ & 3)) return fail(R3G_ERR_INVALID, "%s: needs m, n >= 0, k >= 256, k %% 256 == 0, n %% 4 == 0", who);
+    if (m_ == 0 || n_ == 0) return R3G_OK;
+    auto misaligned = [](const void* q, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; };
+    if (!d_a8 || !d_w8 || !d_scale_a || !d_scale_w || !d_c) return fail(R3G_ERR_INVALID, "%s: null argument", who);
+    if ((lda & 15) || (ldw & 15) || lda < k_ || ldw < k_ || misaligned(d_a8, 15) || misaligned(d_w8, 15))
+        return fail(R3G_ERR_INVALID, "%s: a8 / w8 rows are staged 16 bytes at a time: lda, ldw %% 16 == 0, >= k, 16-byte aligned pointers", who);
+    if (misaligned(d_scale_w, 15) || misaligned(d_scale_a, 3)) return fail(R3G_ERR_INVALID, "%s: scale_w must be 16-byte, scale_a 4-byte aligned", who);
+    if (misaligned(d_bias, 15) || misaligned(d_gate, 15)) return fail(R3G_ERR_INVALID, "%s: bias / gate must be 16-byte aligned", who);
+    if ((ldc & 3) || ldc < n_ || misaligned(d_c, (uintptr_t)(4 * c_elem - 1)))
+        return fail(R3G_ERR_INVALID, "%s: needs ldc %% 4 == 0, ldc >= n and c aligned to 4 elements (%d bytes)", who, 4 * c_elem);
+    if ((int64_t)m_ * lda >= (1ll << 32) || (int64_t)n_ * ldw >= (1ll << 32)) return fail(R3G_ERR_INVALID, "%s: m * lda and n * ldw must stay below 2^32", who);
+    *launch = true;
+    return R3G_OK;
+}
+
 int r3g_op_gemm_fp8(const uint8_t* d_a8, int64_t lda, const float* d_scale_a, const uint8_t* d_w8, int64_t ldw,
                     const float* d_scale_w, const float* d_bias, void* d_c, int64_t ldc, const float* d_gate, int m_, int n_,
                     int k_, int epilogue, void* stream) {
-    if (!d_a8 || !d_w8 || !d_scale_a || !d_scale_w || !d_c) return fail(R3G_ERR_INVALID, "r3g_op_gemm_fp8: null argument");
+    const bool f32_out = epilogue == EPI_RESID_F32;
+    if (!f32_out && epilogue != EPI_BF16 && epilogue != EPI_BF16_GELU_TANH && epilogue != EPI_BF16_GELU_ERF && epilogue != EPI_RESID_BF16)
+        return fail(R3G_ERR_INVALID, "r3g_op_gemm_fp8: epilogue %d is not one of 0, 1, 2, 3, 6", epilogue);   // 7: r3g_op_gemm_fp8_e4m3
+    bool launch = false;
+    R3G_RC(op_gemm_fp8_args("r3g_op_gemm_fp8", d_a8, lda, d_scale_a, d_w8, ldw, d_scale_w, d_bias, d_c, ldc, f32_out ? 4 : 2, d_gate, m_, n_, k_, &launch));
+    if (!launch) return R3G_OK;
     GemmArgs p{};
     p.A = reinterpret_cast<const uint16_t*>(d_a8); p.lda = lda; p.W = reinterpret_cast<const uint16_t*>(d_w8); p.ldw = ldw;
     p.bias = d_bias; p.C = d_c; p.ldc = ldc; p.gate = d_gate;
     p.M = m_; p.N = n_; p.K = k_; p.epi = epilogue;
     hipError_t e = gemm_fp8_launch(p, d_scale_a, d_scale_w, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "r3g_op_gemm_fp8 (needs K % 256 == 0, 16-byte aligned rows, N % 4 == 0, a bf16 / residual epilogue)");
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_gemm_fp8");
+    return R3G_OK;
+}
+
+int r3g_op_gemm_fp8_e4m3(const uint8_t* d_a8, int64_t lda, const float* d_scale_a, const uint8_t* d_w8, int64_t ldw,
+                         const float* d_scale_w, const float* d_bias, uint8_t* d_c8, int64_t ldc_bytes, float out_scale, int m_, int n_,
+                         int k_, void* stream) {
+    if (!(out_scale > 0.f) || !std::isfinite(out_scale)) return fail(R3G_ERR_INVALID, "r3g_op_gemm_fp8_e4m3: out_scale must be positive and finite");
+    bool launch = false;
+    R3G_RC(op_gemm_fp8_args("r3g_op_gemm_fp8_e4m3", d_a8, lda, d_scale_a, d_w8, ldw, d_scale_w, d_bias, d_c8, ldc_bytes, 1, nullptr, m_, n_, k_, &launch));
+    if (!launch) return R3G_OK;
+    GemmArgs p{};
+    p.A = reinterpret_cast<const uint16_t*>(d_a8); p.lda = lda; p.W = reinterpret_cast<const uint16_t*>(d_w8); p.ldw = ldw;
+    p.bias = d_bias; p.C = d_c8; p.ldc = ldc_bytes;
+    p.M = m_; p.N = n_; p.K = k_; p.epi = EPI_FP8_GELU_ERF;
+    p.out_inv_scale = 1.0f / out_scale;
+    hipError_t e = gemm_fp8_launch(p, d_scale_a, d_scale_w, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_gemm_fp8_e4m3");
     return R3G_OK;
 }
 

@@ -755,7 +755,7 @@ int r3g_sched_euler_ancestral_step(float* d_sample, const float* d_model_out, co
 /* ---- single kernels, for parity tests through the ABI ------------------------------------------ */
 /* C = epilogue(A[m][k] . W[n][k]^T + bias); epilogue: 0 bf16, 1 bf16 gelu(tanh), 2 bf16 gelu(erf),
  * 3 f32 C += gate*(..), 4 f32, 6 bf16 C = bf16(C + gate*(..)), 8 the same in fp16 (the sum formed in fp32; gate null: 1).  Any other
- * epilogue is R3G_ERR_INVALID: 5 and 9-11 need operands this entry point cannot carry, 7 belongs to r3g_op_gemm_fp8.
+ * epilogue is R3G_ERR_INVALID: 5 and 9-11 need operands this entry point cannot carry, 7 belongs to r3g_op_gemm_fp8_e4m3.
  * Shapes: m >= 0 (0: nothing is launched), k % 64 == 0, n % 4 == 0.  Operands: a and w are staged 16 bytes at a time -- lda % 8 == 0,
  * ldw % 8 == 0, both >= k, d_a and d_w 16-byte aligned; d_bias and d_gate (either may be null) 16-byte aligned, n floats each.
  * Output: the kernels store four consecutive columns at a time on their narrowest path, so ldc % 4 == 0, ldc >= n, and d_c aligned to
@@ -810,8 +810,8 @@ int r3g_op_geo_tail(const uint16_t* d_cat, const uint16_t* d_x0, int n, int hidd
  *   d_scale2 / d_shift2 (both required then) instead.  16-bit rows, and f32 rows with c % 256 == 0, ldx % 4 == 0 and ldy % 4 == 0, run on
  *   the row-in-registers kernel, which moves four elements per access: ldx, x_batch_stride, ldy, y_batch_stride, mod_stride % 4 == 0, x
  *   and y aligned to four elements, the six vectors to 16 bytes.  Any other f32 row runs on the scalar kernel (no alignment demands).
- *   d_y8 != null: INSTEAD of y, OCP e4m3 bytes [rows][ldy8] and d_y_scale f32 [rows] (amax / 448 of the finished row, 1 for an all-zero
- *   row; round to nearest even).  That form indexes its outputs by the launch row, so it takes one batch only: d_y null, ldy = 0, both
+ *   d_y8 != null: INSTEAD of y, OCP e4m3 bytes [rows][ldy8] and d_y_scale f32 [rows] (amax / 448 of the finished row, floored at 2^-126
+ *   as r3g_op_quant_fp8 states, 1 for an all-zero row; round to nearest even).  That form indexes its outputs by the launch row, so it takes one batch only: d_y null, ldy = 0, both
  *   batch strides 0, rows_per_batch >= rows, c % 256 == 0 on the row-in-registers kernel, ldy8 % 4 == 0, d_y8 4-byte aligned.
  * ln_dot: d_out f32 [rows] = (do_ln ? LN(x) (lnw, lnb: both or neither) : x) . w + b; x f32 or bf16 (x_bf16 1: c % 256 == 0), c as above;
  *   f32 rows with c % 256 == 0 and ldx % 4 == 0, and all bf16 rows, move four elements per access (alignment as for layernorm).
@@ -844,15 +844,38 @@ int r3g_op_group_norm(const float* d_x, int rows, int c, int groups, const float
 int r3g_op_softmax_rows(const float* d_s, int64_t lds, uint16_t* d_p, int64_t ldp, int rows, int n, float scale, void* stream);
 int r3g_op_geglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f, void* stream);
 int r3g_op_swiglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f, void* stream);
-/* FP8 operands (BASELINE.json configs[3]).  quant_fp8: bf16 [rows][k] -> OCP e4m3 bytes [rows][k] + one fp32 scale per row
- * (amax / 448; round to nearest even, saturating).  gemm_fp8: C = epilogue((scale_a[m] scale_w[n]) sum_k a8[m][k] w8[n][k] +
- * bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the bf16 matrix rate); k % 256 == 0, lda / ldw in bytes and multiples
- * of 16, epilogue one of 0, 1, 2 (bf16 out), 3 (fp32 residual), 6 (bf16 residual).  Test / benchmark hooks; the model uses
- * the same kernels for the geo decoder under r3g_set_option("geo_fp8", 1). */
+/* FP8 operands (BASELINE.json configs[3]).  Test / benchmark hooks; the model uses the same kernels for the geo decoder under
+ * r3g_set_option("geo_fp8", 1).
+ * quant_fp8: bf16 [rows][k] -> OCP e4m3 bytes [rows][k] + one fp32 scale per row; k % 8 == 0, ldx % 8 == 0, ldq % 8 == 0.
+ *   scale = max(fl(amax fl(1 / 448)), 2^-126) for a row with amax > 0 and 1 for an all-zero row; code = the e4m3 nearest to
+ *   fl(x fl(1 / scale)) (ties to even; the quotient exceeds 448 by three roundings at most and rounds to 448).  The floor -- the smallest normal fp32 -- keeps 1 / scale finite: a finite row never
+ *   produces a NaN code, the decoded code times scale is within half an e4m3 step (2^-10 scale at least) of x, and only rows with
+ *   amax < 448 * 2^-126 (about 5.3e-36) are touched by it.  The e4m3 output of r3g_op_layernorm scales its rows by the same rule.
+ *   Non-finite elements are not repaired: a NaN element becomes the NaN code (0x7F under the sign bit) and does not enter amax, so the rest
+ *   of its row is quantised as if it were absent; a +-Inf element makes the row's scale +Inf, its own code the NaN code and every finite
+ *   element of the row a zero code (tests/test_fp8_edges_gpu.py pins both).
+ * gemm_fp8: C = epilogue((scale_a[m] scale_w[n]) sum_k a8[m][k] w8[n][k] + bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the bf16
+ *   matrix rate); epilogue 0, 1, 2 (bf16 out), 3 (fp32 residual), 6 (bf16 residual) as for r3g_op_gemm (gate null: 1); the GELU epilogues
+ *   take their fp32 forms whatever "gelu_pk" says.  Any other epilogue is R3G_ERR_INVALID: 5 and 9-11 need operands this entry point
+ *   cannot carry, 4 and 8 have no fp8 form, 7 is r3g_op_gemm_fp8_e4m3.  Shapes: m, n >= 0 (either 0: R3G_OK, nothing is launched),
+ *   k >= 256, k % 256 == 0, n % 4 == 0.  Operands: a8 and w8 are staged 16 bytes at a time -- lda, ldw in bytes, % 16 == 0, both >= k,
+ *   d_a8 and d_w8 16-byte aligned, m * lda and n * ldw below 2^32 (32-bit staging offsets); d_scale_a f32 [m] 4-byte aligned, d_scale_w
+ *   f32 [n] 16-byte aligned (read four at a time); d_bias and d_gate (either may be null) 16-byte aligned, n floats each.  Output as for
+ *   r3g_op_gemm: ldc % 4 == 0, ldc >= n, d_c aligned to four elements (8 bytes for 0, 1, 2, 6; 16 bytes for 3); with n % 8 == 0,
+ *   ldc % 8 == 0 and a 16-byte aligned d_c the 16-bit outputs leave in 16-byte stores instead (same values).  Nothing outside [m) x [n)
+ *   of C is written; rows past m / n and bytes past k of a8 and w8, and entries past m / n of the scales, bias and gate, are never read.
+ *   A violation is R3G_ERR_INVALID with nothing launched or written.  Counter "gemm_fp8" moves by one per launch.
+ * gemm_fp8_e4m3 (epilogue 7, the operand of a following fp8 GEMM under a static scale): c8[m][n] = the e4m3 code nearest to
+ *   gelu_erf(lin) * fl(1 / out_scale) clamped to +-448 (fp32 GELU form, ties to even; a NaN stays the NaN code), lin as above; out_scale > 0 and finite.  The same contract
+ *   with C in bytes: ldc_bytes % 4 == 0, ldc_bytes >= n, d_c8 4-byte aligned; with n % 16 == 0, ldc_bytes % 16 == 0 and a 16-byte aligned
+ *   d_c8 the codes leave in 16-byte stores (same values). */
 int r3g_op_quant_fp8(const uint16_t* d_x, int64_t ldx, int rows, int k, uint8_t* d_q, int64_t ldq, float* d_scale, void* stream);
 int r3g_op_gemm_fp8(const uint8_t* d_a8, int64_t lda, const float* d_scale_a, const uint8_t* d_w8, int64_t ldw,
                     const float* d_scale_w, const float* d_bias, void* d_c, int64_t ldc, const float* d_gate, int m, int n,
                     int k, int epilogue, void* stream);
+int r3g_op_gemm_fp8_e4m3(const uint8_t* d_a8, int64_t lda, const float* d_scale_a, const uint8_t* d_w8, int64_t ldw,
+                         const float* d_scale_w, const float* d_bias, uint8_t* d_c8, int64_t ldc_bytes, float out_scale, int m, int n,
+                         int k, void* stream);
 /* Per-kernel-family timing with HIP events on the launch stream (bench.py's roofline leg).  Families, in order:
  * 0 gemm, 1 attention, 2 layernorm, 3 qkv_split, 4 gemv, 5 elementwise, 6 mc_classify, 7 mc_other, 8 mesh
  * cleaners (n >= 9).  work = algorithmic FLOPs (0,1,4) / bytes (6,8) summed over the launches since r3g_prof_enable(1). */
@@ -980,7 +1003,8 @@ int r3g_get_option(const char* name, int* value);
  * tile per workgroup; the folded geo epilogues included), "gemm_phased_persistent", "gemm_mixed" (a single block's fused QKV + MLP-in
  * as one persistent launch), "gemm_splitk2" (split-K over two workgroups per tile), "gemm_splitk128" (the slices of the 128 x 128
  * kernel plus their reduce; the slice launch counts under its own form as well), "gemm_deep_ring", "gemm_conv_implicit",
- * "gemm_register_staged" (a tile-kernel launch without LDS-DMA; the phased kernels have no such form).  Attention: "attn_gen1",
+ * "gemm_register_staged" (a tile-kernel launch without LDS-DMA; the phased kernels have no such form), "gemm_fp8" (the e4m3-operand form
+ * of the phased kernel: r3g_op_gemm_fp8, r3g_op_gemm_fp8_e4m3 and the geo decoder under "geo_fp8"; no other GEMM counter moves with it).  Attention: "attn_gen1",
  * "attn_pipelined", "attn_gen2", "attn_gen3", "attn_gen4", "attn_gen5", "attn_gen6", "attn_gen9" (the generation launched, after "attn_generation" 7's rule), and
  * "attn_register_staged".  Row kernels: "ln_rows1" / "ln_rows4" (LayerNorm and ln_dot launches with 1 | 4 rows per wave), "ln_fixed_count"
  * (with a compile-time row length), "ln_mode_inst" (with the affine-only / modulation-only instantiation); "mc_rows4", "mc_rows8",
