@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "dev_buf.h"
 #include "grid_csr.h"
 
 namespace r3g {
@@ -36,10 +37,8 @@ static_assert(sizeof(GridCsrSmall) == 56, "GridCsrSmall travels through the 64-b
 // what a user keeps in the context between its build and its queries
 template <int D>
 struct GridCsrState {
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
-    char* pairs = nullptr;          // int32 [GridCsrSmall::pairs]: a buffer of its own
-    size_t pairs_bytes = 0;
+    DevBuf ws;
+    DevBuf pairs;                   // int32 [GridCsrSmall::pairs]: a buffer of its own
     GridCsrLayout lay{};
     r3g_grid::GridN<D> grid{};
     bool built = false;

@@ -96,11 +96,9 @@ struct Model {
     // the geo decoder's own width and head count: W / Wh unless the checkpoint carries a narrow decoder; read off
     // vae.geo_decoder.query_proj.weight by geo_dims() at the start of every r3g_vae_decode / grid query
     int Wg = 0, Hg = 0;
-    void* geo_tail_packed = nullptr;      // geo_tail_pack_launch's fragment stream (fused tail of a narrow decoder)
-    size_t geo_tail_packed_bytes = 0;
-    // device buffers
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
+    DevBuf geo_tail_packed;               // geo_tail_pack_launch's fragment stream (fused tail of a narrow decoder)
+    // device buffers (every DevBuf below goes with the model)
+    DevBuf arena;
     float* f32a = nullptr;      // residual stream
     uint16_t* xn = nullptr;     // normalised / modulated operand
     uint16_t* qkv = nullptr;    // fused projection output
@@ -117,28 +115,29 @@ struct Model {
     uint16_t *geoK = nullptr, *geoVt = nullptr;
     bool have_z = false;
     // all adaLN modulation GEMVs of one DiT forward, batched into one launch
-    GemvJob* mod_jobs = nullptr;
+    DevBuf mod_jobs;                    // GemvJob [n_mod_jobs]
     int n_mod_jobs = 0;
-    float* mod_all = nullptr;           // [job][B][N]
+    DevBuf mod_all;                     // f32 [job][B][N]
     std::vector<int64_t> mod_off;       // per job offset into mod_all
     // second stream: the MLP half of a single block's linear1 runs beside the attention kernel (see dit_forward_grouped)
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // fp8 mode of the geo decoder (option geo_fp8): e4m3 copies of its weights with one scale per output row, made on
     // first use; per-row scales of the activations LayerNorm quantises; the constant scale vector of the MLP hidden
-    struct W8 { uint8_t* w8; float* sw; };
+    struct W8 { DevBuf w8, sw; };                    // e4m3 [N][K], f32 [N rounded up to 64]
     std::unordered_map<const void*, W8> w8;
-    float *fp8_sa = nullptr, *fp8_sconst = nullptr;
-    uint16_t* lnf_w = nullptr;                       // ln_3 fold: bf16(c_fc.weight * ln_3.weight) [N][W]
-    float *lnf_c = nullptr, *lnf_stats = nullptr;    //   c1 | c2 [2 N], (mean, rstd) per row of a pass [qc][2]
-    int lnf_n = 0, lnf_k = 0, lnd_w = 0;             // the shapes lnf_* / lnd_* were allocated for (a re-registered decoder may differ)
-    float *lnd_gw = nullptr, *lnd_part = nullptr;   // EPI_RESID_BF16_LND: gamma * w [W] + 2 constants, chunk statistics [qc][W / 64][4]
+    DevBuf fp8_sa, fp8_sconst;                       // f32 [qc] each
+    // The folds' buffers are grown to the decoder at hand by size alone: lnf_w, lnf_c and lnd_gw are rewritten by every grid query
+    // (the weights may have been re-registered), lnd_part and lnf_stats are written before they are read within a pass.
+    DevBuf lnf_w;                                    // ln_3 fold: bf16(c_fc.weight * ln_3.weight) [N][W]
+    DevBuf lnf_c, lnf_stats;                         //   f32 c1 | c2 [2 N], (mean, rstd) per row of a pass [qc][2]
+    DevBuf lnd_gw, lnd_part;                         // EPI_RESID_BF16_LND: f32 gamma * w [W] + 2 constants, chunk statistics [qc][W / 64][4]
     // activation arena of the grouped DiT engine for `cap_obj` objects and `cap_lat` latent blocks (= attention entries) per
     // launch (allocated on first use), and the segment tables of its fused QKV epilogues for `nb` objects of `epo` entries each
     // (2: classifier-free guidance with the de-duplicated unconditional entry | 1: a guidance-distilled model, no CFG batch)
     struct DitBatch {
         int cap_obj = 0, cap_lat = 0, nb = 0, epo = 0;
-        char* base = nullptr;
+        DevBuf base;
         float *f32a = nullptr, *v2 = nullptr, *lat0 = nullptr;   // lat0: the group's initial latents (fp16-stream overflow guard)
         int* bad = nullptr;                                        // device flag of that guard
         uint16_t *xn = nullptr, *Q = nullptr, *K = nullptr, *Vt = nullptr, *cat = nullptr, *inb = nullptr, *ctx = nullptr;
@@ -155,19 +154,18 @@ struct Model {
         int R = -1, W = 0;                      // W: the decoder width the rows were laid out for
         double bound = 0.0;
         int64_t passes = 0;
-        uint16_t *x0 = nullptr, *Q = nullptr;   // [passes][qc][W] each
+        DevBuf x0;                              // bf16 [passes][qc][W], and behind it ...
+        uint16_t* Q = nullptr;                  // ... [passes][qc][W] in the same allocation
         std::vector<char> built;
         unsigned epoch = 0;                     // option epoch the built passes belong to (kernel generations change what Q holds)
         bool refused = false;                   // allocation failed for this (R, bound): do not try again
     } gq;
     // hierarchical volume decoder (r3g_grid_query_hier): the grids of the levels below the finest, the active list of the level
     // being built and its logits; grown on demand, released with the model
-    char *hier_grids = nullptr, *hier_idx = nullptr, *hier_val = nullptr;
-    size_t hier_grids_bytes = 0, hier_idx_bytes = 0, hier_val_bytes = 0;
+    DevBuf hier_grids, hier_idx, hier_val;
     // top-k KV selection (kvsel_kernels.h), grown on demand: the grouped Q of a pass, the compact K / V^T and the index table of its
     // (group, head) pairs, and the row-major copy of the object's V (made by the first top-k pass after r3g_vae_decode)
-    char *kv_q = nullptr, *kv_k = nullptr, *kv_vt = nullptr, *kv_idx = nullptr, *kv_v = nullptr;
-    size_t kv_q_bytes = 0, kv_k_bytes = 0, kv_vt_bytes = 0, kv_idx_bytes = 0, kv_v_bytes = 0;
+    DevBuf kv_q, kv_k, kv_vt, kv_idx, kv_v;
     bool kv_v_valid = false;
     int kv_last_groups = 0, kv_last_k = 0;      // shape of the table the last top-k pass left in kv_idx (0: none yet)
     const uint16_t* kv_last_q = nullptr;        // ... and the Q rows it was made from: [H][kv_last_npad][64], kv_last_n of them valid
@@ -345,9 +343,9 @@ static int build_mod_jobs(Model& m) {
     }
     for (int i = 0; i < c.dit_depth_single; ++i) R3G_RC(add(fmt("model.single_blocks.%d.modulation.lin", i), 3));
     R3G_RC(add("model.final_layer.adaLN_modulation.1", 2));
-    R3G_TRY(hipMalloc((void**)&m.mod_jobs, jobs.size() * sizeof(GemvJob)));
-    R3G_TRY(hipMemcpy(m.mod_jobs, jobs.data(), jobs.size() * sizeof(GemvJob), hipMemcpyHostToDevice));
-    R3G_TRY(hipMalloc((void**)&m.mod_all, (size_t)off * sizeof(float)));
+    R3G_RC(m.mod_all.grow((size_t)off * sizeof(float), nullptr, "modulation outputs"));
+    R3G_RC(m.mod_jobs.grow(jobs.size() * sizeof(GemvJob), nullptr, "modulation jobs"));      // (last: its presence marks the table as built)
+    R3G_TRY(hipMemcpy(m.mod_jobs.p, jobs.data(), jobs.size() * sizeof(GemvJob), hipMemcpyHostToDevice));
     m.n_mod_jobs = (int)jobs.size();
     return R3G_OK;
 }
@@ -383,7 +381,7 @@ static int dit_forward(Model& m, const float* x_in, const float* t_dev, float t_
 
     if (g_batch_mods) {
         R3G_RC(build_mod_jobs(m));
-        R3G_TRY(gemv_multi_launch(m.vec, B, H, m.mod_jobs, m.n_mod_jobs, m.mod_all, 1, s));
+        R3G_TRY(gemv_multi_launch(m.vec, B, H, m.mod_jobs.as<GemvJob>(), m.n_mod_jobs, m.mod_all.as<float>(), 1, s));
     }
     const int nd = n_double < 0 ? c.dit_depth_double : n_double;
     const int ns = n_single < 0 ? c.dit_depth_single : n_single;
@@ -400,7 +398,7 @@ static int dit_forward(Model& m, const float* x_in, const float* t_dev, float t_
             const std::string blk = fmt("model.double_blocks.%d.%s", i, nm);
             // mods: [stream][B][6H] = shift1 scale1 gate1 shift2 scale2 gate2
             float* mm = m.mods + (int64_t)st * 2 * 6 * H;
-            if (g_batch_mods) mm = m.mod_all + m.mod_off[2 * i + st];
+            if (g_batch_mods) mm = m.mod_all.as<float>() + m.mod_off[2 * i + st];
             else R3G_RC(dit_modulation(m, blk + "_mod.lin", B, 6, mm, s));
             R3G_RC(layernorm(m.f32a + (int64_t)row0 * H, H, xs, m.xn + (int64_t)row0 * H, H, xs, rows, B, H, nullptr, nullptr,
                              mm + H, mm, 6 * H, 1e-6f, s));
@@ -419,7 +417,7 @@ static int dit_forward(Model& m, const float* x_in, const float* t_dev, float t_
             const char* nm = st == 0 ? "img" : "txt";
             const int row0 = st == 0 ? 0 : Nl, rows = st == 0 ? Nl : Lc;
             const std::string blk = fmt("model.double_blocks.%d.%s", i, nm);
-            float* mm = g_batch_mods ? m.mod_all + m.mod_off[2 * i + st] : m.mods + (st == 0 ? 0 : (int64_t)2 * 6 * H);
+            float* mm = g_batch_mods ? m.mod_all.as<float>() + m.mod_off[2 * i + st] : m.mods + (st == 0 ? 0 : (int64_t)2 * 6 * H);
             float* xr = m.f32a + (int64_t)row0 * H;
             R3G_RC(get_lin(m, blk + "_attn.proj", true, &l));
             R3G_RC(gemm(m.cat + (int64_t)row0 * catld, catld, cats, l, 0, H, xr, H, xs, rows, H, EPI_RESID_F32, mm + 2 * H,
@@ -437,7 +435,7 @@ static int dit_forward(Model& m, const float* x_in, const float* t_dev, float t_
     for (int i = 0; i < ns; ++i) {
         const std::string blk = fmt("model.single_blocks.%d", i);
         float* mm = m.mods;  // [B][3H]: shift scale gate
-        if (g_batch_mods) mm = m.mod_all + m.mod_off[2 * c.dit_depth_double + i];
+        if (g_batch_mods) mm = m.mod_all.as<float>() + m.mod_off[2 * c.dit_depth_double + i];
         else R3G_RC(dit_modulation(m, blk + ".modulation.lin", B, 3, mm, s));
         R3G_RC(layernorm(m.f32a, H, xs, m.xn, H, xs, T, B, H, nullptr, nullptr, mm + H, mm, 3 * H, 1e-6f, s));
         R3G_RC(get_lin(m, blk + ".linear1", true, &l));
@@ -458,7 +456,7 @@ static int dit_forward(Model& m, const float* x_in, const float* t_dev, float t_
     // final layer on the latent rows
     float* fm = m.mods;
     if (g_batch_mods) {
-        fm = m.mod_all + m.mod_off[2 * c.dit_depth_double + c.dit_depth_single];
+        fm = m.mod_all.as<float>() + m.mod_off[2 * c.dit_depth_double + c.dit_depth_single];
     } else {
         R3G_RC(get_lin(m, "model.final_layer.adaLN_modulation.1", true, &l));
         R3G_TRY(gemv_launch(m.vec, B, H, l.w, l.ldw, l.b, fm, 2 * H, 1, 0, s));
@@ -519,7 +517,9 @@ static int ensure_dit_batch(Model& m, int NB, int E) {
     const int H = m.H, Nl = c.vae_num_latents, Lc = m.Lc;
     const int Ltp = dit_txt_rows(m);
     if (d.cap_obj < NB || d.cap_lat < E * NB) {
-        if (d.base) { R3G_TRY(hipDeviceSynchronize()); (void)hipFree(d.base); d.base = nullptr; }
+        // the whole device, not a stream: m.aux, the second stream of dit_forward_grouped, works in this arena too
+        if (d.base) R3G_TRY(hipDeviceSynchronize());
+        d.base.release();
         const int co = std::max(d.cap_obj, NB), cl = std::max(d.cap_lat, E * NB);
         d.cap_obj = d.cap_lat = 0;
         const int64_t rows = rup((int64_t)cl * Nl + (int64_t)co * Ltp, 256);
@@ -530,9 +530,13 @@ static int ensure_dit_batch(Model& m, int NB, int E) {
                      o_v = carve(n_attn * 2), o_cat = carve(rows * 5 * H * 2), o_inb = carve((int64_t)co * Nl * m.cin_pad * 2),
                      o_ctx = carve((int64_t)co * Ltp * c.dit_context_dim * 2), o_v2 = carve((int64_t)cl * Nl * c.dit_in_channels * 4),
                      o_seg = carve(2 * 64 * 16), o_lat0 = carve((int64_t)co * Nl * c.dit_in_channels * 4), o_bad = carve(256);
-        R3G_TRY(hipMalloc((void**)&d.base, off));
-        R3G_TRY(hipMemset(d.base, 0, off));   // padded rows / columns must start finite
-        char* a = d.base;
+        R3G_RC(d.base.grow(off, nullptr, "dit batch arena"));
+        const hipError_t e = hipMemset(d.base.p, 0, off);   // padded rows / columns must start finite
+        if (e != hipSuccess) {
+            d.base.release();      // (capacities are 0: the next call starts over)
+            return hip_fail(e, "hipMemset(dit batch arena)");
+        }
+        char* a = d.base.p;
         d.f32a = (float*)(a + o_f); d.xn = (uint16_t*)(a + o_xn); d.Q = (uint16_t*)(a + o_q); d.K = (uint16_t*)(a + o_k);
         d.Vt = (uint16_t*)(a + o_v); d.cat = (uint16_t*)(a + o_cat); d.inb = (uint16_t*)(a + o_inb);
         d.ctx = (uint16_t*)(a + o_ctx); d.v2 = (float*)(a + o_v2); d.seg_txt = (int*)(a + o_seg); d.seg_all = d.seg_txt + 64 * 4;
@@ -605,7 +609,7 @@ static int dit_forward_grouped(Model& m, const float* x_lat, float t_scalar, flo
     R3G_TRY(gemv_launch(m.th, 1, H, l.w, l.ldw, l.b, m.vec, H, 0, 0, s));
     if (gvec) R3G_TRY(vec_add_launch(m.vec, gvec, H, s));   // vec = time_in(emb(t)) + guidance_in(emb(g))
     R3G_RC(build_mod_jobs(m));
-    R3G_TRY(gemv_multi_launch(m.vec, 1, H, m.mod_jobs, m.n_mod_jobs, m.mod_all, 1, s));
+    R3G_TRY(gemv_multi_launch(m.vec, 1, H, m.mod_jobs.as<GemvJob>(), m.n_mod_jobs, m.mod_all.as<float>(), 1, s));
 
     AttnArgs at{};
     at.Q = d.Q; at.K = d.K; at.Vt = d.Vt; at.O = d.cat; at.ldo = catld; at.strideO = 0;
@@ -673,8 +677,8 @@ static int dit_forward_grouped(Model& m, const float* x_lat, float t_scalar, flo
     };
     for (int i = 0; i < c.dit_depth_double; ++i) {
         const std::string bi = fmt("model.double_blocks.%d.img", i), bt = fmt("model.double_blocks.%d.txt", i);
-        const float* mi = m.mod_all + m.mod_off[2 * i];
-        const float* mt = m.mod_all + m.mod_off[2 * i + 1];
+        const float* mi = m.mod_all.as<float>() + m.mod_off[2 * i];
+        const float* mt = m.mod_all.as<float>() + m.mod_off[2 * i + 1];
         QkvSplitArgs qi, qt;
         Lin li, lt;
         // img stream: the E*NB latent blocks (one GEMM batch entry = one attention batch slot); txt stream: per object Lc
@@ -717,7 +721,7 @@ static int dit_forward_grouped(Model& m, const float* x_lat, float t_scalar, flo
     }
     for (int i = 0; i < c.dit_depth_single; ++i) {
         const std::string blk = fmt("model.single_blocks.%d", i);
-        const float* mm = m.mod_all + m.mod_off[2 * c.dit_depth_double + i];
+        const float* mm = m.mod_all.as<float>() + m.mod_off[2 * c.dit_depth_double + i];
         R3G_RC(layernorm(d.f32a, H, 0, d.xn, H, 0, Rall, 1, H, nullptr, nullptr, mm + H, mm, 0, 1e-6f, s, xfmt));
         R3G_RC(get_lin(m, blk + ".linear1", true, &l));
         QkvSplitArgs q;
@@ -751,7 +755,7 @@ static int dit_forward_grouped(Model& m, const float* x_lat, float t_scalar, flo
         R3G_RC(get_lin(m, blk + ".linear2", true, &l));
         R3G_RC(gemm(d.cat, catld, 0, l, 0, H, d.f32a, H, 0, Rall, H + mh, epi_res, mm + 2 * H, 0, 1, s));
     }
-    const float* fm = m.mod_all + m.mod_off[2 * c.dit_depth_double + c.dit_depth_single];
+    const float* fm = m.mod_all.as<float>() + m.mod_off[2 * c.dit_depth_double + c.dit_depth_single];
     R3G_RC(layernorm(d.f32a, H, 0, d.xn, H, 0, TX0, 1, H, nullptr, nullptr, fm + H, fm, 0, 1e-6f, s, xfmt));
     R3G_RC(get_lin(m, "model.final_layer.linear", true, &l));
     R3G_RC(gemm(d.xn, H, 0, l, 0, c.dit_in_channels, out2, c.dit_in_channels, 0, TX0, H, EPI_F32, nullptr, 0, 1, s));
@@ -861,27 +865,27 @@ static int fill_f32(float* dst, int n, float v, hipStream_t s) {
     return R3G_OK;
 }
 
-static int lin_fp8(Model& m, const Lin& l, Model::W8* out, hipStream_t s) {
+static int lin_fp8(Model& m, const Lin& l, const Model::W8** out, hipStream_t s) {
     auto it = m.w8.find(l.w);
     if (it == m.w8.end()) {
-        Model::W8 q{};
-        R3G_TRY(hipMalloc((void**)&q.w8, (size_t)l.N * l.K));
-        R3G_TRY(hipMalloc((void**)&q.sw, 4 * (size_t)rup(l.N, 64)));
-        R3G_TRY(quant_fp8_rows_launch(l.w, l.ldw, l.N, l.K, q.w8, l.K, q.sw, s));
-        it = m.w8.emplace(l.w, q).first;
+        Model::W8 q;
+        R3G_RC(q.w8.grow((size_t)l.N * l.K, s, "fp8 weight"));
+        R3G_RC(q.sw.grow(4 * (size_t)rup(l.N, 64), s, "fp8 weight scales"));
+        R3G_TRY(quant_fp8_rows_launch(l.w, l.ldw, l.N, l.K, q.w8.as<uint8_t>(), l.K, q.sw.as<float>(), s));
+        it = m.w8.emplace(l.w, std::move(q)).first;
     }
-    *out = it->second;
+    *out = &it->second;
     return R3G_OK;
 }
 
 // C = epi(A8 W8^T): A8 [M][K] e4m3 with row scales sa, weights quantised on first use
 static int gemm_fp8(Model& m, const uint8_t* A8, const float* sa, const Lin& l, void* C, int64_t ldc, int M, int epi,
                     const QkvSplitArgs* q, int qkv_layout, hipStream_t s) {
-    Model::W8 w;
+    const Model::W8* w;
     R3G_RC(lin_fp8(m, l, &w, s));
     GemmArgs p{};
     p.A = reinterpret_cast<const uint16_t*>(A8); p.lda = l.K;
-    p.W = reinterpret_cast<const uint16_t*>(w.w8); p.ldw = l.K;
+    p.W = w->w8.as<const uint16_t>(); p.ldw = l.K;
     p.bias = l.b; p.C = C; p.ldc = ldc;
     p.M = M; p.N = l.N; p.K = l.K; p.epi = epi;
     p.out_inv_scale = 1.0f / kGeoHiddenScale;
@@ -891,7 +895,7 @@ static int gemm_fp8(Model& m, const uint8_t* A8, const float* sa, const Lin& l, 
         p.qkv.qw = q->qw; p.qkv.qb = q->qb; p.qkv.kw = q->kw; p.qkv.kb = q->kb; p.qkv.eps = q->eps;
         p.qkv.q_scale = q->q_scale;
     }
-    hipError_t e = gemm_fp8_launch(p, sa, w.sw, s);
+    hipError_t e = gemm_fp8_launch(p, sa, w->sw.as<const float>(), s);
     if (e != hipSuccess) return hip_fail(e, "gemm_fp8_launch");
     return R3G_OK;
 }
@@ -909,18 +913,6 @@ static int layernorm_fp8(const float* x, int64_t ldx, uint8_t* y8, int64_t ldy8,
 }
 
 // ---- top-k KV selection ---------------------------------------------------------------------
-static int kv_grow(char** buf, size_t* have, size_t need, hipStream_t s, const char* what) {
-    if (need <= *have) return R3G_OK;
-    if (*buf) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(*buf); *buf = nullptr; *have = 0; }
-    if (hipMalloc((void**)buf, need) != hipSuccess) {
-        (void)hipGetLastError();
-        *buf = nullptr;
-        return fail(R3G_ERR_HIP, "hipMalloc(%s, %zu bytes) failed", what, need);
-    }
-    *have = need;
-    return R3G_OK;
-}
-
 // the keys kept per (group, head) under the current options: 0 = exact attention
 static int kv_topk_for(int num_latents) {
     if (g_geo_kv_topk == 0) return 0;
@@ -934,14 +926,14 @@ static int kv_topk_for(int num_latents) {
 static int kv_attention(Model& m, const uint16_t* Qp, int n, int npad, int k, hipStream_t s) {
     const int W = m.Wg, Nl = m.c.vae_num_latents, heads = m.Hg, G = g_geo_kv_group, Lkp = (int)rup(Nl, 64), kpad = (int)rup(k, 64);
     const KvselCut cut = kvsel_cut(n, G);
-    R3G_RC(kv_grow(&m.kv_q, &m.kv_q_bytes, 2 * (size_t)kvsel_grouped_elems(n, G, heads), s, "grouped Q"));
-    R3G_RC(kv_grow(&m.kv_k, &m.kv_k_bytes, 2 * (size_t)cut.groups * heads * kpad * 64, s, "compact K"));
-    R3G_RC(kv_grow(&m.kv_vt, &m.kv_vt_bytes, 2 * (size_t)cut.groups * heads * kpad * 64, s, "compact V^T"));
-    R3G_RC(kv_grow(&m.kv_idx, &m.kv_idx_bytes, 4 * (size_t)cut.groups * heads * k, s, "selection indices"));
-    R3G_RC(kv_grow(&m.kv_v, &m.kv_v_bytes, 2 * (size_t)heads * Nl * 64, s, "row-major V"));
-    uint16_t *gq = reinterpret_cast<uint16_t*>(m.kv_q), *kc = reinterpret_cast<uint16_t*>(m.kv_k), *vtc = reinterpret_cast<uint16_t*>(m.kv_vt);
-    uint16_t* vrows = reinterpret_cast<uint16_t*>(m.kv_v);
-    int32_t* idx = reinterpret_cast<int32_t*>(m.kv_idx);
+    R3G_RC(m.kv_q.grow(2 * (size_t)kvsel_grouped_elems(n, G, heads), s, "grouped Q"));
+    R3G_RC(m.kv_k.grow(2 * (size_t)cut.groups * heads * kpad * 64, s, "compact K"));
+    R3G_RC(m.kv_vt.grow(2 * (size_t)cut.groups * heads * kpad * 64, s, "compact V^T"));
+    R3G_RC(m.kv_idx.grow(4 * (size_t)cut.groups * heads * k, s, "selection indices"));
+    R3G_RC(m.kv_v.grow(2 * (size_t)heads * Nl * 64, s, "row-major V"));
+    uint16_t *gq = m.kv_q.as<uint16_t>(), *kc = m.kv_k.as<uint16_t>(), *vtc = m.kv_vt.as<uint16_t>();
+    uint16_t* vrows = m.kv_v.as<uint16_t>();
+    int32_t* idx = m.kv_idx.as<int32_t>();
     if (!m.kv_v_valid) {
         R3G_TRY(kvsel_vrows_launch(m.geoVt, Nl, Lkp, heads, vrows, s));
         m.kv_v_valid = true;
@@ -1017,7 +1009,9 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
     const int64_t passes_all = (total + m.qc - 1) / m.qc;
     bool use_cache = g_geo_q_cache && xb && !f8q && cache && !list;
     if (use_cache && (gq.R != R || gq.bound != bound || gq.W != W)) {
-        if (gq.x0) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(gq.x0); gq.x0 = nullptr; gq.Q = nullptr; }
+        if (gq.x0) R3G_TRY(hipStreamSynchronize(s));
+        gq.x0.release();
+        gq.Q = nullptr;
         gq.R = R; gq.bound = bound; gq.W = W; gq.passes = 0; gq.built.clear(); gq.refused = false;
     }
     // (no allocation for a call that contains no canonical pass, e.g. a test's 3 000-point slice of the grid)
@@ -1034,18 +1028,17 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
         if (e == hipSuccess && free_b > ((size_t)16 << 30)) budget = std::min(budget, free_b - ((size_t)16 << 30));
         else budget = 0;
         const int64_t n_cached = std::min<int64_t>(passes_all, (int64_t)(budget / per_pass));
-        if (n_cached < 1 || hipMalloc((void**)&gq.x0, (size_t)n_cached * per_pass) != hipSuccess) {
+        if (n_cached < 1 || gq.x0.alloc((size_t)n_cached * per_pass) != hipSuccess) {
             (void)hipGetLastError();
-            gq.x0 = nullptr;
             gq.refused = true;            // every pass is recomputed, as before
         } else {
-            gq.Q = gq.x0 + n_cached * (int64_t)m.qc * W;
+            gq.Q = gq.x0.as<uint16_t>() + n_cached * (int64_t)m.qc * W;
             ++g_geo_q_cache_builds;
             gq.passes = n_cached;
             gq.built.assign((size_t)n_cached, 0);
         }
     }
-    use_cache = use_cache && gq.x0 != nullptr;
+    use_cache = use_cache && gq.x0;
     if (use_cache && gq.epoch != g_option_epoch) {      // an option changed since these passes were built: build them again
         std::fill(gq.built.begin(), gq.built.end(), 0);
         gq.epoch = g_option_epoch;
@@ -1064,41 +1057,38 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
     // stream (2 x 268 MB per pass).
     const bool lnf = g_geo_ln3_fold && xb && !f8m && W % 256 == 0 && W <= 4096 && lfc.N % 256 == 0 &&
                      gemm_fold_supported(EPI_RESID_BF16_ST, m.qc, W, W) && gemm_fold_supported(EPI_BF16_GELU_ERF_LNF, m.qc, lfc.N, W);
-    if ((lnd || lnf) && !tail && m.lnd_w < W) {
-        if (m.lnd_part || m.lnd_gw) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(m.lnd_part); (void)hipFree(m.lnd_gw); m.lnd_part = m.lnd_gw = nullptr; }
-        m.lnd_w = W;
-    }
-    if ((lnd || lnf) && !tail && !m.lnd_part) R3G_TRY(hipMalloc((void**)&m.lnd_part, 16 * (size_t)m.qc * (size_t)(W / 64)));
+    if ((lnd || lnf) && !tail) R3G_RC(m.lnd_part.grow(16 * (size_t)m.qc * (size_t)(W / 64), s, "ln fold chunk statistics"));
     if (lnd && !tail) {
-        if (!m.lnd_gw) R3G_TRY(hipMalloc((void**)&m.lnd_gw, 4 * (size_t)(W + 64)));
-        R3G_TRY(lnd_prepare_launch(lpw, lpb, ow, ob, W, m.lnd_gw, m.lnd_gw + W, s));      // (per call: the weights may have been re-registered)
+        R3G_RC(m.lnd_gw.grow(4 * (size_t)(W + 64), s, "ln_post fold weights"));
+        float* gw = m.lnd_gw.as<float>();
+        R3G_TRY(lnd_prepare_launch(lpw, lpb, ow, ob, W, gw, gw + W, s));      // (per call: the weights may have been re-registered)
     }
     if (tail) {
-        const size_t need = geo_tail_packed_bytes(lfc.N);
-        if (m.geo_tail_packed_bytes < need) {
-            if (m.geo_tail_packed) { R3G_TRY(hipStreamSynchronize(s)); (void)hipFree(m.geo_tail_packed); m.geo_tail_packed = nullptr; m.geo_tail_packed_bytes = 0; }
-            R3G_TRY(hipMalloc(&m.geo_tail_packed, need));
-            m.geo_tail_packed_bytes = need;
-        }
+        R3G_RC(m.geo_tail_packed.grow(geo_tail_packed_bytes(lfc.N), s, "narrow tail fragments"));
         // (per call: the weights may have been re-registered)
-        R3G_TRY(geo_tail_pack_launch(lproj.w, lproj.ldw, lfc.w, lfc.ldw, lfp.w, lfp.ldw, lfc.N, m.geo_tail_packed, s));
+        R3G_TRY(geo_tail_pack_launch(lproj.w, lproj.ldw, lfc.w, lfc.ldw, lfp.w, lfp.ldw, lfc.N, m.geo_tail_packed.p, s));
     }
     Lin lfc2 = lfc;
-    if (lnf && !tail) {
-        if (m.lnf_w && (m.lnf_n != lfc.N || m.lnf_k != W)) {
-            R3G_TRY(hipStreamSynchronize(s));
-            (void)hipFree(m.lnf_w); (void)hipFree(m.lnf_c); (void)hipFree(m.lnf_stats);
-            m.lnf_w = nullptr; m.lnf_c = nullptr; m.lnf_stats = nullptr;
-        }
-        if (!m.lnf_w) {
-            m.lnf_n = lfc.N; m.lnf_k = W;
-            R3G_TRY(hipMalloc((void**)&m.lnf_w, 2 * (size_t)lfc.N * (size_t)W));
-            R3G_TRY(hipMalloc((void**)&m.lnf_c, 4 * 2 * (size_t)lfc.N));
-            R3G_TRY(hipMalloc((void**)&m.lnf_stats, 8 * (size_t)m.qc));
-        }
-        R3G_TRY(lnf_prepare_launch(lfc.w, lfc.ldw, lfc.b, l3w, l3b, lfc.N, W, m.lnf_w, m.lnf_c, m.lnf_c + lfc.N, s));
-        lfc2.w = m.lnf_w; lfc2.ldw = W; lfc2.K = W; lfc2.b = m.lnf_c + lfc.N;
+    if (lnf && !tail) {      // each buffer on its own: a call after a failed allocation makes up what is missing
+        R3G_RC(m.lnf_w.grow(2 * (size_t)lfc.N * (size_t)W, s, "ln_3 fold weights"));
+        R3G_RC(m.lnf_c.grow(4 * 2 * (size_t)lfc.N, s, "ln_3 fold constants"));
+        R3G_RC(m.lnf_stats.grow(8 * (size_t)m.qc, s, "ln_3 fold row statistics"));
+        float* c1 = m.lnf_c.as<float>();
+        R3G_TRY(lnf_prepare_launch(lfc.w, lfc.ldw, lfc.b, l3w, l3b, lfc.N, W, m.lnf_w.as<uint16_t>(), c1, c1 + lfc.N, s));
+        lfc2.w = m.lnf_w.as<uint16_t>(); lfc2.ldw = W; lfc2.K = W; lfc2.b = c1 + lfc.N;
     }
+    if (f8) {
+        R3G_RC(m.fp8_sa.grow(4 * (size_t)m.qc, s, "fp8 activation scales"));
+        if (!m.fp8_sconst) {
+            R3G_RC(m.fp8_sconst.grow(4 * (size_t)m.qc, s, "fp8 hidden scales"));
+            if (const int rc = fill_f32(m.fp8_sconst.as<float>(), m.qc, kGeoHiddenScale, s)) {
+                m.fp8_sconst.release();      // held means filled
+                return rc;
+            }
+        }
+    }
+    float *const lnd_part = m.lnd_part.as<float>(), *const lnd_gw = m.lnd_gw.as<float>();
+    float *const fp8_sa = m.fp8_sa.as<float>(), *const fp8_sconst = m.fp8_sconst.as<float>();
     for (int64_t off = 0; off < count; off += m.qc) {
         const int n = (int)std::min<int64_t>(m.qc, count - off);
         const int npad = (int)rup(n, 128);
@@ -1108,21 +1098,16 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
         const int64_t pidx = p0 / m.qc;
         const bool canon = use_cache && pidx < gq.passes && p0 % m.qc == 0 && n == (int)std::min<int64_t>(m.qc, total - p0);
         const bool hit = canon && gq.built[(size_t)pidx];
-        uint16_t* x0 = canon ? gq.x0 + pidx * (int64_t)m.qc * W : reinterpret_cast<uint16_t*>(m.f32a);
+        uint16_t* x0 = canon ? gq.x0.as<uint16_t>() + pidx * (int64_t)m.qc * W : reinterpret_cast<uint16_t*>(m.f32a);
         uint16_t* Qp = canon ? gq.Q + pidx * (int64_t)m.qc * W : m.Q;
         uint8_t* xn8 = reinterpret_cast<uint8_t*>(m.xn);
         uint8_t* hid8 = reinterpret_cast<uint8_t*>(m.hid);
-        if (f8 && !m.fp8_sa) {
-            R3G_TRY(hipMalloc((void**)&m.fp8_sa, 4 * (size_t)m.qc));
-            R3G_TRY(hipMalloc((void**)&m.fp8_sconst, 4 * (size_t)m.qc));
-            R3G_RC(fill_f32(m.fp8_sconst, m.qc, kGeoHiddenScale, s));
-        }
         if (!hit) {
             if (list) R3G_TRY(fourier_points_launch(m.inb, list + off, n, npad, R, bound, c.vae_num_freqs, c.vae_include_pi, s));
             else R3G_TRY(fourier_grid_launch(m.inb, p0, npad, R, bound, c.vae_num_freqs, c.vae_include_pi, s));
             R3G_RC(gemm(m.inb, 64, 0, lq, 0, W, xb ? (void*)x0 : (void*)m.f32a, W, 0, n, 64, epi_x0, nullptr, 0, 1, s));
             const float* xin = xb ? reinterpret_cast<const float*>(x0) : m.f32a;
-            if (f8q) R3G_RC(layernorm_fp8(xin, W, xn8, W, m.fp8_sa, n, W, l1w, l1b, 1e-6f, s, xb));
+            if (f8q) R3G_RC(layernorm_fp8(xin, W, xn8, W, fp8_sa, n, W, l1w, l1b, 1e-6f, s, xb));
             else R3G_RC(layernorm(xin, W, 0, m.xn, W, 0, n, 1, W, l1w, l1b, nullptr, nullptr, 0, 1e-6f, s, xb));
             QkvSplitArgs q{};
             q.src = m.qkv; q.ld = W; q.src_batch_stride = 0;
@@ -1134,7 +1119,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
                 R3G_RC(get_vec(m, g + ".cross_attn_decoder.attn.attention.q_norm.weight", 64, &q.qw));
                 R3G_RC(get_vec(m, g + ".cross_attn_decoder.attn.attention.q_norm.bias", 64, &q.qb));
             }
-            if (f8q) R3G_RC(gemm_fp8(m, xn8, m.fp8_sa, lcq, nullptr, 0, n, EPI_QKV, &q, QKV_Q_ONLY, s));
+            if (f8q) R3G_RC(gemm_fp8(m, xn8, fp8_sa, lcq, nullptr, 0, n, EPI_QKV, &q, QKV_Q_ONLY, s));
             else R3G_RC(gemm_qkv(m, m.xn, W, 0, lcq, 0, W, n, W, 1, q, QKV_Q_ONLY, s));
             if (canon) gq.built[(size_t)pidx] = 1;
         }
@@ -1144,7 +1129,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
             GeoTailArgs ta{};
             ta.cat = m.cat; ta.ld_cat = W;
             ta.x0 = canon ? x0 : reinterpret_cast<const uint16_t*>(m.f32a); ta.ld_x0 = W;
-            ta.packed = m.geo_tail_packed;
+            ta.packed = m.geo_tail_packed.p;
             ta.b_proj = lproj.b; ta.ln3_w = l3w; ta.ln3_b = l3b; ta.b_fc = lfc.b; ta.b_fp = lfp.b;
             ta.lnp_w = lpw; ta.lnp_b = lpb; ta.out_w = ow; ta.out_b = ob;
             ta.hidden = lfc.N; ta.n = n; ta.out = grid + start + off;
@@ -1154,22 +1139,22 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
         }
         {   // x1 = x0 + c_proj(attention): the old values come from the cached x0 where there is one
             GemmArgs pr = gemm_args(m.cat, W, 0, lproj, 0, W, m.f32a, W, 0, n, W, lnf ? (int)EPI_RESID_BF16_ST : epi_res, nullptr, 0);
-            pr.lnd_part = m.lnd_part;
+            pr.lnd_part = lnd_part;
             if (canon) pr.resid_src = x0;
             hipError_t e = gemm_launch(pr, 1, s);
             if (e != hipSuccess) return hip_fail(e, "gemm_launch(geo c_proj)");
         }
         if (f8m) {
-            R3G_RC(layernorm_fp8(m.f32a, W, xn8, W, m.fp8_sa, n, W, l3w, l3b, 1e-6f, s, xb));
-            R3G_RC(gemm_fp8(m, xn8, m.fp8_sa, lfc, hid8, lfc.N, n, EPI_FP8_GELU_ERF, nullptr, 0, s));
-            R3G_RC(gemm_fp8(m, hid8, m.fp8_sconst, lfp, m.f32a, W, n, epi_res, nullptr, 0, s));
+            R3G_RC(layernorm_fp8(m.f32a, W, xn8, W, fp8_sa, n, W, l3w, l3b, 1e-6f, s, xb));
+            R3G_RC(gemm_fp8(m, xn8, fp8_sa, lfc, hid8, lfc.N, n, EPI_FP8_GELU_ERF, nullptr, 0, s));
+            R3G_RC(gemm_fp8(m, hid8, fp8_sconst, lfp, m.f32a, W, n, epi_res, nullptr, 0, s));
         } else {
             if (lnf) {
-                R3G_TRY(lnf_stats_launch(m.lnd_part, n, W / 64, 1e-6f, m.lnf_stats, s));
+                R3G_TRY(lnf_stats_launch(lnd_part, n, W / 64, 1e-6f, m.lnf_stats.as<float>(), s));
                 GemmArgs pf = gemm_args(reinterpret_cast<const uint16_t*>(m.f32a), W, 0, lfc2, 0, lfc.N, m.hid, lfc.N, 0, n, W,
                                         EPI_BF16_GELU_ERF_LNF, nullptr, 0);
-                pf.lnf_c1 = m.lnf_c;
-                pf.lnf_stats = m.lnf_stats;
+                pf.lnf_c1 = m.lnf_c.as<float>();
+                pf.lnf_stats = m.lnf_stats.as<float>();
                 hipError_t e = gemm_launch(pf, 1, s);
                 if (e != hipSuccess) return hip_fail(e, "gemm_launch(geo ln_3 + mlp.c_fc)");
                 ++g_geo_lnf_passes;
@@ -1179,11 +1164,11 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
             }
             if (lnd) {
                 GemmArgs pl = gemm_args(m.hid, lfc.N, 0, lfp, 0, W, m.f32a, W, 0, n, lfc.N, EPI_RESID_BF16_LND, nullptr, 0);
-                pl.lnd_gw = m.lnd_gw;
-                pl.lnd_part = m.lnd_part;
+                pl.lnd_gw = lnd_gw;
+                pl.lnd_part = lnd_part;
                 hipError_t e = gemm_launch(pl, 1, s);
                 if (e != hipSuccess) return hip_fail(e, "gemm_launch(geo mlp.c_proj + ln_post + output_proj)");
-                R3G_TRY(lnd_finalize_launch(m.lnd_part, n, W / 64, 1e-5f, m.lnd_gw + W, grid + start + off, s));
+                R3G_TRY(lnd_finalize_launch(lnd_part, n, W / 64, 1e-5f, lnd_gw + W, grid + start + off, s));
                 ++g_geo_lnd_passes;
                 continue;
             }
@@ -1246,32 +1231,10 @@ static int cond_encode(Model& m, const float* img, uint16_t* out, hipStream_t s)
 // ---- lifetime ----------------------------------------------------------------------------------------
 static void model_free(Model* m) {
     if (!m) return;
-    if (m->arena) (void)hipFree(m->arena);
-    if (m->mod_jobs) (void)hipFree(m->mod_jobs);
-    if (m->mod_all) (void)hipFree(m->mod_all);
     if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
     if (m->ev_join) (void)hipEventDestroy(m->ev_join);
     if (m->aux) (void)hipStreamDestroy(m->aux);
-    for (auto& kv : m->w8) {
-        (void)hipFree(kv.second.w8);
-        (void)hipFree(kv.second.sw);
-    }
-    if (m->fp8_sa) (void)hipFree(m->fp8_sa);
-    if (m->lnf_w) (void)hipFree(m->lnf_w);
-    if (m->lnf_c) (void)hipFree(m->lnf_c);
-    if (m->lnf_stats) (void)hipFree(m->lnf_stats);
-    if (m->lnd_gw) (void)hipFree(m->lnd_gw);
-    if (m->lnd_part) (void)hipFree(m->lnd_part);
-    if (m->fp8_sconst) (void)hipFree(m->fp8_sconst);
-    if (m->db.base) (void)hipFree(m->db.base);
-    if (m->gq.x0) (void)hipFree(m->gq.x0);
-    if (m->geo_tail_packed) (void)hipFree(m->geo_tail_packed);
-    if (m->hier_grids) (void)hipFree(m->hier_grids);
-    if (m->hier_idx) (void)hipFree(m->hier_idx);
-    if (m->hier_val) (void)hipFree(m->hier_val);
-    for (char* p : {m->kv_q, m->kv_k, m->kv_vt, m->kv_idx, m->kv_v})
-        if (p) (void)hipFree(p);
-    delete m;
+    delete m;      // the buffers go with their DevBuf members
 }
 
 static int model_create(Ctx* ctx, const r3g_model_config* cfg) {
@@ -1316,12 +1279,10 @@ static int model_create(Ctx* ctx, const r3g_model_config* cfg) {
                  o_k = carve(n_kv * 2), o_vt = carve(n_kv * 2), o_cat = carve(n_cat * 2), o_hid = carve(n_hid * 2),
                  o_inb = carve(n_inb * 2), o_small = carve(n_small * 4), o_z = carve(n_z * 4), o_gk = carve(n_geo * 2),
                  o_gv = carve(n_geo * 2);
-    hipError_t e = hipMalloc((void**)&m->arena, off);
-    if (e != hipSuccess) { model_free(m); return hip_fail(e, "hipMalloc(model arena)"); }
-    m->arena_bytes = off;
-    e = hipMemset(m->arena, 0, off);  // padded rows / columns must start finite
+    if (const int rc = m->arena.grow(off, nullptr, "model arena")) { model_free(m); return rc; }
+    const hipError_t e = hipMemset(m->arena.p, 0, off);  // padded rows / columns must start finite
     if (e != hipSuccess) { model_free(m); return hip_fail(e, "hipMemset(model arena)"); }
-    char* a = m->arena;
+    char* a = m->arena.p;
     m->f32a = (float*)(a + o_f32a); m->xn = (uint16_t*)(a + o_xn); m->qkv = (uint16_t*)(a + o_qkv);
     m->Q = (uint16_t*)(a + o_q); m->K = (uint16_t*)(a + o_k); m->Vt = (uint16_t*)(a + o_vt);
     m->cat = (uint16_t*)(a + o_cat); m->hid = (uint16_t*)(a + o_hid); m->inb = (uint16_t*)(a + o_inb);
@@ -1508,6 +1469,7 @@ int r3g_get_counter(const char* name, int64_t* value) {
     else if (!strcmp(name, "geo_narrow_passes")) *value = g_geo_narrow_passes;
     else if (!strcmp(name, "geo_lnf_passes")) *value = g_geo_lnf_passes;
     else if (!strcmp(name, "geo_lnd_passes")) *value = g_geo_lnd_passes;
+    else if (!strcmp(name, "device_bytes_live")) *value = g_device_bytes_live.load();
     else if (!strcmp(name, "meshdist_tests")) *value = meshdist_tests_total();
     else if (!strcmp(name, "meshinside_tests")) *value = meshinside_tests_total();
     else if (!strcmp(name, "meshfit_steps")) *value = meshfit_steps_total();
@@ -1535,8 +1497,7 @@ int r3g_model_trim(r3g_ctx* ctx) {
     m->kv_last_q = nullptr;
     if (gq.x0) {
         R3G_TRY(hipDeviceSynchronize());
-        (void)hipFree(gq.x0);
-        gq.x0 = nullptr;
+        gq.x0.release();
         gq.Q = nullptr;
         gq.passes = 0;
         gq.built.clear();
@@ -1633,8 +1594,8 @@ int r3g_grid_query_hier(r3g_ctx* ctx, double bound, int octree_resolution, doubl
             off[(size_t)l] = need;
             need += ((size_t)pts(lv[(size_t)l]) * 4 + 255) & ~(size_t)255;
         }
-        R3G_RC(c->reserve(&m->hier_grids, &m->hier_grids_bytes, need, "hipMalloc(hier level grids)"));
-        float* G = reinterpret_cast<float*>(m->hier_grids + off[0]);
+        R3G_RC(m->hier_grids.grow(need, s, "hier level grids"));
+        float* G = reinterpret_cast<float*>(m->hier_grids.p + off[0]);
         R3G_RC(grid_query(*m, bound, lv[0], G, 0, pts(lv[0]), s, nullptr, false));
         evaluated[0] = pts(lv[0]);
         for (int l = 1; l < L; ++l) {
@@ -1642,14 +1603,13 @@ int r3g_grid_query_hier(r3g_ctx* ctx, double bound, int octree_resolution, doubl
             int64_t count = 0;
             R3G_RC(hier_select(c, G, lv[(size_t)l - 1] + 1, mc_level, band, finest ? 1 : 0, &count, s));
             if (count) {
-                R3G_RC(c->reserve(&m->hier_idx, &m->hier_idx_bytes, (size_t)count * 4, "hipMalloc(hier index list)"));
-                R3G_RC(c->reserve(&m->hier_val, &m->hier_val_bytes, (size_t)count * 4, "hipMalloc(hier values)"));
-                R3G_RC(hier_indices(c, reinterpret_cast<int32_t*>(m->hier_idx), s));
-                R3G_RC(grid_query(*m, bound, lv[(size_t)l], reinterpret_cast<float*>(m->hier_val), 0, count, s,
-                                  reinterpret_cast<const int32_t*>(m->hier_idx), false));
+                R3G_RC(m->hier_idx.grow((size_t)count * 4, s, "hier index list"));
+                R3G_RC(m->hier_val.grow((size_t)count * 4, s, "hier values"));
+                R3G_RC(hier_indices(c, m->hier_idx.as<int32_t>(), s));
+                R3G_RC(grid_query(*m, bound, lv[(size_t)l], m->hier_val.as<float>(), 0, count, s, m->hier_idx.as<const int32_t>(), false));
             }
-            float* F = finest ? d_grid : reinterpret_cast<float*>(m->hier_grids + off[(size_t)l]);
-            R3G_RC(hier_merge(c, G, reinterpret_cast<const float*>(m->hier_val), F, s));
+            float* F = finest ? d_grid : reinterpret_cast<float*>(m->hier_grids.p + off[(size_t)l]);
+            R3G_RC(hier_merge(c, G, m->hier_val.as<const float>(), F, s));
             evaluated[(size_t)l] = count;
             G = F;
         }
@@ -1805,12 +1765,12 @@ int r3g_op_kv_gather(const uint16_t* d_k, const uint16_t* d_vt, int lk, int lk_p
                      uint16_t* d_k_out, uint16_t* d_vt_out, void* stream) {
     if (!d_k || !d_vt || !d_idx || !d_k_out || !d_vt_out || lk < 1 || heads < 1) return fail(R3G_ERR_INVALID, "r3g_op_kv_gather: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    uint16_t* v = nullptr;      // the row-major copy of V the model keeps per object: here per call (a test hook; synchronous)
-    R3G_TRY(hipMalloc((void**)&v, 2 * (size_t)heads * lk * 64));
+    DevBuf tmp;      // the row-major copy of V the model keeps per object: here per call (a test hook; synchronous)
+    R3G_RC(tmp.grow(2 * (size_t)heads * lk * 64, s, "r3g_op_kv_gather row-major V"));
+    uint16_t* v = tmp.as<uint16_t>();
     hipError_t e = kvsel_vrows_launch(d_vt, lk, lk_pad, heads, v, s);
     if (e == hipSuccess) e = kvsel_gather_launch(d_k, v, lk, lk_pad, heads, d_idx, groups, topk, d_k_out, d_vt_out, s);
-    const hipError_t e2 = hipStreamSynchronize(s);
-    (void)hipFree(v);
+    const hipError_t e2 = hipStreamSynchronize(s);      // (before tmp goes)
     if (e != hipSuccess) return hip_fail(e, "r3g_op_kv_gather");
     if (e2 != hipSuccess) return hip_fail(e2, "r3g_op_kv_gather");
     return R3G_OK;
@@ -1823,8 +1783,9 @@ int r3g_op_geo_tail(const uint16_t* d_cat, const uint16_t* d_x0, int n, int hidd
     if (!d_cat || !d_x0 || !d_w_proj || !d_w_fc || !d_w_fp || !d_logits || n < 1 || !geo_tail_supported(GEO_TAIL_WIDTH, hidden))
         return fail(R3G_ERR_INVALID, "r3g_op_geo_tail: bad argument (width 256, hidden 256 | 512 | 1024, n >= 1)");
     hipStream_t s = (hipStream_t)stream;
-    void* packed = nullptr;      // the fragment stream the model keeps per grid query: here per call (a test hook; synchronous)
-    R3G_TRY(hipMalloc(&packed, geo_tail_packed_bytes(hidden)));
+    DevBuf tmp;      // the fragment stream the model keeps per grid query: here per call (a test hook; synchronous)
+    R3G_RC(tmp.grow(geo_tail_packed_bytes(hidden), s, "r3g_op_geo_tail fragments"));
+    void* packed = tmp.p;
     hipError_t e = geo_tail_pack_launch(d_w_proj, 256, d_w_fc, 256, d_w_fp, hidden, hidden, packed, s);
     if (e == hipSuccess) {
         GeoTailArgs ta{};
@@ -1834,8 +1795,7 @@ int r3g_op_geo_tail(const uint16_t* d_cat, const uint16_t* d_x0, int n, int hidd
         ta.hidden = hidden; ta.n = n; ta.out = d_logits;
         e = geo_tail_launch(ta, s);
     }
-    const hipError_t e2 = hipStreamSynchronize(s);
-    (void)hipFree(packed);
+    const hipError_t e2 = hipStreamSynchronize(s);      // (before tmp goes)
     if (e != hipSuccess) return hip_fail(e, "r3g_op_geo_tail");
     if (e2 != hipSuccess) return hip_fail(e2, "r3g_op_geo_tail");
     return R3G_OK;
@@ -1950,11 +1910,10 @@ int r3g_op_group_norm(const float* d_x, int rows, int c, int groups, const float
     else if (d_addv && (add_stride < c || (add_stride & 3) || op_misaligned(d_addv, 15))) bad = "addv 16-byte aligned, add_stride % 4 == 0, add_stride >= c";
     if (bad) return fail(R3G_ERR_INVALID, "r3g_op_group_norm: needs %s", bad);
     hipStream_t s = (hipStream_t)stream;
-    double* partial = nullptr;      // the workspace the UNet keeps per model: here per call (a test hook; synchronous)
-    R3G_TRY(hipMalloc((void**)&partial, sizeof(double) * (size_t)nb * ((size_t)group_norm_blocks(rows) * groups * 2 + groups)));
-    hipError_t e = group_norm_launch(d_x, rows, c, groups, d_gamma, d_beta, eps, do_silu, d_y, partial, s, nb, d_addv, add_stride);
-    const hipError_t e2 = hipStreamSynchronize(s);
-    (void)hipFree(partial);
+    DevBuf tmp;      // the workspace the UNet keeps per model: here per call (a test hook; synchronous)
+    R3G_RC(tmp.grow(sizeof(double) * (size_t)nb * ((size_t)group_norm_blocks(rows) * groups * 2 + groups), s, "r3g_op_group_norm partial sums"));
+    hipError_t e = group_norm_launch(d_x, rows, c, groups, d_gamma, d_beta, eps, do_silu, d_y, tmp.as<double>(), s, nb, d_addv, add_stride);
+    const hipError_t e2 = hipStreamSynchronize(s);      // (before tmp goes)
     if (e != hipSuccess) return hip_fail(e, "r3g_op_group_norm");
     if (e2 != hipSuccess) return hip_fail(e2, "r3g_op_group_norm");
     return R3G_OK;
@@ -2004,7 +1963,7 @@ int r3g_kv_selection_last(r3g_ctx* ctx, int32_t* d_idx, int64_t capacity, int* g
     if (k) *k = m->kv_last_k;
     if (d_idx) {
         if (capacity < count) return fail(R3G_ERR_INVALID, "r3g_kv_selection_last: the table has %lld entries, capacity %lld", (long long)count, (long long)capacity);
-        R3G_TRY(hipMemcpyAsync(d_idx, m->kv_idx, 4 * (size_t)count, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        R3G_TRY(hipMemcpyAsync(d_idx, m->kv_idx.p, 4 * (size_t)count, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return R3G_OK;
 }

@@ -28,17 +28,20 @@ int hip_fail(hipError_t e, const char* what) {
     return fail(R3G_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
-int Ctx::reserve(char** buf, size_t* have, size_t need, const char* what) {
-    if (*have >= need) return R3G_OK;
-    if (*buf) {
-        hipError_t e = hipFree(*buf);
-        *buf = nullptr;
-        *have = 0;
-        if (e != hipSuccess) return hip_fail(e, what);
-    }
-    hipError_t e = hipMalloc((void**)buf, need);
-    if (e != hipSuccess) return hip_fail(e, what);
-    *have = need;
+// "meshdist_fill", "meshinside pairs": a step's or a buffer's name for the error text, with the user's name in it
+struct Named {
+    char s[64];
+    Named(const char* fmt, const char* who) { snprintf(s, sizeof s, fmt, who); }
+    operator const char*() const { return s; }
+};
+
+// the read-back of a tiny device result: n bytes through a pinned buffer into *out, behind everything queued on the stream
+static int read_back(const DevBuf& pinned, const char* dev, void* out, size_t n, const char* name, hipStream_t s) {
+    hipError_t e = hipMemcpyAsync(pinned.p, dev, n, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hip_fail(e, Named("hipMemcpyAsync(%s)", name));
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, Named("hipStreamSynchronize(%s)", name));
+    memcpy(out, pinned.p, n);
     return R3G_OK;
 }
 
@@ -49,16 +52,14 @@ int hier_select(Ctx* c, const float* d_coarse, int n_coarse, double level, doubl
     if (!(band >= 0.0)) return fail(R3G_ERR_INVALID, "r3g_hier_select: band must be >= 0");
     HierLayout lay;
     const size_t need = hier_workspace_bytes(n_coarse, &lay);
-    int rc = c->reserve(&c->hier_ws, &c->hier_ws_bytes, need, "hipMalloc(hier workspace)");
+    int rc = c->hier_ws.grow(need, s, "hier workspace");
     if (rc) return rc;
-    hipError_t e = hier_select_launch(d_coarse, level, band, is_finest, c->hier_ws, lay, s);
+    hipError_t e = hier_select_launch(d_coarse, level, band, is_finest, c->hier_ws.p, lay, s);
     if (e != hipSuccess) return hip_fail(e, "hier_select_launch");
-    e = hipMemcpyAsync(c->h_small, c->hier_ws + lay.off_small, 8, hipMemcpyDeviceToHost, s);    // the level's one read-back
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(hier count)");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(hier select)");
+    unsigned long long n = 0;
+    if ((rc = read_back(c->h_small, c->hier_ws.p + lay.off_small, &n, 8, "hier select", s))) return rc;    // the level's one read-back
     c->hier_lay = lay;
-    c->hier_count = (int64_t) * (const unsigned long long*)c->h_small;
+    c->hier_count = (int64_t)n;
     c->hier_selected = true;
     *count = c->hier_count;
     return R3G_OK;
@@ -68,7 +69,7 @@ int hier_indices(Ctx* c, int32_t* d_idx_out, hipStream_t s) {
     if (!c->hier_selected) return fail(R3G_ERR_STATE, "r3g_hier_indices: no successful r3g_hier_select precedes this call");
     if (c->hier_count == 0) return R3G_OK;
     if (!d_idx_out) return fail(R3G_ERR_INVALID, "r3g_hier_indices: null argument");
-    hipError_t e = hier_indices_launch(c->hier_ws, c->hier_lay, d_idx_out, s);
+    hipError_t e = hier_indices_launch(c->hier_ws.p, c->hier_lay, d_idx_out, s);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "hier_indices_launch");
 }
 
@@ -76,37 +77,23 @@ int hier_merge(Ctx* c, const float* d_coarse, const float* d_values, float* d_fi
     if (!c->hier_selected) return fail(R3G_ERR_STATE, "r3g_hier_merge: no successful r3g_hier_select precedes this call");
     if (!d_coarse || !d_fine_out || (c->hier_count && !d_values)) return fail(R3G_ERR_INVALID, "r3g_hier_merge: null argument");
     if ((uintptr_t)d_fine_out % 16) return fail(R3G_ERR_INVALID, "r3g_hier_merge: d_fine_out must be 16-byte aligned");
-    hipError_t e = hier_merge_launch(c->hier_ws, c->hier_lay, d_coarse, d_values, d_fine_out, s);
+    hipError_t e = hier_merge_launch(c->hier_ws.p, c->hier_lay, d_coarse, d_values, d_fine_out, s);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "hier_merge_launch");
 }
 
 int hier_unsafe_cells(Ctx* c, const float* d_fine, double level, int64_t* count, hipStream_t s) {
     if (!c->hier_selected) return fail(R3G_ERR_STATE, "hier_unsafe_cells: no successful select precedes this call");
-    hipError_t e = hier_unsafe_launch(c->hier_ws, c->hier_lay, d_fine, level, s);
+    hipError_t e = hier_unsafe_launch(c->hier_ws.p, c->hier_lay, d_fine, level, s);
     if (e != hipSuccess) return hip_fail(e, "hier_unsafe_launch");
-    e = hipMemcpyAsync(c->h_small, c->hier_ws + c->hier_lay.off_small + 8, 8, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(hier unsafe cells)");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(hier unsafe cells)");
-    *count = (int64_t) * (const unsigned long long*)c->h_small;
+    unsigned long long n = 0;
+    if (const int rc = read_back(c->h_small, c->hier_ws.p + c->hier_lay.off_small + 8, &n, 8, "hier unsafe cells", s)) return rc;
+    *count = (int64_t)n;
     return R3G_OK;
 }
 
 // ---- grids in CSR form: the mesh distance's cells and the point-in-mesh columns ----------------------
-// "meshdist_fill", "hipMalloc(meshinside pairs)": a step's name for the error text, with the user's name in it
-struct Named {
-    char s[64];
-    Named(const char* fmt, const char* who) { snprintf(s, sizeof s, fmt, who); }
-    operator const char*() const { return s; }
-};
-
 static int grid_small(Ctx* c, const char* ws, const GridCsrLayout& lay, const char* who, hipStream_t s, GridCsrSmall* out) {
-    hipError_t e = hipMemcpyAsync(c->h_small, ws + lay.off_small, sizeof(GridCsrSmall), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, Named("hipMemcpyAsync(%s)", who));
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, Named("hipStreamSynchronize(%s)", who));
-    memcpy(out, c->h_small, sizeof(GridCsrSmall));
-    return R3G_OK;
+    return read_back(c->h_small, ws + lay.off_small, out, sizeof(GridCsrSmall), who, s);
 }
 
 // what the build driver needs to know of its user; `records` launches the user's records kernel
@@ -150,13 +137,13 @@ static int grid_csr_build(Ctx* c, GridCsrState<U::D>* st, const U& user, const f
     const int initial = U::initial_resolution(n_faces);
     GridCsrLayout lay;
     const size_t need = grid_csr_workspace_bytes(n_faces, U::record_bytes, r3g_grid::cells<D>(resolution ? resolution : initial), &lay);
-    int rc = c->reserve(&st->ws, &st->ws_bytes, need, Named("hipMalloc(%s workspace)", who));
+    int rc = st->ws.grow(need, s, Named("%s workspace", who));
     if (rc) return rc;
     st->lay = lay;
-    hipError_t e = user.records(st->ws, lay, d_verts, n_verts, d_faces, n_faces, s);
+    hipError_t e = user.records(st->ws.p, lay, d_verts, n_verts, d_faces, n_faces, s);
     if (e != hipSuccess) return hip_fail(e, Named("%s_records", who));
     GridCsrSmall sm;
-    if ((rc = grid_small(c, st->ws, lay, who, s, &sm))) return rc;
+    if ((rc = grid_small(c, st->ws.p, lay, who, s, &sm))) return rc;
     // (-2 by the contract of include/r3g.h: found on the device, before anything is read through the index)
     if (sm.bad_index) return fail(-2, "r3g_%s_build: a face index lies outside [0, %lld)", who, (long long)n_verts);
     if ((int64_t)sm.skipped >= n_faces)
@@ -166,17 +153,17 @@ static int grid_csr_build(Ctx* c, GridCsrState<U::D>* st, const U& user, const f
     r3g_grid::GridN<D> g;
     int64_t pairs = 0;
     rc = r3g_grid::choose_resolution(lo, hi, resolution, initial, n_faces, [&](const r3g_grid::GridN<D>& cand, int64_t* n) {
-        e = grid_csr_count_pairs(st->ws, lay, n_faces, cand, s);
+        e = grid_csr_count_pairs(st->ws.p, lay, n_faces, cand, s);
         if (e != hipSuccess) return hip_fail(e, Named("%s_count_pairs", who));
-        const int r = grid_small(c, st->ws, lay, who, s, &sm);
+        const int r = grid_small(c, st->ws.p, lay, who, s, &sm);
         *n = (int64_t)sm.pairs;
         return r;
     }, &g, &pairs);
     if (rc) return rc;
     if (pairs >= (1ll << 31))
         return fail(R3G_ERR_INVALID, "r3g_%s_build: %lld (face, %s) pairs at resolution %d; force a lower one", who, (long long)pairs, U::cell, g.res);
-    if ((rc = c->reserve(&st->pairs, &st->pairs_bytes, 4 * (size_t)pairs, Named("hipMalloc(%s pairs)", who)))) return rc;
-    e = grid_csr_fill(st->ws, lay, n_faces, g, (int32_t*)st->pairs, s);
+    if ((rc = st->pairs.grow(4 * (size_t)pairs, s, Named("%s pairs", who)))) return rc;
+    e = grid_csr_fill(st->ws.p, lay, n_faces, g, (int32_t*)st->pairs.p, s);
     if (e != hipSuccess) return hip_fail(e, Named("%s_fill", who));
     e = hipStreamSynchronize(s);      // the caller may free its mesh buffers, and a fault would surface here
     if (e != hipSuccess) return hip_fail(e, Named("hipStreamSynchronize(%s_fill)", who));
@@ -221,16 +208,15 @@ static int surf_count(Ctx* c, SurfState* st, const float* d_grid, int n0, int n1
     st->counted = false;
     SurfWorkspaceLayout lay;
     const size_t need = U::workspace_bytes(n0, n1, n2, &lay);
-    int rc = c->reserve(&st->ws, &st->ws_bytes, need, Named("hipMalloc(%s workspace)", who));
+    int rc = st->ws.grow(need, s, Named("%s workspace", who));
     if (rc) return rc;
-    hipError_t e = U::count_launch(d_grid, n0, n1, n2, level, flag, st->ws, lay, s);
+    hipError_t e = U::count_launch(d_grid, n0, n1, n2, level, flag, st->ws.p, lay, s);
     if (e != hipSuccess) return hip_fail(e, Named("%s_count_launch", who));
-    e = hipMemcpyAsync(c->h_small, st->ws + lay.off_small, 64, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, Named("hipMemcpyAsync(%s totals)", who));
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, Named("hipStreamSynchronize(%s count)", who));
-    const unsigned status = *(const unsigned*)c->h_small;
-    const unsigned long long* totals = (const unsigned long long*)c->h_small + 2;      // {vertices, triangles or quads, non-empty blocks} @16
+    unsigned long long small[8];
+    if ((rc = read_back(c->h_small, st->ws.p + lay.off_small, small, 64, Named("%s count", who), s))) return rc;
+    unsigned status;                                     // @0
+    memcpy(&status, small, sizeof status);
+    const unsigned long long* totals = small + 2;        // {vertices, triangles or quads, non-empty blocks} @16
     *n_verts = (int64_t)totals[0];
     *n_faces = (int64_t)(U::faces_per_item * totals[1]);
     // numpy: level < vol.min() or level > vol.max(); a NaN anywhere makes both comparisons false
@@ -250,7 +236,7 @@ template <class U>
 static int surf_emit(SurfState* st, float* d_verts, int32_t* d_faces, const double* xform, int reverse_faces, hipStream_t s) {
     const char* who = U::who;
     if (!st->counted) return fail(R3G_ERR_STATE, "r3g_%s_emit: no successful r3g_%s_count precedes this call", who, who);
-    hipError_t e = U::emit_launch(st->grid, st->n[0], st->n[1], st->n[2], st->level, st->ws, st->lay, d_verts, d_faces, xform,
+    hipError_t e = U::emit_launch(st->grid, st->n[0], st->n[1], st->n[2], st->level, st->ws.p, st->lay, d_verts, d_faces, xform,
                                   reverse_faces, s);
     if (e != hipSuccess) return hip_fail(e, Named("%s_emit_launch", who));
     return R3G_OK;
@@ -286,10 +272,9 @@ int r3g_create(int device, r3g_ctx** out) {
     c->device = device;
     c->num_cu = prop.multiProcessorCount;
     gemm_set_auto_rule(-1, c->num_cu);
-    e = hipHostMalloc((void**)&c->h_small, 64, hipHostMallocDefault);
-    if (e != hipSuccess) {
+    if (const int rc = c->h_small.grow(64, nullptr, "read-back buffer")) {
         delete c;
-        return hip_fail(e, "hipHostMalloc");
+        return rc;
     }
     *out = reinterpret_cast<r3g_ctx*>(c);
     return R3G_OK;
@@ -298,33 +283,12 @@ int r3g_create(int device, r3g_ctx** out) {
 void r3g_destroy(r3g_ctx* ctx) {
     if (!ctx) return;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    (void)hipSetDevice(c->device);
-    if (c->mc.ws) (void)hipFree(c->mc.ws);
-    if (c->dmc.ws) (void)hipFree(c->dmc.ws);
-    if (c->mesh_ws) (void)hipFree(c->mesh_ws);
-    if (c->meshdist.ws) (void)hipFree(c->meshdist.ws);
-    if (c->meshdist.pairs) (void)hipFree(c->meshdist.pairs);
-    if (c->meshfit_ws) (void)hipFree(c->meshfit_ws);
-    if (c->h_fit) (void)hipHostFree(c->h_fit);
-    if (c->meshinside.ws) (void)hipFree(c->meshinside.ws);
-    if (c->meshinside.pairs) (void)hipFree(c->meshinside.pairs);
-    if (c->cloud.ws) (void)hipFree(c->cloud.ws);
-    if (c->cloud.pairs) (void)hipFree(c->cloud.pairs);
-    if (c->recon.channels) (void)hipFree(c->recon.channels);
-    if (c->recon.levels) (void)hipFree(c->recon.levels);
-    if (c->orient_ws) (void)hipFree(c->orient_ws);
-    if (c->dbscan_ws) (void)hipFree(c->dbscan_ws);
+    (void)hipSetDevice(c->device);      // before anything is freed: the buffers below belong to this device
     if (c->dbscan_ev_made)
         for (hipEvent_t e : c->dbscan_ev) (void)hipEventDestroy(e);
-    if (c->meshtopo_ws) (void)hipFree(c->meshtopo_ws);
-    if (c->h_topo) (void)hipHostFree(c->h_topo);
-    if (c->meshfill_ws) (void)hipFree(c->meshfill_ws);
-    if (c->tex_ws) (void)hipFree(c->tex_ws);
-    if (c->hier_ws) (void)hipFree(c->hier_ws);
-    if (c->h_small) (void)hipHostFree(c->h_small);
     c->release_model();
     c->release_unet();
-    delete c;
+    delete c;                           // every buffer of the context goes with its DevBuf member
 }
 
 int r3g_mc_count(r3g_ctx* ctx, const float* d_grid, int n0, int n1, int n2, double level, int use_classic,
@@ -386,9 +350,9 @@ int r3g_mesh_remove_floaters(r3g_ctx* ctx, float* d_verts, int64_t* n_verts, int
     int rc = mesh_args("r3g_mesh_remove_floaters", ctx, d_verts, n_verts, d_faces, n_faces);
     if (rc) return rc;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    rc = c->reserve(&c->mesh_ws, &c->mesh_ws_bytes, mesh_workspace_bytes(*n_verts, *n_faces, 0), "hipMalloc(mesh workspace)");
+    rc = c->mesh_ws.grow(mesh_workspace_bytes(*n_verts, *n_faces, 0), (hipStream_t)stream, "mesh workspace");
     if (rc) return rc;
-    hipError_t e = mesh_remove_floaters(c->mesh_ws, c->mesh_ws_bytes, (unsigned*)c->h_small, d_verts, n_verts, d_faces,
+    hipError_t e = mesh_remove_floaters(c->mesh_ws.p, c->mesh_ws.bytes, c->h_small.as<unsigned>(), d_verts, n_verts, d_faces,
                                         n_faces, min_ratio, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "mesh_remove_floaters");
 }
@@ -398,9 +362,9 @@ int r3g_mesh_remove_degenerate(r3g_ctx* ctx, float* d_verts, int64_t* n_verts, i
     int rc = mesh_args("r3g_mesh_remove_degenerate", ctx, d_verts, n_verts, d_faces, n_faces);
     if (rc) return rc;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    rc = c->reserve(&c->mesh_ws, &c->mesh_ws_bytes, mesh_workspace_bytes(*n_verts, *n_faces, 0), "hipMalloc(mesh workspace)");
+    rc = c->mesh_ws.grow(mesh_workspace_bytes(*n_verts, *n_faces, 0), (hipStream_t)stream, "mesh workspace");
     if (rc) return rc;
-    hipError_t e = mesh_remove_degenerate(c->mesh_ws, c->mesh_ws_bytes, (unsigned*)c->h_small, d_verts, n_verts, d_faces,
+    hipError_t e = mesh_remove_degenerate(c->mesh_ws.p, c->mesh_ws.bytes, c->h_small.as<unsigned>(), d_verts, n_verts, d_faces,
                                           n_faces, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "mesh_remove_degenerate");
 }
@@ -411,9 +375,9 @@ int r3g_mesh_reduce_faces(r3g_ctx* ctx, float* d_verts, int64_t* n_verts, int32_
     if (rc) return rc;
     if (max_faces < 1 || max_faces > 200000000) return fail(R3G_ERR_INVALID, "r3g_mesh_reduce_faces: max_faces out of range");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    rc = c->reserve(&c->mesh_ws, &c->mesh_ws_bytes, mesh_workspace_bytes(*n_verts, *n_faces, 0), "hipMalloc(mesh workspace)");
+    rc = c->mesh_ws.grow(mesh_workspace_bytes(*n_verts, *n_faces, 0), (hipStream_t)stream, "mesh workspace");
     if (rc) return rc;
-    hipError_t e = mesh_reduce_faces(c->mesh_ws, c->mesh_ws_bytes, (unsigned*)c->h_small, d_verts, n_verts, d_faces,
+    hipError_t e = mesh_reduce_faces(c->mesh_ws.p, c->mesh_ws.bytes, c->h_small.as<unsigned>(), d_verts, n_verts, d_faces,
                                      n_faces, max_faces, nullptr, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "mesh_reduce_faces");
 }
@@ -425,10 +389,9 @@ int r3g_mesh_cluster_faces(r3g_ctx* ctx, float* d_verts, int64_t* n_verts, int32
     if (max_faces < 1 || max_faces > 200000000) return fail(R3G_ERR_INVALID, "r3g_mesh_cluster_faces: max_faces out of range");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     const int64_t r = mesh_reduce_initial_res(max_faces);
-    rc = c->reserve(&c->mesh_ws, &c->mesh_ws_bytes, mesh_workspace_bytes(*n_verts, *n_faces, r * r * r),
-                    "hipMalloc(mesh workspace)");
+    rc = c->mesh_ws.grow(mesh_workspace_bytes(*n_verts, *n_faces, r * r * r), (hipStream_t)stream, "mesh workspace");
     if (rc) return rc;
-    hipError_t e = mesh_cluster_faces(c->mesh_ws, c->mesh_ws_bytes, (unsigned*)c->h_small, d_verts, n_verts, d_faces,
+    hipError_t e = mesh_cluster_faces(c->mesh_ws.p, c->mesh_ws.bytes, c->h_small.as<unsigned>(), d_verts, n_verts, d_faces,
                                       n_faces, max_faces, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "mesh_cluster_faces");
 }
@@ -450,11 +413,11 @@ int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, fl
     if (n_points == 0) return R3G_OK;
     if (!d_points || !d_dist2 || !d_face) return fail(R3G_ERR_INVALID, "r3g_meshdist_query: null buffer");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = meshdist_query(c->meshdist.ws, c->meshdist.lay, c->meshdist.grid, (const int32_t*)c->meshdist.pairs, d_points,
+    hipError_t e = meshdist_query(c->meshdist.ws.p, c->meshdist.lay, c->meshdist.grid, c->meshdist.pairs.as<const int32_t>(), d_points,
                                   n_points, d_dist2, d_face, s);
     if (e != hipSuccess) return hip_fail(e, "meshdist_query");
     GridCsrSmall sm;
-    int rc = grid_small(c, c->meshdist.ws, c->meshdist.lay, "meshdist", s, &sm);
+    int rc = grid_small(c, c->meshdist.ws.p, c->meshdist.lay, "meshdist", s, &sm);
     if (rc) return rc;
     meshdist_add_tests((int64_t)sm.tests);
     return R3G_OK;
@@ -477,13 +440,13 @@ int r3g_cloud_build(r3g_ctx* ctx, const float* d_points, int64_t n_points, int r
     const int res_most = resolution ? resolution : r3g_cl::auto_resolution(n_points, r3g_cl::kPointsPerCell);
     GridCsrLayout lay;
     const size_t need = grid_csr_workspace_bytes(n_points, sizeof(r3g_cl::Pt), r3g_grid::cells<3>(res_most), &lay);
-    int rc = c->reserve(&st->ws, &st->ws_bytes, need, "hipMalloc(cloud workspace)");
+    int rc = st->ws.grow(need, s, "cloud workspace");
     if (rc) return rc;
     st->lay = lay;
-    hipError_t e = cloud_records(st->ws, lay, d_points, n_points, s);
+    hipError_t e = cloud_records(st->ws.p, lay, d_points, n_points, s);
     if (e != hipSuccess) return hip_fail(e, "cloud_records");
     GridCsrSmall sm;
-    if ((rc = grid_small(c, st->ws, lay, "cloud", s, &sm))) return rc;
+    if ((rc = grid_small(c, st->ws.p, lay, "cloud", s, &sm))) return rc;
     if ((int64_t)sm.skipped >= n_points)
         return fail(R3G_ERR_INVALID, "r3g_cloud_build: every point has a non-finite coordinate (%lld skipped)", (long long)sm.skipped);
     const int64_t usable = n_points - (int64_t)sm.skipped;
@@ -491,8 +454,8 @@ int r3g_cloud_build(r3g_ctx* ctx, const float* d_points, int64_t n_points, int r
     for (int a = 0; a < 3; ++a) lo[a] = r3g_grid::dec_float(sm.box[a]), hi[a] = r3g_grid::dec_float(sm.box[3 + a]);
     const int res = resolution ? resolution : r3g_cl::auto_resolution(usable, r3g_cl::kPointsPerCell);
     const r3g_cl::Grid g = r3g_grid::make_grid(lo, hi, res);
-    if ((rc = c->reserve(&st->pairs, &st->pairs_bytes, sizeof(r3g_cl::Pt) * (size_t)usable, "hipMalloc(cloud points)"))) return rc;
-    e = cloud_fill(st->ws, lay, n_points, g, (r3g_cl::Pt*)st->pairs, s);
+    if ((rc = st->pairs.grow(sizeof(r3g_cl::Pt) * (size_t)usable, s, "cloud points"))) return rc;
+    e = cloud_fill(st->ws.p, lay, n_points, g, st->pairs.as<r3g_cl::Pt>(), s);
     if (e != hipSuccess) return hip_fail(e, "cloud_fill");
     e = hipStreamSynchronize(s);      // the caller may free its points, and a fault would surface here
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(cloud_fill)");
@@ -512,11 +475,11 @@ int r3g_cloud_knn(r3g_ctx* ctx, const float* d_queries, int64_t n_queries, int k
     if (n_queries == 0) return R3G_OK;
     if (!d_queries || !d_dist2 || !d_index) return fail(R3G_ERR_INVALID, "r3g_cloud_knn: null buffer");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = cloud_knn(c->cloud.ws, c->cloud.lay, c->cloud.grid, (const r3g_cl::Pt*)c->cloud.pairs, d_queries, n_queries, k, d_dist2,
+    hipError_t e = cloud_knn(c->cloud.ws.p, c->cloud.lay, c->cloud.grid, c->cloud.pairs.as<const r3g_cl::Pt>(), d_queries, n_queries, k, d_dist2,
                              d_index, s);
     if (e != hipSuccess) return hip_fail(e, "cloud_knn");
     GridCsrSmall sm;
-    int rc = grid_small(c, c->cloud.ws, c->cloud.lay, "cloud", s, &sm);
+    int rc = grid_small(c, c->cloud.ws.p, c->cloud.lay, "cloud", s, &sm);
     if (rc) return rc;
     cloud_add_tests((int64_t)sm.tests);
     return R3G_OK;
@@ -534,16 +497,10 @@ int r3g_cloud_orient(r3g_ctx* ctx, const float* d_points, const float* d_normals
         return fail(R3G_ERR_INVALID, "r3g_cloud_orient: resolution outside [0, %d] (0 = automatic)", r3g_cl::kMaxRes);
     if (!d_points || !d_normals || !d_sign || !d_tree) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: null buffer");
     OrientLayout lay;
-    int rc = c->reserve(&c->orient_ws, &c->orient_ws_bytes, orient_workspace_bytes(n_points, k, &lay), "hipMalloc(orient workspace)");
+    int rc = c->orient_ws.grow(orient_workspace_bytes(n_points, k, &lay), s, "orient workspace");
     if (rc) return rc;
-    char* ws = c->orient_ws;
-    auto small = [&](OrientSmall* out) -> int {
-        hipError_t e = hipMemcpyAsync(c->h_small, ws + lay.off_small, sizeof(OrientSmall), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_fail(e, "r3g_cloud_orient: read-back");
-        memcpy(out, c->h_small, sizeof(OrientSmall));
-        return R3G_OK;
-    };
+    char* ws = c->orient_ws.p;
+    auto small = [&](OrientSmall* out) { return read_back(c->h_small, ws + lay.off_small, out, sizeof(OrientSmall), "orient", s); };
     static_assert(sizeof(OrientSmall) <= 64, "the pinned read-back buffer");
     hipError_t e = orient_prepare(ws, lay, d_points, d_normals, n_points, s);
     if (e != hipSuccess) return hip_fail(e, "orient_prepare");
@@ -602,22 +559,22 @@ int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, doub
         c->dbscan_ev_made = true;
     }
     DbscanLayout dl;
-    int rc = c->reserve(&c->dbscan_ws, &c->dbscan_ws_bytes, dbscan_workspace_bytes(n_points, &dl), "hipMalloc(dbscan workspace)");
+    int rc = c->dbscan_ws.grow(dbscan_workspace_bytes(n_points, &dl), s, "dbscan workspace");
     if (rc) return rc;
     // the automatic resolution can only fall when points are skipped: the workspace sized for all of them is enough
     const int res_most = resolution ? resolution : r3g_db::auto_resolution_most(n_points);
     GridCsrLayout lay;
     const size_t need = grid_csr_workspace_bytes(n_points, sizeof(r3g_cl::Pt), r3g_grid::cells<3>(res_most), &lay);
-    if ((rc = c->reserve(&st->ws, &st->ws_bytes, need, "hipMalloc(cloud workspace)"))) return rc;
+    if ((rc = st->ws.grow(need, s, "cloud workspace"))) return rc;
     st->lay = lay;
     int64_t launches = 0;
     hipError_t e = hipEventRecord(c->dbscan_ev[0], s);
     if (e != hipSuccess) return hip_fail(e, "hipEventRecord(dbscan)");
-    if ((e = dbscan_begin(c->dbscan_ws, dl, n_points, d_label, d_count, s)) != hipSuccess) return hip_fail(e, "dbscan_begin");
-    if ((e = cloud_records(st->ws, lay, d_points, n_points, s)) != hipSuccess) return hip_fail(e, "cloud_records");
+    if ((e = dbscan_begin(c->dbscan_ws.p, dl, n_points, d_label, d_count, s)) != hipSuccess) return hip_fail(e, "dbscan_begin");
+    if ((e = cloud_records(st->ws.p, lay, d_points, n_points, s)) != hipSuccess) return hip_fail(e, "cloud_records");
     launches += 2;
     GridCsrSmall sm;
-    if ((rc = grid_small(c, st->ws, lay, "dbscan", s, &sm))) return rc;
+    if ((rc = grid_small(c, st->ws.p, lay, "dbscan", s, &sm))) return rc;
     const int64_t usable = n_points - (int64_t)sm.skipped;
     if (usable <= 0) {              // nothing to cluster: every label is -1 already
         dbscan_add_launches(launches);
@@ -627,20 +584,17 @@ int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, doub
     for (int a = 0; a < 3; ++a) lo[a] = r3g_grid::dec_float(sm.box[a]), hi[a] = r3g_grid::dec_float(sm.box[3 + a]);
     const int res = resolution ? resolution : r3g_db::auto_resolution(lo, hi, eps, usable);
     const r3g_cl::Grid g = r3g_grid::make_grid(lo, hi, res);
-    if ((rc = c->reserve(&st->pairs, &st->pairs_bytes, sizeof(r3g_cl::Pt) * (size_t)usable, "hipMalloc(cloud points)"))) return rc;
-    if ((e = cloud_fill(st->ws, lay, n_points, g, (r3g_cl::Pt*)st->pairs, s)) != hipSuccess) return hip_fail(e, "cloud_fill");
+    if ((rc = st->pairs.grow(sizeof(r3g_cl::Pt) * (size_t)usable, s, "cloud points"))) return rc;
+    if ((e = cloud_fill(st->ws.p, lay, n_points, g, st->pairs.as<r3g_cl::Pt>(), s)) != hipSuccess) return hip_fail(e, "cloud_fill");
     launches += 5;                  // count, the scan's three, fill
     int run = 0;
-    e = dbscan_run(c->dbscan_ws, dl, g, (const r3g_cl::Pt*)st->pairs, (const unsigned*)(st->ws + lay.off_starts), usable, n_points, eps,
+    e = dbscan_run(c->dbscan_ws.p, dl, g, st->pairs.as<const r3g_cl::Pt>(), (const unsigned*)(st->ws.p + lay.off_starts), usable, n_points, eps,
                    (uint32_t)min_samples, d_label, d_count, c->dbscan_ev + 1, &run, s);
     if (e != hipSuccess) return hip_fail(e, "dbscan_run");
     launches += run;
     static_assert(sizeof(DbscanSmall) <= 64, "the pinned read-back buffer");
-    e = hipMemcpyAsync(c->h_small, c->dbscan_ws + dl.off_small, sizeof(DbscanSmall), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);      // the caller may free its points, and a fault would surface here
-    if (e != hipSuccess) return hip_fail(e, "r3g_cloud_dbscan: read-back");
-    DbscanSmall ds;
-    memcpy(&ds, c->h_small, sizeof ds);
+    DbscanSmall ds;      // (its sync: the caller may free its points, and a fault would surface here)
+    if ((rc = read_back(c->h_small, c->dbscan_ws.p + dl.off_small, &ds, sizeof ds, "dbscan", s))) return rc;
     st->grid = g;
     st->built = true;
     c->dbscan_timed = true;
@@ -666,12 +620,7 @@ int r3g_cloud_dbscan_times(r3g_ctx* ctx, double* ms) {
 
 // ---- Poisson surface on a uniform lattice ---------------------------------------------------------------
 static int recon_small(Ctx* c, ReconState* st, const char* what, hipStream_t s, ReconSmall* out) {
-    hipError_t e = hipMemcpyAsync(c->h_small, st->channels + recon_small_offset(st->lat.depth), sizeof(ReconSmall), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, what);
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, what);
-    memcpy(out, c->h_small, sizeof(ReconSmall));
-    return R3G_OK;
+    return read_back(c->h_small, st->channels.p + recon_small_offset(st->lat.depth), out, sizeof(ReconSmall), what, s);
 }
 
 int r3g_recon_splat(r3g_ctx* ctx, const float* d_points, const float* d_normals, int64_t n_points, int depth, const double* centre,
@@ -689,17 +638,17 @@ int r3g_recon_splat(r3g_ctx* ctx, const float* d_points, const float* d_normals,
     bool ok = side > 0.0 && side - side == 0.0 && L.inv_h > 0.0f && L.inv_2h > 0.0f && L.inv_h - L.inv_h == 0.0f;
     for (int a = 0; a < 3; ++a) ok = ok && L.lo[a] - L.lo[a] == 0.0f;
     if (!ok) return fail(R3G_ERR_INVALID, "r3g_recon_splat: the box (centre, side) is not finite and positive in float32");
-    int rc = c->reserve(&st->channels, &st->channels_bytes, recon_channels_bytes(depth), "hipMalloc(recon channels)");
+    int rc = st->channels.grow(recon_channels_bytes(depth), s, "recon channels");
     if (rc) return rc;
-    if ((rc = c->reserve(&st->levels, &st->levels_bytes, recon_levels_bytes(depth), "hipMalloc(recon levels)"))) return rc;
+    if ((rc = st->levels.grow(recon_levels_bytes(depth), s, "recon levels"))) return rc;
     st->lat = L;
     st->side = side;
     hipError_t e = recon_splat(st, d_points, d_normals, n_points, s);
     if (e != hipSuccess) return hip_fail(e, "recon_splat");
-    if (d_channels_out && (e = hipMemcpyAsync(d_channels_out, st->channels, recon_small_offset(depth), hipMemcpyDeviceToDevice, s)) != hipSuccess)
+    if (d_channels_out && (e = hipMemcpyAsync(d_channels_out, st->channels.p, recon_small_offset(depth), hipMemcpyDeviceToDevice, s)) != hipSuccess)
         return hip_fail(e, "hipMemcpyAsync(recon channels)");
     ReconSmall sm;
-    if ((rc = recon_small(c, st, "r3g_recon_splat: read-back", s, &sm))) return rc;
+    if ((rc = recon_small(c, st, "recon splat", s, &sm))) return rc;
     if (sm.usable == 0) return fail(R3G_ERR_INVALID, "r3g_recon_splat: no usable point (finite coordinates, finite non-zero normal)");
     st->splatted = true;
     if (usable_out) *usable_out = (int64_t)sm.usable;
@@ -718,7 +667,7 @@ int r3g_recon_solve(r3g_ctx* ctx, int cycles, float* d_b_out, float* d_chi_out, 
     if (e != hipSuccess) return hip_fail(e, "recon_solve");
     const int depth = st->lat.depth;
     const size_t bytes = (size_t)recon_nodes(depth) * 4;
-    const float* lv = (const float*)st->levels;
+    const float* lv = st->levels.as<const float>();
     if (d_b_out && (e = hipMemcpyAsync(d_b_out, lv + recon_level_offset(depth, depth, 2), bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess)
         return hip_fail(e, "hipMemcpyAsync(recon b)");
     if (d_chi_out && (e = hipMemcpyAsync(d_chi_out, lv + recon_level_offset(depth, depth, 0), bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess)
@@ -744,7 +693,7 @@ int r3g_recon_sample(r3g_ctx* ctx, int field, const float* d_points, const float
     hipError_t e = recon_sample(st, field, d_points, d_normals, n_points, d_values_out, s);
     if (e != hipSuccess) return hip_fail(e, "recon_sample");
     ReconSmall sm;
-    int rc = recon_small(c, st, "r3g_recon_sample: read-back", s, &sm);
+    int rc = recon_small(c, st, "recon sample", s, &sm);
     if (rc) return rc;
     if (sum_out) *sum_out = (int64_t)sm.sum;
     if (count_out) *count_out = (int64_t)sm.usable;
@@ -759,7 +708,7 @@ int r3g_meshdist_closest(r3g_ctx* ctx, const float* d_points, int64_t n_points, 
     if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: n_points out of range");
     if (n_points == 0) return R3G_OK;
     if (!d_points || !d_dist2 || !d_face || !d_closest) return fail(R3G_ERR_INVALID, "r3g_meshdist_closest: null buffer");
-    hipError_t e = meshfit_closest(c->meshdist.ws, c->meshdist.lay, c->meshdist.grid, (const int32_t*)c->meshdist.pairs, d_points,
+    hipError_t e = meshfit_closest(c->meshdist.ws.p, c->meshdist.lay, c->meshdist.grid, c->meshdist.pairs.as<const int32_t>(), d_points,
                                    n_points, d_dist2, d_face, d_closest, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "meshfit_closest");
 }
@@ -767,21 +716,14 @@ int r3g_meshdist_closest(r3g_ctx* ctx, const float* d_points, int64_t n_points, 
 // one accumulation under x -> the record in c->h_fit
 static int meshfit_accumulate(Ctx* c, const float* d_points, int64_t n, const float* d_weights, const r3g_md::Sim& x, int mode,
                               double max_dist, hipStream_t s, MeshfitRecord* out) {
-    int rc = c->reserve(&c->meshfit_ws, &c->meshfit_ws_bytes, meshfit_workspace_bytes(), "hipMalloc(meshfit workspace)");
+    int rc = c->meshfit_ws.grow(meshfit_workspace_bytes(), s, "meshfit workspace");
     if (rc) return rc;
-    if (!c->h_fit) {
-        hipError_t e = hipHostMalloc((void**)&c->h_fit, sizeof(MeshfitRecord), hipHostMallocDefault);
-        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(meshfit)");
-    }
+    if ((rc = c->h_fit.grow(sizeof(MeshfitRecord), s, "meshfit read-back buffer"))) return rc;
     const float md2 = (float)(max_dist * max_dist);
-    hipError_t e = meshfit_step(c->meshfit_ws, c->meshdist.ws, c->meshdist.lay, c->meshdist.grid, (const int32_t*)c->meshdist.pairs,
+    hipError_t e = meshfit_step(c->meshfit_ws.p, c->meshdist.ws.p, c->meshdist.lay, c->meshdist.grid, c->meshdist.pairs.as<const int32_t>(),
                                 d_points, n, d_weights, x, mode, md2, s);
     if (e != hipSuccess) return hip_fail(e, "meshfit_step");
-    e = hipMemcpyAsync(c->h_fit, c->meshfit_ws, sizeof(MeshfitRecord), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshfit)");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshfit)");
-    memcpy(out, c->h_fit, sizeof(MeshfitRecord));
+    if ((rc = read_back(c->h_fit, c->meshfit_ws.p, out, sizeof(MeshfitRecord), "meshfit", s))) return rc;
     meshfit_add_steps(1);
     meshdist_add_tests((int64_t)out->tests);
     return R3G_OK;
@@ -885,11 +827,11 @@ int r3g_meshinside_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, 
     if (n_points == 0) return R3G_OK;
     if (!d_points || !d_count) return fail(R3G_ERR_INVALID, "r3g_meshinside_query: null buffer");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = meshinside_query(c->meshinside.ws, c->meshinside.lay, c->meshinside.grid, c->meshinside_axis,
-                                    (const int32_t*)c->meshinside.pairs, d_points, n_points, d_count, s);
+    hipError_t e = meshinside_query(c->meshinside.ws.p, c->meshinside.lay, c->meshinside.grid, c->meshinside_axis,
+                                    c->meshinside.pairs.as<const int32_t>(), d_points, n_points, d_count, s);
     if (e != hipSuccess) return hip_fail(e, "meshinside_query");
     GridCsrSmall sm;
-    int rc = grid_small(c, c->meshinside.ws, c->meshinside.lay, "meshinside", s, &sm);
+    int rc = grid_small(c, c->meshinside.ws.p, c->meshinside.lay, "meshinside", s, &sm);
     if (rc) return rc;
     meshinside_add_tests((int64_t)sm.tests);
     return R3G_OK;
@@ -897,34 +839,25 @@ int r3g_meshinside_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, 
 
 // ---- mesh topology ------------------------------------------------------------------------------------------------
 static int meshtopo_small(Ctx* c, hipStream_t s, r3g_mt::Small* out) {
-    hipError_t e = hipMemcpyAsync(c->h_topo, c->meshtopo_ws + c->meshtopo_lay.off_small, sizeof(r3g_mt::Small), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshtopo)");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshtopo)");
-    memcpy(out, c->h_topo, sizeof(r3g_mt::Small));
-    return R3G_OK;
+    return read_back(c->h_topo, c->meshtopo_ws.p + c->meshtopo_lay.off_small, out, sizeof(r3g_mt::Small), "meshtopo", s);
 }
 
 // the build behind r3g_meshtopo_build and r3g_meshtopo_orient (arguments checked by the caller)
 static int meshtopo_build(Ctx* c, const char* who, const float* d_verts, int64_t n_verts, const int32_t* d_faces, int64_t n_faces,
                           hipStream_t s) {
     c->meshtopo_built = false;
-    int rc;
-    if (!c->h_topo) {
-        hipError_t e = hipHostMalloc((void**)&c->h_topo, 256, hipHostMallocDefault);
-        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(meshtopo)");
-    }
-    MeshtopoLayout lay;
-    rc = c->reserve(&c->meshtopo_ws, &c->meshtopo_ws_bytes, meshtopo_workspace_bytes(n_verts, n_faces, &lay), "hipMalloc(meshtopo workspace)");
+    int rc = c->h_topo.grow(256, s, "meshtopo read-back buffer");
     if (rc) return rc;
+    MeshtopoLayout lay;
+    if ((rc = c->meshtopo_ws.grow(meshtopo_workspace_bytes(n_verts, n_faces, &lay), s, "meshtopo workspace"))) return rc;
     c->meshtopo_lay = lay;
-    hipError_t e = meshtopo_check(c->meshtopo_ws, lay, d_verts, n_verts, d_faces, n_faces, s);
+    hipError_t e = meshtopo_check(c->meshtopo_ws.p, lay, d_verts, n_verts, d_faces, n_faces, s);
     if (e != hipSuccess) return hip_fail(e, "meshtopo_check");
     r3g_mt::Small sm;
     if ((rc = meshtopo_small(c, s, &sm))) return rc;
     // (-2 by the contract of include/r3g.h: found on the device, before anything is read through the index)
     if (sm.bad_index) return fail(-2, "%s: a face index lies outside [0, %lld)", who, (long long)n_verts);
-    e = meshtopo_edges(c->meshtopo_ws, lay, d_faces, n_faces, s);
+    e = meshtopo_edges(c->meshtopo_ws.p, lay, d_faces, n_faces, s);
     if (e != hipSuccess) return hip_fail(e, "meshtopo_edges");
     int rounds = 0;
     for (;;) {
@@ -932,13 +865,13 @@ static int meshtopo_build(Ctx* c, const char* who, const float* d_verts, int64_t
             meshtopo_add_counters(0, rounds);
             return fail(R3G_ERR_INVALID, "%s: the body labels still move after %d rounds; no labelling is returned", who, rounds);
         }
-        e = meshtopo_round(c->meshtopo_ws, lay, n_faces, s);
+        e = meshtopo_round(c->meshtopo_ws.p, lay, n_faces, s);
         if (e != hipSuccess) return hip_fail(e, "meshtopo_round");
         ++rounds;
         if ((rc = meshtopo_small(c, s, &sm))) return rc;
         if (!sm.changed) break;
     }
-    e = meshtopo_finish(c->meshtopo_ws, lay, d_verts, d_faces, n_faces, s);
+    e = meshtopo_finish(c->meshtopo_ws.p, lay, d_verts, d_faces, n_faces, s);
     if (e != hipSuccess) return hip_fail(e, "meshtopo_finish");
     if ((rc = meshtopo_small(c, s, &sm))) return rc;      // (also: the caller may free its buffers, a fault would surface here)
     meshtopo_add_counters(1, rounds);
@@ -990,7 +923,7 @@ int r3g_meshtopo_mates(r3g_ctx* ctx, int32_t* d_mate, void* stream) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c->meshtopo_built) return fail(R3G_ERR_STATE, "r3g_meshtopo_mates: no successful r3g_meshtopo_build on this context");
     if (!d_mate) return fail(R3G_ERR_INVALID, "r3g_meshtopo_mates: null buffer");
-    hipError_t e = hipMemcpyAsync(d_mate, c->meshtopo_ws + c->meshtopo_lay.off_mate, 12 * (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice,
+    hipError_t e = hipMemcpyAsync(d_mate, c->meshtopo_ws.p + c->meshtopo_lay.off_mate, 12 * (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice,
                                   (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshtopo mates)");
     return R3G_OK;
@@ -1001,9 +934,9 @@ int r3g_meshtopo_bodies(r3g_ctx* ctx, int32_t* d_body, uint8_t* d_flip, void* st
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c->meshtopo_built) return fail(R3G_ERR_STATE, "r3g_meshtopo_bodies: no successful r3g_meshtopo_build on this context");
     hipError_t e = hipSuccess;
-    if (d_body) e = hipMemcpyAsync(d_body, c->meshtopo_ws + c->meshtopo_lay.off_body, 4 * (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (d_body) e = hipMemcpyAsync(d_body, c->meshtopo_ws.p + c->meshtopo_lay.off_body, 4 * (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e == hipSuccess && d_flip)
-        e = hipMemcpyAsync(d_flip, c->meshtopo_ws + c->meshtopo_lay.off_flip, (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        e = hipMemcpyAsync(d_flip, c->meshtopo_ws.p + c->meshtopo_lay.off_flip, (size_t)c->meshtopo_nf, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshtopo bodies)");
     return R3G_OK;
 }
@@ -1020,7 +953,7 @@ int r3g_meshtopo_orient(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, int
     hipStream_t s = (hipStream_t)stream;
     if ((rc = meshtopo_build(c, "r3g_meshtopo_orient", d_verts, n_verts, d_faces, n_faces, s))) return rc;
     c->meshtopo_built = false;                    // until the state describes the faces as this call leaves them
-    hipError_t e = meshtopo_apply(c->meshtopo_ws, c->meshtopo_lay, d_faces, n_faces, outward, s);
+    hipError_t e = meshtopo_apply(c->meshtopo_ws.p, c->meshtopo_lay, d_faces, n_faces, outward, s);
     if (e != hipSuccess) return hip_fail(e, "meshtopo_apply");
     r3g_mt::Small sm;
     if ((rc = meshtopo_small(c, s, &sm))) return rc;
@@ -1053,17 +986,11 @@ int r3g_meshfill_plan(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const
     r3g_mf::Small sm{};
     MeshfillLayout lay{};
     if (boundary > 0) {
-        rc = c->reserve(&c->meshfill_ws, &c->meshfill_ws_bytes, meshfill_workspace_bytes(n_verts, n_faces, boundary, &lay),
-                        "hipMalloc(meshfill workspace)");
-        if (rc) return rc;
-        hipError_t e = meshfill_plan(c->meshfill_ws, &lay, (const int32_t*)(c->meshtopo_ws + c->meshtopo_lay.off_mate), d_verts, n_verts,
+        if ((rc = c->meshfill_ws.grow(meshfill_workspace_bytes(n_verts, n_faces, boundary, &lay), s, "meshfill workspace"))) return rc;
+        hipError_t e = meshfill_plan(c->meshfill_ws.p, &lay, (const int32_t*)(c->meshtopo_ws.p + c->meshtopo_lay.off_mate), d_verts, n_verts,
                                      d_faces, rounds, max_loop, mode, s);
         if (e != hipSuccess) return hip_fail(e, "meshfill_plan");
-        e = hipMemcpyAsync(c->h_small, c->meshfill_ws + lay.off_small, sizeof sm, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(meshfill)");
-        e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(meshfill)");
-        memcpy(&sm, c->h_small, sizeof sm);
+        if ((rc = read_back(c->h_small, c->meshfill_ws.p + lay.off_small, &sm, sizeof sm, "meshfill", s))) return rc;
     }
     meshfill_add_counters(1, 2 * (int64_t)rounds);
     const int64_t verts_added = mode == r3g_mf::kModeCentroid ? (int64_t)sm.filled : 0;
@@ -1090,7 +1017,7 @@ int r3g_meshfill_emit(r3g_ctx* ctx, int32_t* d_new_faces, float* d_new_verts, vo
     const int64_t* r = c->meshfill_report;
     if (r[r3g_mf::kRepFacesAdded] == 0) return R3G_OK;
     if (!d_new_faces) return fail(R3G_ERR_INVALID, "r3g_meshfill_emit: null buffer");
-    hipError_t e = meshfill_emit(c->meshfill_ws, c->meshfill_lay, r[r3g_mf::kRepVerts], r[r3g_mf::kRepMaxLoop], (int)r[r3g_mf::kRepMode],
+    hipError_t e = meshfill_emit(c->meshfill_ws.p, c->meshfill_lay, r[r3g_mf::kRepVerts], r[r3g_mf::kRepMaxLoop], (int)r[r3g_mf::kRepMode],
                                  r[r3g_mf::kRepFilled], r[r3g_mf::kRepFacesAdded], d_new_faces, d_new_verts, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "meshfill_emit");
     return R3G_OK;
@@ -1103,7 +1030,7 @@ int r3g_meshfill_loops(r3g_ctx* ctx, int64_t* d_loop_start, int32_t* d_loop_vert
     const int64_t* r = c->meshfill_report;
     if (!d_loop_start || (r[r3g_mf::kRepLoops] && (!d_loop_verts || !d_loop_status)))
         return fail(R3G_ERR_INVALID, "r3g_meshfill_loops: null buffer");
-    hipError_t e = meshfill_loops(c->meshfill_ws, c->meshfill_lay, r[r3g_mf::kRepMaxLoop], r[r3g_mf::kRepLoops], r[r3g_mf::kRepLoopEdges],
+    hipError_t e = meshfill_loops(c->meshfill_ws.p, c->meshfill_lay, r[r3g_mf::kRepMaxLoop], r[r3g_mf::kRepLoops], r[r3g_mf::kRepLoopEdges],
                                   d_loop_start, d_loop_verts, d_loop_status, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "meshfill_loops");
     return R3G_OK;
@@ -1118,9 +1045,9 @@ int r3g_tex_rasterize(r3g_ctx* ctx, const float* d_pos_clip, int64_t n_verts, co
     if (n_verts < 0 || n_faces < 0 || n_faces >= (1ll << 30) || (n_faces && (!d_pos_clip || !d_tri)))
         return fail(R3G_ERR_INVALID, "r3g_tex_rasterize: bad mesh arguments");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    int rc = c->reserve(&c->tex_ws, &c->tex_ws_bytes, 8 * (size_t)height * width, "hipMalloc(z-buffer)");
+    int rc = c->tex_ws.grow(8 * (size_t)height * width, (hipStream_t)stream, "z-buffer");
     if (rc) return rc;
-    hipError_t e = tex_rasterize(d_pos_clip, d_tri, (int)n_faces, height, width, (unsigned long long*)c->tex_ws, d_findices,
+    hipError_t e = tex_rasterize(d_pos_clip, d_tri, (int)n_faces, height, width, c->tex_ws.as<unsigned long long>(), d_findices,
                                  d_bary, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "tex_rasterize");
 }
@@ -1181,9 +1108,9 @@ int r3g_tex_inpaint(r3g_ctx* ctx, float* d_texture, uint8_t* d_mask, int tex_siz
         dilate_iters < 0 || dilate_iters > 4096)
         return fail(R3G_ERR_INVALID, "r3g_tex_inpaint: bad sizes");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    int rc = c->reserve(&c->tex_ws, &c->tex_ws_bytes, tex_inpaint_workspace(n_verts, tex_size), "hipMalloc(inpaint workspace)");
+    int rc = c->tex_ws.grow(tex_inpaint_workspace(n_verts, tex_size), (hipStream_t)stream, "inpaint workspace");
     if (rc) return rc;
-    hipError_t e = tex_inpaint(c->tex_ws, (unsigned*)c->h_small, d_texture, d_mask, tex_size, d_findices_uv, d_bary_uv, d_verts,
+    hipError_t e = tex_inpaint(c->tex_ws.p, c->h_small.as<unsigned>(), d_texture, d_mask, tex_size, d_findices_uv, d_bary_uv, d_verts,
                                n_verts, d_pos_tri, d_uv, d_uv_tri, n_faces, dilate_iters, rounds_out, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "tex_inpaint");
 }

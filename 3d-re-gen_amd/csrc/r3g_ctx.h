@@ -7,6 +7,7 @@
 
 #include "cloud_kernels.h"
 #include "dbscan_kernels.h"
+#include "dev_buf.h"
 #include "dmc_kernels.h"
 #include "hier_kernels.h"
 #include "kernels.h"
@@ -21,25 +22,20 @@
 
 namespace r3g {
 
-int fail(int code, const char* fmt, ...);
-int hip_fail(hipError_t e, const char* what);
-
+// Every buffer below is a DevBuf (dev_buf.h): it goes with the context, and none of them is released by hand.
 struct Ctx {
     int device = 0;
     int num_cu = 0;
-    char* h_small = nullptr;  // pinned, 64 B: read-back of tiny device results
+    DevBuf h_small{true};     // pinned, 64 B: read-back of tiny device results
     // marching cubes and dual marching cubes (SurfState: surf_compact_kernels.h): a caller may hold a counted state of each at once
     SurfState mc, dmc;
     // mesh cleaners
-    char* mesh_ws = nullptr;
-    size_t mesh_ws_bytes = 0;
+    DevBuf mesh_ws;
     // mesh distance: the grid of the last r3g_meshdist_build (records, CSR starts; the pair list has its own buffer)
     GridCsrState<3> meshdist;
     // mesh registration: the partial records of a fit step, and the pinned buffer its result is read back through (the sums
     // do not fit h_small); both made on first use
-    char* meshfit_ws = nullptr;
-    size_t meshfit_ws_bytes = 0;
-    char* h_fit = nullptr;
+    DevBuf meshfit_ws, h_fit{true};
     // point in mesh: the columns of the last r3g_meshinside_build (separate from the distance grid: both may be held at once)
     GridCsrState<2> meshinside;
     int meshinside_axis = 0;
@@ -49,44 +45,36 @@ struct Ctx {
     // Poisson surface: the int64 channels of the last r3g_recon_splat and the solver's float32 lattices (recon_kernels.h)
     ReconState recon;
     // normal orientation: the rows, labels and parities of one r3g_cloud_orient (nothing is kept between calls but the buffer)
-    char* orient_ws = nullptr;
-    size_t orient_ws_bytes = 0;
+    DevBuf orient_ws;
     // DBSCAN: the flags, roots, numbers and sizes of one r3g_cloud_dbscan (nothing is kept between calls but the buffer), and the
     // events around the passes of the last call (made on first use; dbscan_timed: they bracket a complete run)
-    char* dbscan_ws = nullptr;
-    size_t dbscan_ws_bytes = 0;
+    DevBuf dbscan_ws;
     hipEvent_t dbscan_ev[kDbscanPasses + 2] = {};
     bool dbscan_ev_made = false;
     bool dbscan_timed = false;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
     // fit h_small), made on first use
-    char* meshtopo_ws = nullptr;
-    size_t meshtopo_ws_bytes = 0;
-    char* h_topo = nullptr;
+    DevBuf meshtopo_ws, h_topo{true};
     MeshtopoLayout meshtopo_lay{};
     int64_t meshtopo_nf = 0;
     int64_t meshtopo_report[16] = {0};
     bool meshtopo_built = false;
     // mesh fill: the slots, loops and scans of the last r3g_meshfill_plan (a state of its own again; the plan also leaves the
     // topology state above describing its input mesh)
-    char* meshfill_ws = nullptr;
-    size_t meshfill_ws_bytes = 0;
+    DevBuf meshfill_ws;
     MeshfillLayout meshfill_lay{};
     int64_t meshfill_report[16] = {0};
     bool meshfill_planned = false;
     // texture stage (z-buffer / inpainting workspace)
-    char* tex_ws = nullptr;
-    size_t tex_ws_bytes = 0;
+    DevBuf tex_ws;
 
     // hierarchical volume decoder: mask / prefix of the last r3g_hier_select
-    char* hier_ws = nullptr;
-    size_t hier_ws_bytes = 0;
+    DevBuf hier_ws;
     HierLayout hier_lay{};
     int64_t hier_count = 0;
     bool hier_selected = false;
 
-    int reserve(char** buf, size_t* have, size_t need, const char* what);
     void* model = nullptr;  // r3g::Model (model.cpp)
     void release_model();
     void* unet = nullptr;   // r3g::Unet (unet.cpp)

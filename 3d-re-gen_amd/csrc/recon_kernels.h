@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "dev_buf.h"
 #include "recon_core.h"
 
 namespace r3g {
@@ -17,10 +18,7 @@ struct ReconSmall {
 };
 
 struct ReconState {
-    char* channels = nullptr;
-    size_t channels_bytes = 0;
-    char* levels = nullptr;
-    size_t levels_bytes = 0;
+    DevBuf channels, levels;
     r3g_rc::Lattice lat{};
     double side = 0.0;
     bool splatted = false, solved = false;

@@ -129,15 +129,15 @@ std::atomic<int64_t> g_solves{0}, g_cycles{0};
 
 hipError_t recon_splat(ReconState* st, const float* points, const float* normals, int64_t n, hipStream_t s) {
     const int depth = st->lat.depth;
-    R3G_HIP(hipMemsetAsync(st->channels, 0, recon_channels_bytes(depth), s));
-    hipLaunchKernelGGL(rc_splat, dim3(nblocks(n, kT)), dim3(kT), 0, s, points, normals, n, st->lat, (unsigned long long*)st->channels,
-                       (ReconSmall*)(st->channels + recon_small_offset(depth)));
+    R3G_HIP(hipMemsetAsync(st->channels.p, 0, recon_channels_bytes(depth), s));
+    hipLaunchKernelGGL(rc_splat, dim3(nblocks(n, kT)), dim3(kT), 0, s, points, normals, n, st->lat, (unsigned long long*)st->channels.p,
+                       (ReconSmall*)(st->channels.p + recon_small_offset(depth)));
     return hipGetLastError();
 }
 
 hipError_t recon_solve(ReconState* st, int cycles, hipStream_t s) {
     const int depth = st->lat.depth;
-    float* lv = (float*)st->levels;
+    float* lv = (float*)st->levels.p;
     auto buf = [&](int d, int which) { return lv + recon_level_offset(depth, d, which); };
     auto blocks = [](int d) { return dim3(nblocks(recon_nodes(d), kT)); };
     auto n_of = [](int d) { return (1 << d) + 1; };
@@ -147,7 +147,7 @@ hipError_t recon_solve(ReconState* st, int cycles, hipStream_t s) {
         hipLaunchKernelGGL(rc_smooth, blocks(d), dim3(kT), 0, s, buf(d, 0), buf(d, 2), buf(d, 1), n_of(d), h2[d]);
         hipLaunchKernelGGL(rc_smooth, blocks(d), dim3(kT), 0, s, buf(d, 1), buf(d, 2), buf(d, 0), n_of(d), h2[d]);
     };
-    hipLaunchKernelGGL(rc_rhs, blocks(depth), dim3(kT), 0, s, (const int64_t*)st->channels, st->lat, buf(depth, 2));
+    hipLaunchKernelGGL(rc_rhs, blocks(depth), dim3(kT), 0, s, (const int64_t*)st->channels.p, st->lat, buf(depth, 2));
     R3G_HIP(hipMemsetAsync(buf(depth, 0), 0, (size_t)recon_nodes(depth) * 4, s));
     for (int c = 0; c < cycles; ++c) {
         for (int d = depth; d >= 2; --d) {
@@ -168,14 +168,14 @@ hipError_t recon_solve(ReconState* st, int cycles, hipStream_t s) {
 hipError_t recon_sample(ReconState* st, int field, const float* points, const float* normals, int64_t n, float* values_out,
                         hipStream_t s) {
     const int depth = st->lat.depth;
-    ReconSmall* sm = (ReconSmall*)(st->channels + recon_small_offset(depth));
+    ReconSmall* sm = (ReconSmall*)(st->channels.p + recon_small_offset(depth));
     R3G_HIP(hipMemsetAsync(sm, 0, sizeof(ReconSmall), s));
     if (field == 0)
-        hipLaunchKernelGGL((rc_sample<LoadFixed>), dim3(nblocks(n, kT)), dim3(kT), 0, s, LoadFixed{(const int64_t*)st->channels}, points,
+        hipLaunchKernelGGL((rc_sample<LoadFixed>), dim3(nblocks(n, kT)), dim3(kT), 0, s, LoadFixed{(const int64_t*)st->channels.p}, points,
                            normals, n, st->lat, values_out, sm);
     else
         hipLaunchKernelGGL((rc_sample<LoadFloat>), dim3(nblocks(n, kT)), dim3(kT), 0, s,
-                           LoadFloat{(const float*)st->levels + recon_level_offset(depth, depth, 0)}, points, normals, n, st->lat,
+                           LoadFloat{(const float*)st->levels.p + recon_level_offset(depth, depth, 0)}, points, normals, n, st->lat,
                            values_out, sm);
     return hipGetLastError();
 }

@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "dev_buf.h"
+
 namespace r3g {
 
 // small | blk | blkoff | nz | act | table, each aligned to 256 B
@@ -31,8 +33,7 @@ hipError_t surf_scan_launch(char* ws, const SurfWorkspaceLayout& lay, hipStream_
 
 // what an extractor keeps in the context between its count and its emit
 struct SurfState {
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf ws;
     SurfWorkspaceLayout lay{};
     const float* grid = nullptr;
     int n[3] = {0, 0, 0};

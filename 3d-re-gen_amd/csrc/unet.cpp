@@ -41,7 +41,7 @@ struct UTensor {
 struct Unet {
     r3g_unet_config c{};
     std::unordered_map<std::string, UTensor> w;
-    char* arena = nullptr;
+    DevBuf arena;                          // every DevBuf here goes with the UNet
     // activation buffers (sized for max_hw rows x max_channels)
     float *h = nullptr, *t1 = nullptr;     // transformer-level hidden state, resnet intermediate
     uint16_t *xn = nullptr;                // normalised / cast operand [hw][C]
@@ -56,15 +56,14 @@ struct Unet {
     // whole-model forward (r3g_unet_forward): the concatenated input of an up-block resnet, two hidden-state buffers, the
     // time embedding, and the stack of skip connections (allocated on first use for the resolution at hand)
     float *catbuf = nullptr, *hb[2] = {nullptr, nullptr}, *emb = nullptr;
-    float* skips = nullptr;
-    size_t skips_bytes = 0;
+    DevBuf skips;
     // several samples per call (the views of the multiview UNet): rows are [nb][H*W][C]; per-sample small vectors
     float *vecn = nullptr;                 // [kMaxViews][max_channels]: time_emb_proj(silu(emb_n)) of the resnet at hand
     float *embn = nullptr;                 // [kMaxViews][temb_dim]: time embedding + class embedding of every sample
     float *gate = nullptr;                 // [2][max_channels]: constant vectors mva_scale / ref_scale (GEMM epilogue gates)
     // 2.5D transformer blocks ([UPSTREAM-RECALLED] hunyuanpaint/unet/modules.py): what the reference pass writes per
     // transformer ("condition_embed_dict"), keyed by the transformer's prefix
-    struct Cond { uint16_t* p = nullptr; int64_t rows = 0, cols = 0; size_t cap = 0; };
+    struct Cond { DevBuf buf; int64_t rows = 0, cols = 0; };      // bf16 [rows][cols]
     std::unordered_map<std::string, Cond> cond;
     int nb = 1;                            // samples in the running forward
     int mv_flags = 0;                      // 1: write the condition store | 2: read it (reference attention)
@@ -335,13 +334,9 @@ static int unet_transformer(Unet& u, const std::string& pre, float* x, int H, in
     if (u.mv_flags & 1) {          // "w": keep norm1's output of all samples, tokens (n l)
         Unet::Cond& c = u.cond[pre];
         const size_t need = (size_t)rows * C * 2;
-        if (need > c.cap) {
-            if (c.p) { U_TRY(hipStreamSynchronize(s)); (void)hipFree(c.p); c.p = nullptr; c.cap = 0; }
-            U_TRY(hipMalloc((void**)&c.p, need));
-            c.cap = need;
-        }
+        U_RC(c.buf.grow(need, s, "unet condition store"));
         c.rows = rows; c.cols = C;
-        U_TRY(hipMemcpyAsync(c.p, u.xn, need, hipMemcpyDeviceToDevice, s));
+        U_TRY(hipMemcpyAsync(c.buf.p, u.xn, need, hipMemcpyDeviceToDevice, s));
     }
     if (has_ref) {                 // reference attention: every view's tokens query the reference pass's tokens
         const UTensor& ct = cond_it->second;
@@ -443,13 +438,9 @@ static int unet_forward(Unet& u, const float* sample, int H, int W, float timest
             if (i < n - 1) { h /= 2; w /= 2; need += (size_t)h * w * ch[i]; }
         }
         need *= 4 * (size_t)nb;
-        if (need > u.skips_bytes) {
-            if (u.skips) { U_TRY(hipStreamSynchronize(s)); (void)hipFree(u.skips); u.skips = nullptr; u.skips_bytes = 0; }
-            U_TRY(hipMalloc((void**)&u.skips, need));
-            u.skips_bytes = need;
-        }
+        U_RC(u.skips.grow(need, s, "unet skip connections"));
     }
-    float* next_slot = u.skips;
+    float* next_slot = u.skips.as<float>();
     auto push = [&](int cc, int h, int w) { Skip k{next_slot, cc, h, w}; next_slot += (size_t)nb * h * w * cc; stack.push_back(k); return k.p; };
     // time embedding: Timesteps(c0) -> linear_1 -> SiLU -> linear_2
     ULin l1, l2;
@@ -568,13 +559,9 @@ static int vae_attention(Unet& u, const std::string& pre, float* x, int H, int W
     U_RC(u_lin(u, pre + ".to_out.0", true, C, C, &o));
     // scores fp32 [hw][hw] + probabilities bf16 [hw][hw] (64 + 32 MiB at 64 x 64 latents) live in the lazily sized side buffer
     const size_t need = (size_t)hw * hw * 6;
-    if (need > u.skips_bytes) {
-        if (u.skips) { U_TRY(hipStreamSynchronize(s)); (void)hipFree(u.skips); u.skips = nullptr; u.skips_bytes = 0; }
-        U_TRY(hipMalloc((void**)&u.skips, need));
-        u.skips_bytes = need;
-    }
-    float* S = u.skips;
-    uint16_t* P = reinterpret_cast<uint16_t*>(u.skips + (size_t)hw * hw);
+    U_RC(u.skips.grow(need, s, "unet attention scores"));
+    float* S = u.skips.as<float>();
+    uint16_t* P = reinterpret_cast<uint16_t*>(S + (size_t)hw * hw);
     U_TRY(group_norm_launch(x, hw, C, u.c.groups, gw, gb, u.c.resnet_eps, 0, u.xn, u.gn_partial, s));
     U_RC(u_gemm(u.xn, C, q, q.b, u.Q, C, hw, EPI_BF16, s));
     U_RC(u_gemm(u.xn, C, k, k.b, u.K, C, hw, EPI_BF16, s));
@@ -704,17 +691,8 @@ static int vae_encode(Unet& u, const float* img, int H, int W, float* out, hipSt
     return u_gemm(u.xn, 64, qc, qc.b, out, zp, hh * ww, EPI_F32, s);
 }
 
-static void unet_free(Unet* u) {
-    if (!u) return;
-    if (u->arena) (void)hipFree(u->arena);
-    if (u->skips) (void)hipFree(u->skips);
-    for (auto& kv : u->cond)
-        if (kv.second.p) (void)hipFree(kv.second.p);
-    delete u;
-}
-
 static int unet_create(Ctx* ctx, const r3g_unet_config* cfg) {
-    if (ctx->unet) { unet_free((Unet*)ctx->unet); ctx->unet = nullptr; }
+    ctx->release_unet();
     const r3g_unet_config& c = *cfg;
     if (c.max_hw < 1 || c.max_channels < 64 || c.max_channels % 64 || c.max_channels > 3072 || c.temb_dim < 1 || c.temb_dim % 8 ||
         c.ctx_dim % 64 || c.ctx_tokens < 1 || c.groups < 1 || c.groups > 256)
@@ -731,11 +709,10 @@ static int unet_create(Ctx* ctx, const r3g_unet_config* cfg) {
                  o_gn = carve((int64_t)kMaxViews * (256LL * 256 * 2 * 8 + 256 * 2 * 4)), o_cat = carve(hw * C * 4), o_hb0 = carve(hw * C * 4), o_hb1 = carve(hw * C * 4),
                  o_emb = carve((int64_t)(c.temb_dim + 2 * C) * 4), o_vecn = carve((int64_t)kMaxViews * C * 4),
                  o_embn = carve((int64_t)kMaxViews * c.temb_dim * 4), o_gate = carve(2 * C * 4), o_split = carve(kSplitWsElems * 4), o_zero = carve(256);
-    hipError_t e = hipMalloc((void**)&u->arena, off);
-    if (e != hipSuccess) { unet_free(u); return hip_fail(e, "hipMalloc(unet arena)"); }
-    e = hipMemset(u->arena, 0, off);      // padded rows must start finite
-    if (e != hipSuccess) { unet_free(u); return hip_fail(e, "hipMemset(unet arena)"); }
-    char* a = u->arena;
+    if (const int rc = u->arena.grow(off, nullptr, "unet arena")) { delete u; return rc; }
+    const hipError_t e = hipMemset(u->arena.p, 0, off);      // padded rows must start finite
+    if (e != hipSuccess) { delete u; return hip_fail(e, "hipMemset(unet arena)"); }
+    char* a = u->arena.p;
     u->h = (float*)(a + o_h); u->t1 = (float*)(a + o_t1); u->xn = (uint16_t*)(a + o_xn); u->col = (uint16_t*)(a + o_col);
     u->Q = (uint16_t*)(a + o_q); u->K = (uint16_t*)(a + o_k); u->Vt = (uint16_t*)(a + o_v); u->att = (uint16_t*)(a + o_att);
     u->ff = (uint16_t*)(a + o_ff); u->ff2 = (uint16_t*)(a + o_ff2); u->ctxK = (uint16_t*)(a + o_ck); u->ctxVt = (uint16_t*)(a + o_cv);
@@ -753,7 +730,7 @@ static int unet_create(Ctx* ctx, const r3g_unet_config* cfg) {
 using namespace r3g;
 
 void r3g::Ctx::release_unet() {
-    if (unet) unet_free((Unet*)unet);
+    delete (Unet*)unet;      // its buffers go with their DevBuf members
     unet = nullptr;
 }
 
@@ -875,8 +852,8 @@ int r3g_unet_condition(r3g_ctx* ctx, const char* prefix, const void** d_ptr, int
     NEED_UNET("r3g_unet_condition");
     if (!prefix || !d_ptr || !rows || !cols) return fail(R3G_ERR_INVALID, "r3g_unet_condition: null argument");
     auto it = u->cond.find(prefix);
-    if (it == u->cond.end() || !it->second.p) return fail(R3G_ERR_STATE, "r3g_unet_condition: no pass with flag 1 has written '%s'", prefix);
-    *d_ptr = it->second.p; *rows = it->second.rows; *cols = it->second.cols;
+    if (it == u->cond.end() || !it->second.buf) return fail(R3G_ERR_STATE, "r3g_unet_condition: no pass with flag 1 has written '%s'", prefix);
+    *d_ptr = it->second.buf.as<uint16_t>(); *rows = it->second.rows; *cols = it->second.cols;
     return R3G_OK;
 }
 

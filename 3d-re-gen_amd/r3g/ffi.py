@@ -208,7 +208,8 @@ def option(name):
 
 def counter(name):
     """r3g_get_counter: a process-wide event counter of the library ("dit_f16_fallbacks", "dit_groups", "dit_evals", "geo_q_cache_builds",
-    "geo_kv_groups", "geo_narrow_passes", "meshdist_tests", "meshinside_tests", "meshfit_steps", "meshtopo_builds", "meshtopo_rounds", "meshfill_plans", "meshfill_rounds", "cloud_tests", "orient_rounds", "dbscan_launches", "dbscan_tests", "recon_solves", "recon_cycles", ...: the list is in include/r3g.h)"""
+    "geo_kv_groups", "geo_narrow_passes", "meshdist_tests", "meshinside_tests", "meshfit_steps", "meshtopo_builds", "meshtopo_rounds", "meshfill_plans", "meshfill_rounds", "cloud_tests", "orient_rounds", "dbscan_launches", "dbscan_tests", "recon_solves", "recon_cycles", ...: the list is in include/r3g.h), or the one gauge among them: "device_bytes_live", the bytes of
+    device memory the library holds right now outside torch's allocator (workspaces, arenas, the geo decoder's query cache)"""
     v = ctypes.c_int64(0)
     check(lib().r3g_get_counter(name.encode(), ctypes.byref(v)))
     return int(v.value)

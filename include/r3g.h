@@ -995,6 +995,9 @@ int r3g_get_option(const char* name, int* value);
  * "dbscan_launches": kernels launched by r3g_cloud_dbscan so far (per call: a number that does not depend on the data).
  * "dbscan_tests": evaluations of the neighbour predicate made by r3g_cloud_dbscan so far.
  * "recon_solves": successful r3g_recon_solve calls so far; "recon_cycles": the V-cycles they ran.
+ * "device_bytes_live": bytes of device memory the library holds right now, over all contexts of the process: every buffer it keeps
+ *   between calls (workspaces, the model and UNet arenas, the geo decoder's query-side cache, the DiT batch arena; not pinned host
+ *   buffers, not torch's allocator).  A gauge, not an event count: r3g_destroy and r3g_model_trim bring it down.
  * "geo_lnf_passes" / "geo_lnd_passes": geo decoder passes that took the folded ln_3 ("geo_ln3_fold") / ln_post + output_proj
  * ("geo_lnd_fused") epilogues.
  * Kernel-choice counters, one per form a launch can end in, bumped on the host where the launch is issued (tests read them to see
