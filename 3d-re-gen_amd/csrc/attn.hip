@@ -1867,48 +1867,35 @@ __global__ __launch_bounds__(768, 3) void attn6_kernel(AttnArgs p, unsigned long
 
 }  // namespace
 
-static bool g_attn_glds = true;
-static bool g_attn_pipelined = false;  // measured slower than the plain kernel (2 vs 3 waves/SIMD): profiles/r01_attention_variants.md
-static int g_attn_ablate = 0;
-void attn_set_ablate(int mask) { g_attn_ablate = mask; }
-void attn_set_glds(bool on) { g_attn_glds = on; }
-void attn_set_pipelined(bool on) { g_attn_pipelined = on; }
-
+int g_attn_glds = 1;               // staging path: LDS-DMA | 0: register-staged ("lds_dma", kernels.h)
+static int g_attn_pipelined = 0;   // software-pipelined form of the first-round kernel; measured slower than the plain kernel (2 vs 3 waves/SIMD): profiles/r01_attention_variants.md
+static int g_attn_ablate = 0;      // timing-only ablation builds of the attention kernel (tools/bench_attn.py)
+// 7 (default: 6 on deep grids, else 2) | 2 | 6 | 9 | 3, 4, 5 | 1: the first-round kernel (expects plain Q; same V^T layout)
 static int g_attn_gen = 7;
 static int g_attn_variant = 1;     // option "attn_variant" (round 6): 1 = fast pass without a maximum + sticky sum test (default) | 0 = rounds 2-5 (generations 2 / 6 / 7)
-void attn_set_variant(int v) { if (v >= 0 && v <= 1) g_attn_variant = v; }
 // option "attn_interleave": where the 64-query kernel's fast pass puts its softmax.  0 = automatic (attn3_body) | 1 = inside the MFMA gaps of
 // one key tile (attn3_kernel VAR bit 1; measured 2-3 % slower, profiles/attention_interleave.md) | 2 = skewed across key blocks in steady
 // state (VAR bit 3, profiles/attention_skew.md) | 3 = clustered.  Every value computes the same bits.
 static int g_attn_interleave = 0;
-void attn_set_interleave(int v) { if (v >= 0 && v <= 3) g_attn_interleave = v; }
 static int g_attn_async_stage = 1; // option "attn_async_stage": the variant-1 kernels issue their LDS-DMA unseen by the compiler's wait counts (VAR bit 2); 0 = through the builtin
-void attn_set_async_stage(int v) { g_attn_async_stage = v != 0; }
 // generation 7 takes the 64-query-per-wave kernel where its 256-query workgroups make at least four full rounds of the
 // 512 slots (the geo decoder's 131072-query passes: +6 %); on the DiT's 4442-query attention the coarser grid costs more
 // than the kernel gains (576 workgroups on 512 slots), profiles/r02_attention.md
 static int g_wide6_min_items = 2048;
-void attn_set_wide_min(int items) { if (items > 0) g_wide6_min_items = items; }
-void attn_set_generation(int gen) { if ((gen >= 1 && gen <= 7) || gen == 9) g_attn_gen = gen; }
 static int g_attn6_prio = 1;       // option "attn_prio": generation 9's s_setprio use (0 none | 1 matrix phase | 2 softmax phases)
-void attn_set_prio(int v) { if (v >= 0 && v <= 2) g_attn6_prio = v; }
 static int g_attn_stamps = 0;      // option "attn_stamps": generation 9 prints its per-phase s_memtime sums (timing experiments)
-void attn_set_stamps(int on) { g_attn_stamps = on; }
 
-bool attn_glds() { return g_attn_glds; }
-bool attn_get_option(const char* name, int* value) {
-    if (!strcmp(name, "attn_variant")) *value = g_attn_variant;
-    else if (!strcmp(name, "attn_interleave")) *value = g_attn_interleave;
-    else if (!strcmp(name, "attn_async_stage")) *value = g_attn_async_stage;
-    else if (!strcmp(name, "attn_pipelined")) *value = g_attn_pipelined ? 1 : 0;
-    else if (!strcmp(name, "attn_ablate")) *value = g_attn_ablate;
-    else if (!strcmp(name, "attn_generation")) *value = g_attn_gen;
-    else if (!strcmp(name, "attn_stamps")) *value = g_attn_stamps;
-    else if (!strcmp(name, "attn_prio")) *value = g_attn6_prio;
-    else if (!strcmp(name, "attn_wide_min")) *value = g_wide6_min_items;
-    else return false;
-    return true;
-}
+const Option g_attn_options[] = {
+    {"attn_variant", &g_attn_variant, OPT_KEEP, [](int v) { return v >= 0 && v <= 1; }},
+    {"attn_interleave", &g_attn_interleave, OPT_KEEP, [](int v) { return v >= 0 && v <= 3; }},
+    {"attn_async_stage", &g_attn_async_stage},
+    {"attn_pipelined", &g_attn_pipelined},
+    {"attn_ablate", &g_attn_ablate, OPT_ANY},
+    {"attn_generation", &g_attn_gen, OPT_KEEP, [](int v) { return (v >= 1 && v <= 7) || v == 9; }},
+    {"attn_stamps", &g_attn_stamps, OPT_ANY},
+    {"attn_prio", &g_attn6_prio, OPT_KEEP, [](int v) { return v >= 0 && v <= 2; }},
+    {"attn_wide_min", &g_wide6_min_items, OPT_KEEP, [](int v) { return v > 0; }},
+    {}};
 
 // (the first-generation kernels -- attn_generation 1 and the attn_pipelined option -- scale the scores themselves and
 // reject a pre-scaled Q: producers must then leave q plain)
@@ -1970,7 +1957,7 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
         }
         const int qtile = (g_attn_glds && gen == 9) ? 384 : (g_attn_glds && gen >= 4) ? 256 : 128;
         const int items = count(qtile);
-        if (!g_attn_glds) launch_count(LC_ATTN_REGISTER_STAGED);
+        if (!g_attn_glds) counter_add(LC_ATTN_REGISTER_STAGED);
         if (gen == 9 && g_attn_glds) {     // phased 12-wave kernel (round 5): three groups, S1 | S2 | M
             const int prio = g_attn6_prio;
             auto launch6 = [&](auto ST, unsigned long long* d_st) -> hipError_t {
@@ -1983,7 +1970,7 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
                     (void)hipGetLastError();
                     return hipErrorNotSupported;
                 }
-                launch_count(LC_ATTN_GEN9);
+                counter_add(LC_ATTN_GEN9);
                 hipLaunchKernelGGL(k, dim3(items), dim3(768), 4 * STAGE_B, s, p, d_st);
                 return hipGetLastError();
             };
@@ -2006,7 +1993,7 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
             return launch6(std::false_type{}, nullptr);
         }
         if (g_attn_ablate && gen == 2) {
-            launch_count(LC_ATTN_GEN2);
+            counter_add(LC_ATTN_GEN2);
             switch (g_attn_ablate) {
 #define R3G_ABL2(m) case m: hipLaunchKernelGGL((attn2_kernel<true, false, 4, m>), dim3(items), dim3(256), 0, s, p); break;
                 R3G_ABL2(1) R3G_ABL2(4) R3G_ABL2(8) R3G_ABL2(12) R3G_ABL2(16) R3G_ABL2(48) R3G_ABL2(64) R3G_ABL2(128)
@@ -2016,7 +2003,7 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
             }
             return hipGetLastError();
         }
-        launch_count(!g_attn_glds ? LC_ATTN_GEN2 : gen == 3 ? LC_ATTN_GEN3 : gen == 4 ? LC_ATTN_GEN4 : gen == 5 ? LC_ATTN_GEN5 : gen == 6 ? LC_ATTN_GEN6 : LC_ATTN_GEN2);
+        counter_add(!g_attn_glds ? LC_ATTN_GEN2 : gen == 3 ? LC_ATTN_GEN3 : gen == 4 ? LC_ATTN_GEN4 : gen == 5 ? LC_ATTN_GEN5 : gen == 6 ? LC_ATTN_GEN6 : LC_ATTN_GEN2);
         if (!g_attn_glds) hipLaunchKernelGGL((attn2_kernel<false, false, 4>), dim3(items), dim3(256), 0, s, p);
         else if (gen == 3) hipLaunchKernelGGL((attn2_kernel<true, true, 4>), dim3(items), dim3(256), 0, s, p);
         else if (gen == 4) hipLaunchKernelGGL((attn2_kernel<true, true, 8>), dim3(items), dim3(512), 0, s, p);
@@ -2044,8 +2031,8 @@ hipError_t attention_launch(const AttnArgs& p, hipStream_t s) {
     }
     if (p.q_prescaled) return hipErrorInvalidValue;   // the first-generation kernels scale the scores themselves
     dim3 grid(p.Lq_pad / 128, p.H, p.B);
-    launch_count(g_attn_pipelined ? LC_ATTN_PIPELINED : LC_ATTN_GEN1);
-    if (!g_attn_glds) launch_count(LC_ATTN_REGISTER_STAGED);
+    counter_add(g_attn_pipelined ? LC_ATTN_PIPELINED : LC_ATTN_GEN1);
+    if (!g_attn_glds) counter_add(LC_ATTN_REGISTER_STAGED);
     if (g_attn_pipelined) {
         if (g_attn_glds) hipLaunchKernelGGL(attn_kernel_sp<true>, grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL(attn_kernel_sp<false>, grid, dim3(256), 0, s, p);

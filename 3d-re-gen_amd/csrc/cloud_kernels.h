@@ -19,8 +19,5 @@ hipError_t cloud_fill(char* ws, const GridCsrLayout& lay, int64_t n, const r3g_c
 hipError_t cloud_knn(char* ws, const GridCsrLayout& lay, const r3g_cl::Grid& g, const r3g_cl::Pt* sorted, const float* queries,
                      int64_t n, int k, float* dist2, int32_t* index, hipStream_t s);
 
-void cloud_add_tests(int64_t n);     // r3g_get_counter("cloud_tests")
-int64_t cloud_tests_total();
-
 }  // namespace r3g
 #endif

@@ -7,8 +7,6 @@
 // lanes of a wave hit distinct banks whichever slots they are at, and no register array is indexed dynamically.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_GRID_HD static __host__ __device__ __forceinline__
@@ -81,8 +79,6 @@ __global__ __launch_bounds__(LANES) void cl_knn(Grid g, const Pt* __restrict__ s
     if ((threadIdx.x & 63) == 0 && t) atomicAdd(&sm->tests, t);
 }
 
-std::atomic<int64_t> g_tests{0};
-
 }  // namespace
 
 static_assert(sizeof(Pt) == 16, "a target point is one 16-byte load");
@@ -115,8 +111,5 @@ hipError_t cloud_knn(char* ws, const GridCsrLayout& lay, const Grid& g, const Pt
                            (size_t)k * kLanesLargeK * 8, s, g, sorted, starts, queries, n, k, dist2, index, sm);
     return hipGetLastError();
 }
-
-void cloud_add_tests(int64_t n) { g_tests += n; }
-int64_t cloud_tests_total() { return g_tests.load(); }
 
 }  // namespace r3g

@@ -41,10 +41,5 @@ hipError_t dbscan_run(char* ws, const DbscanLayout& lay, const r3g_cl::Grid& g, 
                       int64_t m, int64_t n, double eps, uint32_t min_samples, int32_t* label, uint32_t* count, hipEvent_t* ev,
                       int* launches, hipStream_t s);
 
-void dbscan_add_launches(int64_t n);     // r3g_get_counter("dbscan_launches")
-int64_t dbscan_launches_total();
-void dbscan_add_tests(int64_t n);        // r3g_get_counter("dbscan_tests")
-int64_t dbscan_tests_total();
-
 }  // namespace r3g
 #endif

@@ -9,8 +9,6 @@
 // is fixed: no pass is repeated until it converges.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_GRID_HD static __host__ __device__ __forceinline__
@@ -140,8 +138,6 @@ __global__ __launch_bounds__(kT) void db_largest(int64_t n, const uint32_t* __re
     if ((threadIdx.x & 63) == 0 && best) atomicMax(&sm->best, best);
 }
 
-std::atomic<int64_t> g_launches{0}, g_tests{0};
-
 template <class T>
 T* at(char* ws, size_t off) {
     return (T*)(ws + off);
@@ -200,10 +196,5 @@ hipError_t dbscan_run(char* ws, const DbscanLayout& lay, const Grid& g, const Pt
     *launches = 10;     // count, link, flatten, border, flag, the scan's three, label, largest
     return hipGetLastError();
 }
-
-void dbscan_add_launches(int64_t n) { g_launches += n; }
-int64_t dbscan_launches_total() { return g_launches.load(); }
-void dbscan_add_tests(int64_t n) { g_tests += n; }
-int64_t dbscan_tests_total() { return g_tests.load(); }
 
 }  // namespace r3g

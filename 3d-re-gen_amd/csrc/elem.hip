@@ -670,9 +670,9 @@ inline int blocks_for(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
         /* the two combinations the path is made of, with their optional terms known at compile time (MODE) */            \
         const bool m_aff = g_ln_modes && p.w && p.b && !p.scale && !p.shift && !p.scale2 && !p.shift2 && !p.y8;            \
         const bool m_mod = g_ln_modes && !p.w && !p.b && p.scale && p.shift && !p.y8 && (p.seg2_row1 <= p.seg2_row0 || (p.scale2 && p.shift2)); \
-        launch_count(r4 ? LC_LN_ROWS4 : LC_LN_ROWS1);                                                                      \
-        if ((p.C == 1024 || p.C == 1536) && g_ln_fixed) launch_count(LC_LN_FIXED);                                         \
-        if (p.C == 1024 && g_ln_fixed && (m_mod || m_aff)) launch_count(LC_LN_MODE);                                       \
+        counter_add(r4 ? LC_LN_ROWS4 : LC_LN_ROWS1);                                                                      \
+        if ((p.C == 1024 || p.C == 1536) && g_ln_fixed) counter_add(LC_LN_FIXED);                                         \
+        if (p.C == 1024 && g_ln_fixed && (m_mod || m_aff)) counter_add(LC_LN_MODE);                                       \
         if (p.C == 1024 && g_ln_fixed && m_mod) {                                                                          \
             if (r4) hipLaunchKernelGGL((layernorm_kernel<XB, 4, 4, 2>), g4, blk, 0, s, p);                                 \
             else hipLaunchKernelGGL((layernorm_kernel<XB, 4, 1, 2>), g1, blk, 0, s, p);                                    \
@@ -693,24 +693,18 @@ inline int blocks_for(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
 // rows per wave of the row-in-registers kernels: 4 when that still leaves >= 4096 workgroups (two per workgroup slot of
 // the device), otherwise 1 (the DiT's 7 552-row launches need every wave they can get).  g_ln_rows: 0 automatic | 1 | 4.
 static int g_ln_rows = 0;
-static bool g_ln_modes = true;   // option "ln_modes" (round 6): compile-time MODE instantiations for the affine-only / modulation-only launches
-void ln_set_modes(bool on) { g_ln_modes = on; }
-static bool g_ln_fixed = true;   // compile-time element counts for C = 1024 / 1536 (0: round 2's run-time count everywhere)
-void ln_set_fixed_count(bool on) { g_ln_fixed = on; }
-void ln_set_rows_per_wave(int rows) { g_ln_rows = rows == 1 || rows == 4 ? rows : 0; }
+static int g_ln_modes = 1;   // option "ln_modes" (round 6): compile-time MODE instantiations for the affine-only / modulation-only launches
+static int g_ln_fixed = 1;   // compile-time element counts for C = 1024 / 1536 (0: round 2's run-time count everywhere)
 // 4 rows per wave from 65 536 rows per launch (the geo decoder's 131 072): below that, one row per wave.  Round 4 tried 4 rows
 // from 16 384 (a launch group's 30 060 modulated DiT rows, with the modulation vectors held across a wave's rows): LayerNorm
 // family 45.5 -> 46.8 ms per object, A/B twice on one box (profiles/r04_layernorm_rows.md) -- the option stays for the next try
 static int g_ln_rows4_min = 65536;
-void ln_set_rows4_min(int rows) { g_ln_rows4_min = rows > 0 ? rows : 65536; }
-bool ln_get_option(const char* name, int* value) {
-    if (!strcmp(name, "ln_rows")) *value = g_ln_rows;
-    else if (!strcmp(name, "ln_rows4_min")) *value = g_ln_rows4_min;
-    else if (!strcmp(name, "ln_fixed")) *value = g_ln_fixed ? 1 : 0;
-    else if (!strcmp(name, "ln_modes")) *value = g_ln_modes ? 1 : 0;
-    else return false;
-    return true;
-}
+const Option g_ln_options[] = {
+    {"ln_rows", &g_ln_rows, OPT_ELSE, [](int v) { return v == 1 || v == 4; }, 0},
+    {"ln_rows4_min", &g_ln_rows4_min, OPT_ELSE, [](int v) { return v > 0; }, 65536},
+    {"ln_fixed", &g_ln_fixed},
+    {"ln_modes", &g_ln_modes},
+    {}};
 static int ln_rows_per_wave(int rows) { return g_ln_rows ? g_ln_rows : (rows >= g_ln_rows4_min ? 4 : 1); }
 
 hipError_t layernorm_launch(const LnArgs& p, hipStream_t s) {
@@ -841,8 +835,8 @@ hipError_t fourier_points_launch(uint16_t* out, const int32_t* list, int count, 
 #define R3G_LNDOT_LAUNCH(XB)                                                                                               \
     {                                                                                                                      \
         const bool r4 = ln_rows_per_wave(rows) == 4;                                                                       \
-        launch_count(r4 ? LC_LN_ROWS4 : LC_LN_ROWS1);                                                                      \
-        if (C == 1024 && g_ln_fixed) launch_count(LC_LN_FIXED);                                                            \
+        counter_add(r4 ? LC_LN_ROWS4 : LC_LN_ROWS1);                                                                      \
+        if (C == 1024 && g_ln_fixed) counter_add(LC_LN_FIXED);                                                            \
         const dim3 g1((rows + 3) / 4), g4((rows + 15) / 16), blk(256);                                                     \
         if (C == 1024 && g_ln_fixed) {                                                                                     \
             if (r4) hipLaunchKernelGGL((ln_dot_kernel<XB, 4, 4>), g4, blk, 0, s, x, ldx, rows, C, do_ln, lnw, lnb, eps, w, b, out); \

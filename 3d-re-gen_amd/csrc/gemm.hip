@@ -1693,7 +1693,7 @@ hipError_t launch_gemm8_fp8(const GemmArgs& p, const float* scale_a, const float
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     GemmArgs none{};
-    launch_count(LC_GEMM_FP8);
+    counter_add(LC_GEMM_FP8);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, s, p, none, scale_a, scale_w);
     return hipGetLastError();
 }
@@ -2061,10 +2061,10 @@ namespace r3g {
 namespace {
 #endif
 
-bool g_gemm_xcd_walk = true;   // persistent kernel: an XCD walks one contiguous range of the tile order (round 5) | 0: rounds 2-4's walk
-bool g_gemm_persistent_qkv = true;   // fused QKV launches with more 256x256 tiles than CUs (the double blocks' img + txt pair) on the persistent phased kernel: round 4's 32-row passes cost +17 ms per object, round 6's 64-row passes through the idle k-tile buffer -4 ms (profiles/r06_ab.md)
-bool g_gemm_epi_slices = true;   // persistent kernel, bf16 / fused-QKV epilogues: 64-row passes through the wave's slices of k-tile buffer 1 (round 6) | 0: 32-row passes
-bool g_gemm_mixed = true;        // a single block's [fused QKV | MLP-in + GELU] as ONE persistent launch (round 6) | 0: two launches
+int g_gemm_xcd_walk = 1;   // persistent kernel: an XCD walks one contiguous range of the tile order (round 5) | 0: rounds 2-4's walk
+int g_gemm_persistent_qkv = 1;   // fused QKV launches with more 256x256 tiles than CUs (the double blocks' img + txt pair) on the persistent phased kernel: round 4's 32-row passes cost +17 ms per object, round 6's 64-row passes through the idle k-tile buffer -4 ms (profiles/r06_ab.md)
+int g_gemm_epi_slices = 1;   // persistent kernel, bf16 / fused-QKV epilogues: 64-row passes through the wave's slices of k-tile buffer 1 (round 6) | 0: 32-row passes
+int g_gemm_mixed = 1;        // a single block's [fused QKV | MLP-in + GELU] as ONE persistent launch (round 6) | 0: two launches
 
 // EPI2 != EPI: p2 is a problem with another epilogue (gemm8p_kernel's EPI2)
 template <int EPI, int EPI2 = EPI>
@@ -2085,7 +2085,7 @@ hipError_t launch_gemm8p(const GemmArgs& p, const GemmArgs& p2, int num_cu, hipS
     }
     if (state < 0) { (void)hipGetLastError(); return hipErrorNotSupported; }
     const int walk = g_gemm_xcd_walk ? rounds : 0;
-    launch_count(EPI2 != EPI ? LC_GEMM_MIXED : LC_GEMM_PHASED_PERSISTENT);
+    counter_add(EPI2 != EPI ? LC_GEMM_MIXED : LC_GEMM_PHASED_PERSISTENT);
     if (kSliceable && g_gemm_epi_slices && p.wide_epilogue) { hipLaunchKernelGGL(ks, dim3(grid), dim3(512), lds, s, p, p2, tiles, walk); }
     else { hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, p, p2, tiles, walk); }
     return hipGetLastError();
@@ -2102,7 +2102,7 @@ hipError_t launch_gemm8(const GemmArgs& p, const GemmArgs& p2, hipStream_t s) {
         done = true;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    launch_count(LC_GEMM_PHASED);
+    counter_add(LC_GEMM_PHASED);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, s, p, p2, (float*)nullptr, (unsigned*)nullptr, 0u);
     return hipGetLastError();
 }
@@ -2144,7 +2144,7 @@ hipError_t launch_gemm8_split(const GemmArgs& p, const GemmArgs& p2, hipStream_t
         done = true;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    launch_count(LC_GEMM_SPLITK2);
+    counter_add(LC_GEMM_SPLITK2);
     hipLaunchKernelGGL(k, dim3(2 * tiles), dim3(512), lds, s, p, p2, w.ws, w.flags, w.epoch);
     return hipGetLastError();
 }
@@ -2159,7 +2159,7 @@ hipError_t launch_deep(const GemmArgs& p, int batch, hipStream_t s) {
         done = true;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    launch_count(LC_GEMM_DEEP_RING);
+    counter_add(LC_GEMM_DEEP_RING);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, s, p);
     return hipGetLastError();
 }
@@ -2180,8 +2180,8 @@ hipError_t launch_cfg(const GemmArgs& p, const GemmArgs& p2, bool glds, hipStrea
             (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         }
     }
-    launch_count(BIG == 2 ? LC_GEMM_256X128 : BIG == 1 ? (NW == 16 ? LC_GEMM_W16_256 : LC_GEMM_TWO_STAGE_256) : (NW == 4 ? LC_GEMM_W4_128 : LC_GEMM_W8_128));
-    if (!glds) launch_count(LC_GEMM_REGISTER_STAGED);
+    counter_add(BIG == 2 ? LC_GEMM_256X128 : BIG == 1 ? (NW == 16 ? LC_GEMM_W16_256 : LC_GEMM_TWO_STAGE_256) : (NW == 4 ? LC_GEMM_W4_128 : LC_GEMM_W8_128));
+    if (!glds) counter_add(LC_GEMM_REGISTER_STAGED);
     if (glds) {
         hipLaunchKernelGGL(kt, dim3(tiles), dim3(NW * 64), lds, s, p, p2);
     } else {
@@ -2223,7 +2223,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     *reinterpret_cast<f32x4*>(dst) = v;
 }
 
-bool g_gemm_splitk128 = true;
+int g_gemm_splitk128 = 1;    // split-K of the 128x128 kernel where GemmArgs::split_ws allows it
 constexpr int kSplit128Slots = 512;    // 128x128 workgroups the chip holds at once (2 per CU)
 constexpr int kSplit128MinSteps = 8;   // k-steps of 64 a slice keeps at least
 
@@ -2242,7 +2242,7 @@ static int splitk128_factor(int M, int N, int K, int num_cu) {
     return best;
 }
 
-bool g_conv_implicit = true;
+int g_conv_implicit = 1;     // the texture models' 3 x 3 convolutions gather their A operand themselves | 0: im2col + GEMM
 
 template <int EPI>
 hipError_t launch_conv(const GemmArgs& p, hipStream_t s) {
@@ -2254,20 +2254,21 @@ hipError_t launch_conv(const GemmArgs& p, hipStream_t s) {
         done = true;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    launch_count(LC_GEMM_CONV_IMPLICIT);
+    counter_add(LC_GEMM_CONV_IMPLICIT);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, s, p);
     return hipGetLastError();
 }
 
-static int g_gemm_waves = 0;  // 0 = automatic tile choice
-int g_gemm_raster = -1;
-int g_gemm_auto_rule = 2, g_num_cu = 256;
-bool g_gemm_splitk = false;      // deterministic split-K for deep-K residual GEMMs on under-filled grids (measured: no gain)
-int g_gemm_persistent_resid = 0;   // experiment switch (r3g_set_option "gemm_persistent_resid")
-bool g_gemm_persistent = true;   // phased kernel as a persistent grid when there are more 256x256 tiles than CUs
-bool g_gemm_phased = true;   // 256x256 tiles run the phased (counted-vmcnt) kernel instead of the two-stage one
-bool g_gemm_wide_epilogue = true;
-bool g_gemm_gelu_pk = true;   // GELU epilogues in packed fp16 (gemm_common.h)
+int g_gemm_waves = 0;        // tile kernel: 0 automatic | 4 | 8 | 9 | 10 | 11 | 12 | 13 | 16 | 32 (include/r3g.h)
+int g_gemm_raster = -1;      // tile columns per rasterisation group | < 0: automatic
+int g_gemm_auto_rule = 2;    // tile-choice rule: 0 the first version | 1 round 2's | 2 the current one
+int g_num_cu = 256;          // the CUs the tile rules assume ("gemm_num_cu"; r3g_create stores the device's)
+int g_gemm_splitk = 0;       // deterministic split-K for deep-K residual GEMMs on under-filled grids (measured: no gain)
+int g_gemm_persistent_resid = 0;   // experiment switch: persistent form also for the fp32 (bit 0) / bf16 (bit 1) residual epilogues
+int g_gemm_persistent = 1;   // phased kernel as a persistent grid when there are more 256x256 tiles than CUs
+int g_gemm_phased = 1;       // 256x256 tiles run the phased (counted-vmcnt) kernel instead of the two-stage one
+int g_gemm_wide_epilogue = 1;   // stores go through the wave-private LDS transpose (GemmArgs::wide_epilogue)
+int g_gemm_gelu_pk = 1;      // GELU epilogues in packed fp16 (gemm_common.h) | 0: fp32 with v_exp_f32 / v_rcp_f32 (rounds 3-4)
 
 template <int EPI>
 hipError_t launch_epi(const GemmArgs& p, const GemmArgs& p2, bool glds, hipStream_t s) {
@@ -2341,33 +2342,28 @@ hipError_t launch_epi(const GemmArgs& p, const GemmArgs& p2, bool glds, hipStrea
 
 }  // namespace
 
-std::atomic<int64_t> g_launch_counters[LC_COUNT];
-const char* launch_counter_name(int which) {
-    static const char* const names[LC_COUNT] = {
-        "gemm_w4_128", "gemm_w8_128", "gemm_w16_256", "gemm_two_stage_256", "gemm_256x128", "gemm_phased", "gemm_phased_persistent",
-        "gemm_mixed", "gemm_splitk2", "gemm_splitk128", "gemm_deep_ring", "gemm_conv_implicit", "gemm_register_staged", "gemm_fp8",
-        "attn_gen1", "attn_pipelined", "attn_gen2", "attn_gen3", "attn_gen4", "attn_gen5", "attn_gen6", "attn_gen9", "attn_register_staged",
-        "ln_rows1", "ln_rows4", "ln_fixed_count", "ln_mode_inst", "mc_rows4", "mc_rows8", "mc_rows16", "mc_rows32", "mc_deferred_rows"};
-    return which >= 0 && which < LC_COUNT ? names[which] : nullptr;
-}
+int g_gemm_glds = 1;         // staging path: LDS-DMA | 0: register-staged ("lds_dma", kernels.h)
 
-static bool g_gemm_glds = true;
-void gemm_set_glds(bool on) { g_gemm_glds = on; }
-bool gemm_glds() { return g_gemm_glds; }
-void gemm_set_raster(int group) { g_gemm_raster = group; }
-void gemm_set_auto_rule(int rule, int num_cu) {
-    if (rule >= 0) g_gemm_auto_rule = rule;
-    if (num_cu > 0) g_num_cu = num_cu;
-}
-void gemm_set_wide_epilogue(bool on) { g_gemm_wide_epilogue = on; }
-void gemm_set_gelu_pk(bool on) { g_gemm_gelu_pk = on; }
-void gemm_set_phased(bool on) { g_gemm_phased = on; }
-void gemm_set_persistent(bool on) { g_gemm_persistent = on; }
-void gemm_set_persistent_resid(int mask) { g_gemm_persistent_resid = mask & 3; }
-void gemm_set_splitk(bool on) { g_gemm_splitk = on; }
-void gemm_set_splitk128(bool on) { g_gemm_splitk128 = on; }
-void gemm_set_xcd_walk(bool on) { g_gemm_xcd_walk = on; }
-void gemm_set_conv_implicit(bool on) { g_conv_implicit = on; }
+const Option g_gemm_options[] = {
+    {"gemm_waves", &g_gemm_waves, OPT_KEEP,
+     [](int v) { return v == 0 || v == 4 || v == 8 || v == 9 || v == 10 || v == 11 || v == 12 || v == 13 || v == 16 || v == 32; }},
+    {"gemm_raster", &g_gemm_raster, OPT_ANY},
+    {"gemm_auto_rule", &g_gemm_auto_rule, OPT_KEEP, [](int v) { return v >= 0; }},
+    {"gemm_num_cu", &g_num_cu, OPT_KEEP, [](int v) { return v > 0; }},
+    {"gemm_wide_epilogue", &g_gemm_wide_epilogue},
+    {"gemm_phased", &g_gemm_phased},
+    {"gemm_persistent", &g_gemm_persistent},
+    {"gemm_persistent_resid", &g_gemm_persistent_resid, OPT_MASK, nullptr, 3},
+    {"gemm_splitk", &g_gemm_splitk},
+    {"gemm_splitk128", &g_gemm_splitk128},
+    {"conv_implicit", &g_conv_implicit},
+    {"gemm_xcd_walk", &g_gemm_xcd_walk},
+    {"gemm_epi_slices", &g_gemm_epi_slices},
+    {"gemm_mixed", &g_gemm_mixed},
+    {"gemm_persistent_qkv", &g_gemm_persistent_qkv},
+    {"gelu_pk", &g_gemm_gelu_pk},
+    {}};
+
 bool gemm_conv_implicit() { return g_conv_implicit && g_gemm_glds && g_gemm_waves == 0; }
 // the automatic rule of launch_epi (rule 2) for ONE problem: does it take 256 x 256 tiles (the phased kernel, where K % 128 == 0)?
 bool gemm_auto_takes_256(int M, int N, int K) {
@@ -2379,33 +2375,6 @@ bool gemm_auto_takes_256(int M, int N, int K) {
     return N % 256 == 0 && t256 >= 128 && (K >= 2048 || t256 >= 2048 || (wide_enough && fills));
 }
 int gemm_splitk128_factor(int M, int N, int K) { return splitk128_factor(M, N, K, g_num_cu); }
-void gemm_set_epi_slices(bool on) { g_gemm_epi_slices = on; }
-void gemm_set_mixed(bool on) { g_gemm_mixed = on; }
-void gemm_set_persistent_qkv(bool on) { g_gemm_persistent_qkv = on; }
-void gemm_set_config(int waves) {
-    if (waves == 0 || waves == 4 || waves == 8 || waves == 9 || waves == 10 || waves == 11 || waves == 12 || waves == 13 || waves == 16 || waves == 32) g_gemm_waves = waves;
-}
-
-bool gemm_get_option(const char* name, int* value) {
-    if (!strcmp(name, "gemm_waves")) *value = g_gemm_waves;
-    else if (!strcmp(name, "gemm_raster")) *value = g_gemm_raster;
-    else if (!strcmp(name, "gemm_auto_rule")) *value = g_gemm_auto_rule;
-    else if (!strcmp(name, "gemm_num_cu")) *value = g_num_cu;
-    else if (!strcmp(name, "gemm_wide_epilogue")) *value = g_gemm_wide_epilogue ? 1 : 0;
-    else if (!strcmp(name, "gemm_phased")) *value = g_gemm_phased ? 1 : 0;
-    else if (!strcmp(name, "gemm_persistent")) *value = g_gemm_persistent ? 1 : 0;
-    else if (!strcmp(name, "gemm_persistent_resid")) *value = g_gemm_persistent_resid;
-    else if (!strcmp(name, "gemm_splitk")) *value = g_gemm_splitk ? 1 : 0;
-    else if (!strcmp(name, "gemm_splitk128")) *value = g_gemm_splitk128 ? 1 : 0;
-    else if (!strcmp(name, "conv_implicit")) *value = g_conv_implicit ? 1 : 0;
-    else if (!strcmp(name, "gemm_xcd_walk")) *value = g_gemm_xcd_walk ? 1 : 0;
-    else if (!strcmp(name, "gemm_epi_slices")) *value = g_gemm_epi_slices ? 1 : 0;
-    else if (!strcmp(name, "gemm_mixed")) *value = g_gemm_mixed ? 1 : 0;
-    else if (!strcmp(name, "gemm_persistent_qkv")) *value = g_gemm_persistent_qkv ? 1 : 0;
-    else if (!strcmp(name, "gelu_pk")) *value = g_gemm_gelu_pk ? 1 : 0;
-    else return false;
-    return true;
-}
 
 // the checks of gemm_launch2's three folded branches that depend on the switches and the shape alone (one problem, batch 1)
 bool gemm_fold_supported(int epi, int M, int N, int K) {
@@ -2476,7 +2445,7 @@ hipError_t gemm_launch2(const GemmArgs& p_in, int batch, const GemmArgs* p2_in, 
         }
         if (S > 1) {
             g_last_splitk_slices = S;
-            launch_count(LC_GEMM_SPLITK128);
+            counter_add(LC_GEMM_SPLITK128);
             GemmArgs q = p;
             q.K = p.K / S;
             q.batch = S;
@@ -2507,7 +2476,7 @@ hipError_t gemm_launch2(const GemmArgs& p_in, int batch, const GemmArgs* p2_in, 
         const int64_t MN = (int64_t)p.M * p.N;
         if (S > 1 && (int64_t)S * MN <= p.split_ws_elems) {
             g_last_splitk_slices = S;
-            launch_count(LC_GEMM_SPLITK128);
+            counter_add(LC_GEMM_SPLITK128);
             GemmArgs q = p;
             q.K = p.K / S;
             q.batch = S;

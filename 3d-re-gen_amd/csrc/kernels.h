@@ -5,12 +5,15 @@
 #include <stdint.h>
 #include <atomic>
 
+#include "options.h"
+
 namespace r3g {
 
-// ------------------------------------------------------------------ launch counters (r3g_get_counter)
-// Which kernel form a launch actually took: bumped on the host where the launch is issued, so that a test can tell a switch that
-// was obeyed from one that was ignored (the forms are bit-identical more often than not).  Names: launch_counter_name().
-enum LaunchCounter {
+// ------------------------------------------------------------------ event counters (r3g_get_counter)
+// One table for every counter the library keeps: the enum, g_counters and kCounterNames below it, in the same order.  All are bumped
+// on the host through counter_add.  The kernel-choice counters say which kernel form a launch actually took, bumped where the launch
+// is issued, so that a test can tell a switch that was obeyed from one that was ignored (the forms are bit-identical more often than not).
+enum Counter {
     LC_GEMM_W4_128 = 0,        // launch_cfg: 128 x 128 tile, 4 waves
     LC_GEMM_W8_128,            // 128 x 128 tile, 8 waves
     LC_GEMM_W16_256,           // 256 x 256 tile, 16 waves ("gemm_waves" 16)
@@ -34,11 +37,33 @@ enum LaunchCounter {
     LC_LN_MODE,                // ... with the affine-only / modulation-only instantiation ("ln_modes")
     LC_MC_ROWS4, LC_MC_ROWS8, LC_MC_ROWS16, LC_MC_ROWS32,   // marching cubes: row-kernel classify launches by node rows per wave
     LC_MC_DEFERRED,            // ... of them, with the deferred tiling selection ("mc_deferred")
+    // the shape model (model.cpp)
+    LC_DIT_F16_FALLBACKS,      // launch groups whose fp16 stream overflowed and that ran again on the fp32 stream ("dit_f16_guard")
+    LC_DIT_GROUPS,             // launch groups r3g_flow_sample_batch has run
+    LC_DIT_EVALS,              // DiT evaluations issued, one per launch group and step
+    LC_GEO_Q_CACHE_BUILDS,     // allocations of Model::GeoCache
+    LC_GEO_KV_GROUPS,          // (group, head) selections of the top-k KV selection
+    LC_GEO_NARROW_PASSES,      // grid passes served by the fused tail of a narrow geo decoder ("geo_narrow_fused")
+    LC_GEO_LNF_PASSES, LC_GEO_LND_PASSES,   // passes that took the folded ln_3 / ln_post + output_proj epilogues
+    // the geometry entry points (r3g_api.cpp); include/r3g.h says what each one counts
+    LC_MESHDIST_TESTS, LC_MESHINSIDE_TESTS, LC_MESHFIT_STEPS, LC_MESHTOPO_BUILDS, LC_MESHTOPO_ROUNDS, LC_MESHFILL_PLANS,
+    LC_MESHFILL_ROUNDS, LC_CLOUD_TESTS, LC_ORIENT_ROUNDS, LC_DBSCAN_LAUNCHES, LC_DBSCAN_TESTS, LC_RECON_SOLVES, LC_RECON_CYCLES,
+    LC_DEVICE_BYTES_LIVE,      // a name only: the gauge itself is g_device_bytes_live (dev_buf.h), which r3g_get_counter reads for this row
     LC_COUNT
 };
-extern std::atomic<int64_t> g_launch_counters[LC_COUNT];
-inline void launch_count(int which) { g_launch_counters[which].fetch_add(1, std::memory_order_relaxed); }
-const char* launch_counter_name(int which);
+inline constexpr const char* kCounterNames[LC_COUNT] = {
+    "gemm_w4_128", "gemm_w8_128", "gemm_w16_256", "gemm_two_stage_256", "gemm_256x128", "gemm_phased", "gemm_phased_persistent",
+    "gemm_mixed", "gemm_splitk2", "gemm_splitk128", "gemm_deep_ring", "gemm_conv_implicit", "gemm_register_staged", "gemm_fp8",
+    "attn_gen1", "attn_pipelined", "attn_gen2", "attn_gen3", "attn_gen4", "attn_gen5", "attn_gen6", "attn_gen9", "attn_register_staged",
+    "ln_rows1", "ln_rows4", "ln_fixed_count", "ln_mode_inst", "mc_rows4", "mc_rows8", "mc_rows16", "mc_rows32", "mc_deferred_rows",
+    "dit_f16_fallbacks", "dit_groups", "dit_evals", "geo_q_cache_builds", "geo_kv_groups", "geo_narrow_passes", "geo_lnf_passes",
+    "geo_lnd_passes",
+    "meshdist_tests", "meshinside_tests", "meshfit_steps", "meshtopo_builds", "meshtopo_rounds", "meshfill_plans", "meshfill_rounds",
+    "cloud_tests", "orient_rounds", "dbscan_launches", "dbscan_tests", "recon_solves", "recon_cycles",
+    "device_bytes_live"};
+static_assert(kCounterNames[LC_COUNT - 1] != nullptr, "one name per Counter");
+inline std::atomic<int64_t> g_counters[LC_COUNT];
+inline void counter_add(int which, int64_t n = 1) { g_counters[which].fetch_add(n, std::memory_order_relaxed); }
 
 // ------------------------------------------------------------------ GEMM (gemm.hip)
 enum GemmEpilogue {
@@ -143,40 +168,19 @@ struct GemmArgs {
 hipError_t gemm_launch(const GemmArgs& p, int batch, hipStream_t s);
 // two problems with the same epilogue in one launch (the second one's tiles follow the first one's); p2 may be null
 hipError_t gemm_launch2(const GemmArgs& p, int batch, const GemmArgs* p2, int batch2, hipStream_t s);
-void gemm_set_glds(bool on);  // staging path: LDS-DMA (default) or register-staged
-void attn_set_glds(bool on);
-void attn_set_ablate(int mask);   // timing-only ablation builds of the attention kernel (tools/bench_attn.py)
-void attn_set_variant(int v);       // round 6: 1 (default) fast pass with the re-stabilise test on the sum of the exponentials | 0 rounds 2-5 (generations 2 / 6 / 7)
-void attn_set_interleave(int v);    // the 64-query kernel's fast pass: 0 (default) automatic | 1 softmax inside the MFMA gaps of one key tile (measured slower) | 2 skewed across key blocks in steady state | 3 clustered
-void attn_set_async_stage(int v);   // 1 (default): the variant-1 kernels issue their LDS-DMA from inline asm, unseen by the compiler's wait counts | 0: through the builtin
-void attn_set_pipelined(bool on);  // software-pipelined attention kernel (off by default: slower) vs the plain one
-void gemm_set_config(int waves);   // tile kernel: 0 automatic | 4 | 8 | 9 | 10 | 11 | 12 | 13 | 16 | 32 (include/r3g.h)
-void gemm_set_raster(int group);
-void gemm_set_auto_rule(int rule, int num_cu);  // tile-choice rule (0: first version, 1: current); num_cu > 0 sets the CU count
-void gemm_set_persistent_qkv(bool on);   // fused QKV launches on the persistent phased kernel (default on since round 6)
-void gemm_set_epi_slices(bool on);   // persistent phased kernel: bf16 / fused-QKV epilogues in 64-row passes through the wave's slices of k-tile buffer 1 (default on)
-void gemm_set_mixed(bool on);        // a single block's [fused QKV | MLP-in + GELU] as one persistent launch (default on)
 // fused QKV projection (pq, EPI_QKV) and MLP-in + GELU(tanh) (pm) over the same rows: one launch when the grid fills the machine
 hipError_t gemm_launch_qkv_mlp(const GemmArgs& pq, const GemmArgs& pm, hipStream_t s);
 bool gemm_auto_takes_256(int M, int N, int K);   // the automatic tile rule sends one (M, N, K) problem to the 256 x 256 kernels
-void gemm_set_conv_implicit(bool on);   // the texture models' 3 x 3 convolutions gather their A operand themselves (default on) | im2col + GEMM
-bool gemm_conv_implicit();              // ... and the staging path / tile override allow it right now
-void gemm_set_xcd_walk(bool on);        // persistent phased kernel: contiguous tile range per XCD (default on)
-void gemm_set_splitk128(bool on);    // split-K of the 128x128 kernel where GemmArgs::split_ws allows it (default on)
+bool gemm_conv_implicit();              // "conv_implicit" is on, and the staging path / tile override allow it right now
 int gemm_last_splitk_slices();          // the K slices the last gemm_launch / gemm_launch2 of this process actually ran with (1 = no split)
 int gemm_splitk128_factor(int M, int N, int K);   // the number of K slices the rule picks for one problem (1 = no split)
-void gemm_set_splitk(bool on);       // deterministic split-K over 256x256 tiles for under-filled deep-K residual GEMMs
-void gemm_set_persistent_resid(int mask);   // persistent form also for the fp32 (bit 0) / bf16 (bit 1) residual epilogues
-void gemm_set_persistent(bool on);   // phased kernel walks several tiles per workgroup (default on)
-void gemm_set_phased(bool on);   // 256x256 tiles: phased kernel (default) or the two-stage one
-void gemm_set_gelu_pk(bool on);   // GELU epilogues in packed fp16 (default on) | fp32 with v_exp_f32 / v_rcp_f32 (rounds 3-4)
-void gemm_set_wide_epilogue(bool on);  // 4|8 waves per 128x128 tile, 2|3 LDS stages
-bool gemm_glds();                      // the staging path gemm_set_glds selected
-// current value of a switch that lives in gemm.hip, by its r3g_set_option name; false: not one of them
-bool gemm_get_option(const char* name, int* value);
 // gemm_launch2 serves the folded geo-decoder epilogue `epi` (EPI_RESID_BF16_ST, EPI_BF16_GELU_ERF_LNF, EPI_RESID_BF16_LND) for one
 // problem of this shape under the current staging / epilogue switches: exactly its argument checks that do not depend on pointers
 bool gemm_fold_supported(int epi, int M, int N, int K);
+extern const Option g_gemm_options[];   // the switches of gemm.hip
+// the two variables of "lds_dma" (model.cpp's row; gemm.hip / attn.hip): operand staging by LDS-DMA (1, default) or through registers.
+// r3g_op_gemm and r3g_op_attention write one of them around their one launch.
+extern int g_gemm_glds, g_attn_glds;
 
 // ------------------------------------------------------------------ attention (attn.hip)
 constexpr int kAttnMaxEntries = 8;
@@ -210,19 +214,10 @@ struct AttnArgs {
 };
 
 hipError_t attention_launch(const AttnArgs& p, hipStream_t s);
-bool attn_glds();
-bool attn_get_option(const char* name, int* value);   // as gemm_get_option, for the switches of attn.hip
 // factor the producers of Q fold into it for the current attention kernel: scale * log2(e) (generation 2), or 1
 float attn_q_scale(float scale);
-void attn_set_wide_min(int items);     // generation 7: 256-query workgroups (generation 6) from this many work items on (default 2048)
-void attn_set_prio(int v);            // generation 9: 0 no s_setprio | 1 matrix phase raised | 2 softmax phases raised
-void attn_set_stamps(int on);         // generation 9: print per-phase s_memtime sums of every launch to stderr (timing experiments)
-void attn_set_generation(int gen);   // 7 (default: 6 on deep grids, else 2) | 2 | 6 | 1: the first-round kernel (expects plain Q; same V^T layout)
-void ln_set_rows4_min(int rows);     // automatic rule: launches of at least this many rows take 4 rows per wave (65536)
-void ln_set_modes(bool on);         // LayerNorm: compile-time instantiations for the affine-only / modulation-only launches (default on)
-void ln_set_rows_per_wave(int rows);  // LayerNorm / ln_dot row kernels: 0 automatic | 1 | 4 rows per wave
-void ln_set_fixed_count(bool on);     // 1 (default): compile-time element counts for C = 1024 / 1536
-bool ln_get_option(const char* name, int* value);     // as gemm_get_option, for the "ln_*" switches (elem.hip)
+extern const Option g_attn_options[];   // the switches of attn.hip
+extern const Option g_ln_options[];     // the "ln_*" switches (elem.hip)
 
 // ------------------------------------------------------------------ elementwise / norms (elem.hip)
 // y(bf16)[r][c] = ((x - mean) * rstd * (w ? w[c] : 1) + (b ? b[c] : 0)) * (1 + scale[batch][c]) + shift[batch][c]

@@ -5,14 +5,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "options.h"
 #include "surf_compact_kernels.h"
 
 namespace r3g {
 
-void mc_set_deferred(bool on);         // row kernel: tiling selection batched per wave (default) or per row
-void mc_set_rows_per_wave(int rows);  // node rows a wave marches through in the row kernel (4|8|16|32)
-bool mc_get_deferred();
-int mc_get_rows_per_wave();
+extern const Option g_mc_options[];   // the "mc_*" switches
 size_t mc_workspace_bytes(int n0, int n1, int n2, SurfWorkspaceLayout* lay);
 
 // K1 + K2 (surf_scan_launch).  After the stream drains: status word at ws+off_small, totals {nV, nF, nNZ} at +16.

@@ -486,12 +486,12 @@ __global__ __launch_bounds__(kEmitWg) void mc_faces(int nx, int ny, int cx, int 
 
 namespace r3g {
 
-static int g_rows_per_wave = 16;
-static bool g_deferred = true;   // row kernel with the tiling selection batched over all rows of a wave
-void mc_set_deferred(bool on) { g_deferred = on; }
-void mc_set_rows_per_wave(int rows) { g_rows_per_wave = rows == 4 || rows == 8 || rows == 32 ? rows : 16; }
-bool mc_get_deferred() { return g_deferred; }
-int mc_get_rows_per_wave() { return g_rows_per_wave; }
+static int g_rows_per_wave = 16;   // node rows a wave marches through in the row kernel (4 | 8 | 16 | 32)
+static int g_deferred = 1;         // row kernel with the tiling selection batched over all rows of a wave | 0: per row
+const Option g_mc_options[] = {
+    {"mc_rows", &g_rows_per_wave, OPT_ELSE, [](int v) { return v == 4 || v == 8 || v == 32; }, 16},
+    {"mc_deferred", &g_deferred},
+    {}};
 
 size_t mc_workspace_bytes(int n0, int n1, int n2, SurfWorkspaceLayout* lay) {
     return surf_workspace_bytes(n0, n1, n2, 12 * (uint64_t)n0 * n1 * n2, lay);   // edge -> vertex id table, int32 x 3 per node
@@ -520,8 +520,8 @@ hipError_t mc_count_launch(const float* grid, int n0, int n1, int n2, double lev
             kern = rows == 4 ? mc_classify_rows2<4> : rows == 8 ? mc_classify_rows2<8> : rows == 32 ? mc_classify_rows2<32>
                                                                                                    : mc_classify_rows2<16>;
         }
-        launch_count(rows == 4 ? LC_MC_ROWS4 : rows == 8 ? LC_MC_ROWS8 : rows == 32 ? LC_MC_ROWS32 : LC_MC_ROWS16);
-        if (g_deferred) launch_count(LC_MC_DEFERRED);
+        counter_add(rows == 4 ? LC_MC_ROWS4 : rows == 8 ? LC_MC_ROWS8 : rows == 32 ? LC_MC_ROWS32 : LC_MC_ROWS16);
+        if (g_deferred) counter_add(LC_MC_DEFERRED);
         hipLaunchKernelGGL(kern, dim3((tasks + 3) / 4), dim3(kBlock), 0, stream, grid, nx, ny, cx, cy, cz,
                            lo, exact, level, classic, (uint2*)(ws + lay.off_act), (uint4*)(ws + lay.off_blk),
                            chunk_sums, chunk_nz, status);

@@ -448,9 +448,9 @@ static hipError_t compact_mesh(Arena& ar, float* verts, int64_t nv, int32_t* fac
     return hipSuccess;
 }
 
-static bool g_floater_by_vertex = false;   // option "floater_by_vertex": rounds 1-2 joined components through shared vertices
-void mesh_set_floater_by_vertex(bool on) { g_floater_by_vertex = on; }
-bool mesh_get_floater_by_vertex() { return g_floater_by_vertex; }
+// option "floater_by_vertex": 0 (default) faces joined through shared edges (MeshLab) | 1 through shared vertices (rounds 1-2)
+static int g_floater_by_vertex = 0;
+const Option g_mesh_options[] = {{"floater_by_vertex", &g_floater_by_vertex}, {}};
 
 static int64_t edge_table_slots(int64_t nf) {
     int64_t cap = 64;

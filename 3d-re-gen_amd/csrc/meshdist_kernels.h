@@ -21,8 +21,5 @@ hipError_t grid_csr_fill(char* ws, const GridCsrLayout& lay, int64_t nf, const r
 hipError_t meshdist_query(char* ws, const GridCsrLayout& lay, const r3g_md::Grid& g, const int32_t* pairs, const float* points,
                           int64_t n, float* dist2, int32_t* face, hipStream_t s);
 
-void meshdist_add_tests(int64_t n);     // r3g_get_counter("meshdist_tests")
-int64_t meshdist_tests_total();
-
 }  // namespace r3g
 #endif

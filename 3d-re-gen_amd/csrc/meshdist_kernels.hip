@@ -5,8 +5,6 @@
 // open, is absorbed by the (dist2, face) comparison.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_GRID_HD static __host__ __device__ __forceinline__
@@ -67,8 +65,6 @@ __global__ __launch_bounds__(kT) void md_query(Grid g, const Tri* __restrict__ t
     if ((threadIdx.x & 63) == 0 && t) atomicAdd(&sm->tests, t);
 }
 
-std::atomic<int64_t> g_tests{0};
-
 }  // namespace
 
 static_assert(sizeof(Tri) == 48, "triangle records are three 16-byte loads");
@@ -96,8 +92,5 @@ hipError_t meshdist_query(char* ws, const GridCsrLayout& lay, const Grid& g, con
                        (const unsigned*)(ws + lay.off_starts), pairs, points, n, dist2, face, (GridCsrSmall*)(ws + lay.off_small));
     return hipGetLastError();
 }
-
-void meshdist_add_tests(int64_t n) { g_tests += n; }
-int64_t meshdist_tests_total() { return g_tests.load(); }
 
 }  // namespace r3g

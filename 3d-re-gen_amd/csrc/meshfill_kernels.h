@@ -53,9 +53,5 @@ hipError_t meshfill_emit(const char* ws, const MeshfillLayout& lay, int64_t nv, 
 hipError_t meshfill_loops(const char* ws, const MeshfillLayout& lay, int64_t max_loop, int64_t loops, int64_t loop_edges,
                           int64_t* loop_start, int32_t* loop_verts, int32_t* status, hipStream_t s);
 
-void meshfill_add_counters(int64_t plans, int64_t rounds);      // r3g_get_counter("meshfill_plans" / "meshfill_rounds")
-int64_t meshfill_plans_total();
-int64_t meshfill_rounds_total();
-
 }  // namespace r3g
 #endif

@@ -7,8 +7,6 @@
 // the atomics are integer adds and one maximum, and their order decides nothing.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_MF_HD static __host__ __device__ __forceinline__
@@ -280,8 +278,6 @@ Plan plan_of(const char* ws, const MeshfillLayout& lay) {
 
 unsigned tile_grid(int64_t tiles) { return tiles < 1 ? 1u : (tiles > 4096 ? 4096u : (unsigned)tiles); }
 
-std::atomic<int64_t> g_plans{0}, g_rounds{0};
-
 }  // namespace
 
 static_assert(sizeof(Small) == 40, "r3g_mf::Small travels through the context's 64-byte pinned buffer");
@@ -394,12 +390,5 @@ hipError_t meshfill_loops(const char* ws, const MeshfillLayout& lay, int64_t max
     R3G_HIP(hipMemcpyAsync(loop_verts, ws + lay.off_lverts, 4 * (size_t)loop_edges, hipMemcpyDeviceToDevice, s));
     return hipGetLastError();
 }
-
-void meshfill_add_counters(int64_t plans, int64_t rounds) {
-    g_plans += plans;
-    g_rounds += rounds;
-}
-int64_t meshfill_plans_total() { return g_plans.load(); }
-int64_t meshfill_rounds_total() { return g_rounds.load(); }
 
 }  // namespace r3g

@@ -28,8 +28,5 @@ hipError_t meshfit_closest(char* md_ws, const GridCsrLayout& lay, const r3g_md::
 hipError_t meshfit_step(char* ws, const char* md_ws, const GridCsrLayout& lay, const r3g_md::Grid& g, const int32_t* pairs,
                         const float* points, int64_t n, const float* weights, const r3g_md::Sim& x, int mode, float md2, hipStream_t s);
 
-void meshfit_add_steps(int64_t n);      // r3g_get_counter("meshfit_steps")
-int64_t meshfit_steps_total();
-
 }  // namespace r3g
 #endif

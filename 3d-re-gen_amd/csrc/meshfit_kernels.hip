@@ -9,8 +9,6 @@
 // in index order and runs the same tree.  No floating-point atomics, and no integer ones either: the counts go the same way.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_GRID_HD static __host__ __device__ __forceinline__
@@ -107,8 +105,6 @@ __global__ __launch_bounds__(kT) void mf_final(const MeshfitRecord* __restrict__
     if (threadIdx.x == 65) out->tests = shi[0][1] + shi[1][1] + shi[2][1] + shi[3][1];
 }
 
-std::atomic<int64_t> g_steps{0};
-
 }  // namespace
 
 static_assert(sizeof(MeshfitRecord) == 8 * r3g_md::kFitRecord, "a partial record is kFitRecord 8-byte slots");
@@ -136,8 +132,5 @@ hipError_t meshfit_step(char* ws, const char* md_ws, const GridCsrLayout& lay, c
     hipLaunchKernelGGL(mf_final, dim3(1), dim3(kT), 0, s, (const MeshfitRecord*)(rec + 1), (int)nb, r3g_md::fit_terms(mode), rec);
     return hipGetLastError();
 }
-
-void meshfit_add_steps(int64_t n) { g_steps += n; }
-int64_t meshfit_steps_total() { return g_steps.load(); }
 
 }  // namespace r3g

@@ -22,8 +22,5 @@ hipError_t grid_csr_fill(char* ws, const GridCsrLayout& lay, int64_t nf, const r
 hipError_t meshinside_query(char* ws, const GridCsrLayout& lay, const r3g_mi::Grid2& g, int axis, const int32_t* pairs,
                             const float* points, int64_t n, int32_t* count, hipStream_t s);
 
-void meshinside_add_tests(int64_t n);     // r3g_get_counter("meshinside_tests")
-int64_t meshinside_tests_total();
-
 }  // namespace r3g
 #endif

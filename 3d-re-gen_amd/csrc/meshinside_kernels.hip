@@ -5,8 +5,6 @@
 // The order of the faces inside a column, which the builder leaves open, only permutes the terms of an integer sum.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_GRID_HD static __host__ __device__ __forceinline__
@@ -62,8 +60,6 @@ __global__ __launch_bounds__(kT) void mi_query(Grid2 g, int axis, const Rec* __r
     if ((threadIdx.x & 63) == 0 && t) atomicAdd(&sm->tests, t);
 }
 
-std::atomic<int64_t> g_tests{0};
-
 }  // namespace
 
 static_assert(sizeof(Rec) == 48, "face records are three 16-byte loads");
@@ -91,8 +87,5 @@ hipError_t meshinside_query(char* ws, const GridCsrLayout& lay, const Grid2& g, 
                        (const unsigned*)(ws + lay.off_starts), pairs, points, n, count, (GridCsrSmall*)(ws + lay.off_small));
     return hipGetLastError();
 }
-
-void meshinside_add_tests(int64_t n) { g_tests += n; }
-int64_t meshinside_tests_total() { return g_tests.load(); }
 
 }  // namespace r3g

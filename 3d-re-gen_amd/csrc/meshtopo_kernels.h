@@ -50,9 +50,5 @@ hipError_t meshtopo_finish(char* ws, const MeshtopoLayout& lay, const float* ver
 // reverse in place: flip, then (outward 1) the orientable bodies of negative volume or (outward 2) all of them if the total is
 hipError_t meshtopo_apply(char* ws, const MeshtopoLayout& lay, int32_t* faces, int64_t nf, int outward, hipStream_t s);
 
-void meshtopo_add_counters(int64_t builds, int64_t rounds);     // r3g_get_counter("meshtopo_builds" / "meshtopo_rounds")
-int64_t meshtopo_builds_total();
-int64_t meshtopo_rounds_total();
-
 }  // namespace r3g
 #endif

@@ -8,8 +8,6 @@
 // min and a max, the labels only ever decrease towards a fixed point that the definition fixes.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_MT_HD static __host__ __device__ __forceinline__
@@ -288,8 +286,6 @@ __global__ __launch_bounds__(kT) void mt_apply(int32_t* __restrict__ faces, int6
     add_count(&sm->bodies_reversed, nbodies);
 }
 
-std::atomic<int64_t> g_builds{0}, g_rounds{0};
-
 }  // namespace
 
 static_assert(sizeof(Small) == 136, "r3g_mt::Small travels through the context's pinned buffer");
@@ -368,12 +364,5 @@ hipError_t meshtopo_apply(char* ws, const MeshtopoLayout& lay, int32_t* faces, i
                        (const long long*)(ws + lay.off_bodyvol), outward, (Small*)(ws + lay.off_small));
     return hipGetLastError();
 }
-
-void meshtopo_add_counters(int64_t builds, int64_t rounds) {
-    g_builds += builds;
-    g_rounds += rounds;
-}
-int64_t meshtopo_builds_total() { return g_builds.load(); }
-int64_t meshtopo_rounds_total() { return g_rounds.load(); }
 
 }  // namespace r3g

@@ -52,39 +52,96 @@ static inline int64_t rup(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 // single blocks: MLP-in GEMM on a second stream beside the attention kernel.  Off since the GEMM became a persistent grid of
 // one 160 KiB-LDS workgroup per CU: the two kernels can no longer share a CU and take turns (measured 1.4 % slower with it)
-static bool g_overlap_mlp = false;
-static bool g_group_streams = true;   // img + txt GEMMs of a double block in one launch
-static bool g_fuse_qkv = true;    // QKV split + q/k norm + V transpose in the projection's epilogue
-static bool g_batch_mods = true;  // one GEMV launch for all modulations of a DiT forward
+static int g_overlap_mlp = 0;
+static int g_group_streams = 1;   // img + txt GEMMs of a double block in one launch
+static int g_fuse_qkv = 1;    // QKV split + q/k norm + V transpose in the projection's epilogue
+static int g_batch_mods = 1;  // one GEMV launch for all modulations of a DiT forward
 static int g_geo_fp8 = 0;   // BASELINE.json configs[3]: geo decoder GEMMs on fp8 (e4m3) operands: 0 off (default) | 1 c_q + MLP | 2 MLP only | 3 c_q only
 constexpr float kGeoHiddenScale = 1.0f / 16.0f;   // static scale of the fp8 MLP hidden: |GELU| up to 28 representable
-static bool g_geo_resid_bf16 = true;   // geo decoder block: 16-bit residual stream (the reference's is fp16)
-static bool g_cfg_dedup = true;   // carry the (uniform) unconditional context as one weighted token
+static int g_geo_resid_bf16 = 1;   // geo decoder block: 16-bit residual stream (the reference's is fp16)
+static int g_cfg_dedup = 1;   // carry the (uniform) unconditional context as one weighted token
 static unsigned g_option_epoch = 0;   // bumped by every r3g_set_option: cached intermediate results (Model::GeoCache) are tied to it
-static long long g_geo_q_cache_bytes = -1;   // budget of that cache in bytes (option "geo_q_cache_gb"); < 0: 30 % of the device's memory
-static bool g_geo_q_cache = true;   // keep the object-independent query side of the geo decoder resident in HBM (Model::GeoCache)
-static bool g_dit_f16_guard = true;    // option "dit_f16_guard": check the latents of an fp16-stream group, fall back to fp32 on overflow
-static bool g_geo_ln3_fold = true;    // option "geo_ln3_fold" (round 6): the geo decoder's ln_3 folded into c_proj's epilogue (statistics) and c_fc (W' = W gamma, rstd (acc - mean c1) + c2)
-static bool g_geo_lnd_fused = true;   // option "geo_lnd_fused" (round 6): ln_post + output_proj folded into the geo decoder's last residual GEMM
-static std::atomic<int64_t> g_geo_q_cache_builds{0};   // allocations of Model::GeoCache so far (r3g_get_counter "geo_q_cache_builds")
-static std::atomic<int64_t> g_dit_groups{0};       // launch groups r3g_flow_sample_batch has run (r3g_get_counter)
-static std::atomic<int64_t> g_dit_evals{0};        // DiT evaluations issued, one per launch group and step (r3g_get_counter "dit_evals")
-static std::atomic<int64_t> g_dit_f16_fallbacks{0};    // how often that happened (r3g_set_option("dit_f16_fallbacks_reset", ...) / stderr line)
-static bool g_dit_resid_f16 = true;   // the DiT's residual stream of the de-duplicated CFG path in fp16 (the reference's activation type) instead of fp32
-static bool g_skip_zero_step = true;   // skip the DiT evaluation of a step whose d_sigma is 0 (upstream's last step)
+static int g_geo_q_cache_gb = -1;   // budget of that cache in GiB (option "geo_q_cache_gb"); < 0: 30 % of the device's memory
+static int g_geo_q_cache = 1;   // keep the object-independent query side of the geo decoder resident in HBM (Model::GeoCache)
+static int g_dit_f16_guard = 1;    // option "dit_f16_guard": check the latents of an fp16-stream group, fall back to fp32 on overflow
+static int g_geo_ln3_fold = 1;    // option "geo_ln3_fold" (round 6): the geo decoder's ln_3 folded into c_proj's epilogue (statistics) and c_fc (W' = W gamma, rstd (acc - mean c1) + c2)
+static int g_geo_lnd_fused = 1;   // option "geo_lnd_fused" (round 6): ln_post + output_proj folded into the geo decoder's last residual GEMM
+static int g_dit_resid_f16 = 1;   // the DiT's residual stream of the de-duplicated CFG path in fp16 (the reference's activation type) instead of fp32
+static int g_skip_zero_step = 1;   // skip the DiT evaluation of a step whose d_sigma is 0 (upstream's last step)
 // r3g_flow_sample runs steps [g_flow_first_step, g_flow_last_step) of its schedule (options "flow_first_step" / "flow_last_step";
-// default: all of them).  Consecutive segments of one schedule, each continuing on the previous one's latents, are the same
-// launches as the whole schedule in one call: tests read the latents after 10, 20, ... of 50 steps this way.
-static int g_flow_first_step = 0, g_flow_last_step = 1 << 30;
+// default: all of them, a last step of -1 standing for "to the end").  Consecutive segments of one schedule, each continuing on the
+// previous one's latents, are the same launches as the whole schedule in one call: tests read the latents after 10, 20, ... of 50 steps this way.
+static int g_flow_first_step = 0, g_flow_last_step = -1;
+static int flow_last_step(int steps) { return g_flow_last_step < 0 ? steps : std::min(steps, g_flow_last_step); }
 // adaptive top-k selection of the geo decoder's cross-attention keys (options "geo_kv_topk" / "geo_kv_group" /
 // "geo_kv_stride"): 0 exact (default) | k > 0 keys kept per (group, head), clamped to num_latents | -1 upstream's rule
 static int g_geo_kv_topk = 0, g_geo_kv_group = 8192, g_geo_kv_stride = 64;
-static std::atomic<int64_t> g_geo_kv_groups{0};    // (group, head) selections made so far (r3g_get_counter "geo_kv_groups")
 // narrow geo decoder: option "geo_narrow_fused" -- everything behind the cross-attention of a decoder of width
 // 256 in one launch per pass (geo_narrow.hip) instead of the generic five
-static bool g_geo_narrow_fused = false;
-static std::atomic<int64_t> g_geo_narrow_passes{0};   // passes served by that kernel (r3g_get_counter "geo_narrow_passes")
-static std::atomic<int64_t> g_geo_lnf_passes{0}, g_geo_lnd_passes{0};   // passes that took the folded ln_3 / ln_post epilogues ("geo_lnf_passes" / "geo_lnd_passes")
+static int g_geo_narrow_fused = 0;
+
+static const Option g_model_options[] = {
+    {"fuse_qkv", &g_fuse_qkv},
+    {"batch_mods", &g_batch_mods},
+    {"cfg_dedup", &g_cfg_dedup},
+    {"skip_zero_step", &g_skip_zero_step},
+    {"geo_q_cache", &g_geo_q_cache},
+    {"geo_q_cache_gb", &g_geo_q_cache_gb, OPT_ELSE, [](int v) { return v >= 0; }, -1},
+    {"geo_resid_bf16", &g_geo_resid_bf16},
+    {"dit_resid_f16", &g_dit_resid_f16},
+    {"dit_f16_guard", &g_dit_f16_guard},
+    {"geo_fp8", &g_geo_fp8, OPT_ELSE, [](int v) { return v >= 0 && v <= 3; }, 0},
+    {"group_streams", &g_group_streams},
+    {"overlap_mlp", &g_overlap_mlp},
+    {"geo_lnd_fused", &g_geo_lnd_fused},
+    {"geo_ln3_fold", &g_geo_ln3_fold},
+    {"flow_first_step", &g_flow_first_step, OPT_ANY},
+    {"flow_last_step", &g_flow_last_step, OPT_ELSE, [](int v) { return v >= 0 && v < (1 << 30); }, -1},
+    // the "geo_kv_*" options: nothing cached depends on them, no new epoch
+    {"geo_kv_topk", &g_geo_kv_topk, OPT_REFUSE, [](int v) { return v >= -1; }, 0,
+     "r3g_set_option: geo_kv_topk is 0 (exact), a key count, or -1 (upstream's rule)", false},
+    {"geo_kv_group", &g_geo_kv_group, OPT_REFUSE, [](int v) { return v >= 256 && v % 256 == 0; }, 0,
+     "r3g_set_option: geo_kv_group must be a multiple of 256, at least 256", false},
+    {"geo_kv_stride", &g_geo_kv_stride, OPT_REFUSE, [](int v) { return v >= 1; }, 0, "r3g_set_option: geo_kv_stride must be at least 1", false},
+    {"geo_narrow_fused", &g_geo_narrow_fused, OPT_FLAG, nullptr, 0, nullptr, false},     // behind the cached query side: no new epoch
+    // = r3g_set_staging: the GEMMs' and the attention's staging path are set together and read back as 1 while both are LDS-DMA
+    {"lds_dma", &g_gemm_glds, OPT_FLAG, nullptr, 0, nullptr, true, &g_attn_glds},
+    {}};
+
+// every switch of the library: the rows of the files that own some, in one list
+static const std::vector<const Option*>& options() {
+    static const std::vector<const Option*> all = [] {
+        std::vector<const Option*> v;
+        for (const Option* t : {g_model_options, g_gemm_options, g_attn_options, g_ln_options, g_mc_options, g_mesh_options})
+            for (; t->name; ++t) v.push_back(t);
+        return v;
+    }();
+    return all;
+}
+
+static const Option* find_option(const char* name) {
+    for (const Option* o : options())
+        if (!strcmp(name, o->name)) return o;
+    return nullptr;
+}
+
+// the rules of options.h, once each
+static int store(const Option* o, const char* name, int value) {
+    if (!o) return fail(R3G_ERR_INVALID, "r3g_set_option: unknown option '%s'", name);
+    switch (o->rule) {
+        case OPT_FLAG: value = value != 0; break;
+        case OPT_ANY: break;
+        case OPT_KEEP: if (!o->ok(value)) return R3G_OK; break;
+        case OPT_ELSE: if (!o->ok(value)) value = o->other; break;
+        case OPT_MASK: value &= o->other; break;
+        case OPT_REFUSE: if (!o->ok(value)) return fail(R3G_ERR_INVALID, "%s", o->refusal); break;
+    }
+    *o->slot = value;
+    if (o->slot2) *o->slot2 = value;
+    return R3G_OK;
+}
+
+int option_store(const char* name, int value) { return store(find_option(name), name, value); }
 
 struct Model {
     r3g_model_config c{};
@@ -581,7 +638,7 @@ static int dit_forward_grouped(Model& m, const float* x_lat, float t_scalar, flo
     const int64_t catld = 5 * (int64_t)H;
     const int mh = c.dit_mlp_hidden;
     if (d.nb != NB || (E != 1 && E != 2)) return fail(R3G_ERR_STATE, "dit batch arena not prepared for %d objects", NB);
-    ++g_dit_evals;
+    counter_add(LC_DIT_EVALS);
     // The residual stream: fp32, or (option "dit_resid_f16") fp16 -- the reference's own activation type (its pipelines run in
     // fp16) -- in the same buffer: the read-modify-write epilogues of the N = 1024 projections and the LayerNorm reads move
     // half the bytes.  `xrow(r)` = the stream from row r on, in either format.
@@ -951,7 +1008,7 @@ static int kv_attention(Model& m, const uint16_t* Qp, int n, int npad, int k, hi
     m.kv_last_groups = cut.groups;
     m.kv_last_k = k;
     m.kv_last_q = Qp; m.kv_last_n = n; m.kv_last_npad = npad;
-    g_geo_kv_groups += (int64_t)cut.groups * heads;
+    counter_add(LC_GEO_KV_GROUPS, (int64_t)cut.groups * heads);
     return R3G_OK;
 }
 
@@ -1024,7 +1081,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
         const size_t per_pass = (size_t)m.qc * W * 2 * 2;
         size_t free_b = 0, total_b = 0;
         hipError_t e = hipMemGetInfo(&free_b, &total_b);
-        size_t budget = g_geo_q_cache_bytes >= 0 ? (size_t)g_geo_q_cache_bytes : (size_t)(0.30 * (double)total_b);
+        size_t budget = g_geo_q_cache_gb >= 0 ? (size_t)g_geo_q_cache_gb << 30 : (size_t)(0.30 * (double)total_b);
         if (e == hipSuccess && free_b > ((size_t)16 << 30)) budget = std::min(budget, free_b - ((size_t)16 << 30));
         else budget = 0;
         const int64_t n_cached = std::min<int64_t>(passes_all, (int64_t)(budget / per_pass));
@@ -1033,7 +1090,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
             gq.refused = true;            // every pass is recomputed, as before
         } else {
             gq.Q = gq.x0.as<uint16_t>() + n_cached * (int64_t)m.qc * W;
-            ++g_geo_q_cache_builds;
+            counter_add(LC_GEO_Q_CACHE_BUILDS);
             gq.passes = n_cached;
             gq.built.assign((size_t)n_cached, 0);
         }
@@ -1134,7 +1191,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
             ta.lnp_w = lpw; ta.lnp_b = lpb; ta.out_w = ow; ta.out_b = ob;
             ta.hidden = lfc.N; ta.n = n; ta.out = grid + start + off;
             R3G_TRY(geo_tail_launch(ta, s));
-            ++g_geo_narrow_passes;
+            counter_add(LC_GEO_NARROW_PASSES);
             continue;
         }
         {   // x1 = x0 + c_proj(attention): the old values come from the cached x0 where there is one
@@ -1157,7 +1214,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
                 pf.lnf_stats = m.lnf_stats.as<float>();
                 hipError_t e = gemm_launch(pf, 1, s);
                 if (e != hipSuccess) return hip_fail(e, "gemm_launch(geo ln_3 + mlp.c_fc)");
-                ++g_geo_lnf_passes;
+                counter_add(LC_GEO_LNF_PASSES);
             } else {
                 R3G_RC(layernorm(m.f32a, W, 0, m.xn, W, 0, n, 1, W, l3w, l3b, nullptr, nullptr, 0, 1e-6f, s, xb));
                 R3G_RC(gemm(m.xn, W, 0, lfc, 0, lfc.N, m.hid, lfc.N, 0, n, W, EPI_BF16_GELU_ERF, nullptr, 0, 1, s));
@@ -1169,7 +1226,7 @@ static int grid_query(Model& m, double bound, int R, float* grid, int64_t start,
                 hipError_t e = gemm_launch(pl, 1, s);
                 if (e != hipSuccess) return hip_fail(e, "gemm_launch(geo mlp.c_proj + ln_post + output_proj)");
                 R3G_TRY(lnd_finalize_launch(lnd_part, n, W / 64, 1e-5f, lnd_gw + W, grid + start + off, s));
-                ++g_geo_lnd_passes;
+                counter_add(LC_GEO_LND_PASSES);
                 continue;
             }
             R3G_RC(gemm(m.hid, lfc.N, 0, lfp, 0, W, m.f32a, W, 0, n, lfc.N, epi_res, nullptr, 0, 1, s));
@@ -1375,12 +1432,12 @@ static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int 
         for (int o = 0; o < n_objects; ++o) {
             float* lat = d_latents + o * n;
             const uint16_t* cond2 = d_cond2 + 2 * o * cond_elems;
-            for (int i = std::max(0, g_flow_first_step); i < std::min(steps, g_flow_last_step); ++i) {
+            for (int i = std::max(0, g_flow_first_step); i < flow_last_step(steps); ++i) {
                 const float ds = sig[i + 1] - sig[i];
                 if (ds == 0.f && g_skip_zero_step) continue;
                 R3G_TRY(hipMemcpyAsync(x2, lat, n * 4, hipMemcpyDeviceToDevice, s));
                 R3G_TRY(hipMemcpyAsync(x2 + n, lat, n * 4, hipMemcpyDeviceToDevice, s));
-                ++g_dit_evals;
+                counter_add(LC_DIT_EVALS);
                 R3G_RC(dit_forward(*m, x2, nullptr, sig[i], cond2, m->v2, 2, -1, -1, s));
                 R3G_TRY(cfg_euler_launch(lat, m->v2, n, guidance_scale, ds, s));
             }
@@ -1420,10 +1477,10 @@ static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int 
         // stream -- never silently wrong latents from a checkpoint whose activations outgrow fp16.
         const bool guard = g_dit_resid_f16 && m->H % 256 == 0 && g_dit_f16_guard;
         if (guard) R3G_TRY(hipMemcpyAsync(d.lat0, lat, (size_t)NB * n * 4, hipMemcpyDeviceToDevice, s));
-        ++g_dit_groups;
+        counter_add(LC_DIT_GROUPS);
         for (int attempt = 0; attempt < 2; ++attempt) {
             const bool allow_f16 = attempt == 0;
-            for (int i = std::max(0, g_flow_first_step); i < std::min(steps, g_flow_last_step); ++i) {
+            for (int i = std::max(0, g_flow_first_step); i < flow_last_step(steps); ++i) {
                 // the final step of upstream's schedule has d_sigma = 0: its update is x += 0 * v, so the evaluation is skipped
                 // (bit-identical; r3g_set_option("skip_zero_step", 0) evaluates it as upstream does)
                 const float ds = sig[i + 1] - sig[i];
@@ -1439,7 +1496,7 @@ static int flow_sample(Model* m, float* d_latents, const uint16_t* d_cond2, int 
             R3G_TRY(hipMemcpyAsync(&bad, d.bad, 4, hipMemcpyDeviceToHost, s));
             R3G_TRY(hipStreamSynchronize(s));
             if (!bad) break;
-            ++g_dit_f16_fallbacks;
+            counter_add(LC_DIT_F16_FALLBACKS);
             fprintf(stderr, "[r3g] the fp16 residual stream of the DiT overflowed (non-finite latents): this launch group runs again on "
                             "the fp32 stream (r3g_set_option(\"dit_resid_f16\", 0) makes that the default)\n");
             R3G_TRY(hipMemcpyAsync(lat, d.lat0, (size_t)NB * n * 4, hipMemcpyDeviceToDevice, s));
@@ -1461,35 +1518,15 @@ static std::vector<float> linspace_sigmas(int steps, float shift) {
 
 int r3g_get_counter(const char* name, int64_t* value) {
     if (!name || !value) return fail(R3G_ERR_INVALID, "r3g_get_counter: null argument");
-    if (!strcmp(name, "dit_f16_fallbacks")) *value = g_dit_f16_fallbacks;
-    else if (!strcmp(name, "dit_groups")) *value = g_dit_groups;
-    else if (!strcmp(name, "dit_evals")) *value = g_dit_evals;
-    else if (!strcmp(name, "geo_q_cache_builds")) *value = g_geo_q_cache_builds;
-    else if (!strcmp(name, "geo_kv_groups")) *value = g_geo_kv_groups;
-    else if (!strcmp(name, "geo_narrow_passes")) *value = g_geo_narrow_passes;
-    else if (!strcmp(name, "geo_lnf_passes")) *value = g_geo_lnf_passes;
-    else if (!strcmp(name, "geo_lnd_passes")) *value = g_geo_lnd_passes;
-    else if (!strcmp(name, "device_bytes_live")) *value = g_device_bytes_live.load();
-    else if (!strcmp(name, "meshdist_tests")) *value = meshdist_tests_total();
-    else if (!strcmp(name, "meshinside_tests")) *value = meshinside_tests_total();
-    else if (!strcmp(name, "meshfit_steps")) *value = meshfit_steps_total();
-    else if (!strcmp(name, "meshtopo_builds")) *value = meshtopo_builds_total();
-    else if (!strcmp(name, "meshtopo_rounds")) *value = meshtopo_rounds_total();
-    else if (!strcmp(name, "meshfill_plans")) *value = meshfill_plans_total();
-    else if (!strcmp(name, "meshfill_rounds")) *value = meshfill_rounds_total();
-    else if (!strcmp(name, "cloud_tests")) *value = cloud_tests_total();
-    else if (!strcmp(name, "orient_rounds")) *value = orient_rounds_total();
-    else if (!strcmp(name, "dbscan_launches")) *value = dbscan_launches_total();
-    else if (!strcmp(name, "dbscan_tests")) *value = dbscan_tests_total();
-    else if (!strcmp(name, "recon_solves")) *value = recon_solves_total();
-    else if (!strcmp(name, "recon_cycles")) *value = recon_cycles_total();
-    else {
-        for (int i = 0; i < LC_COUNT; ++i)
-            if (!strcmp(name, launch_counter_name(i))) { *value = g_launch_counters[i].load(std::memory_order_relaxed); return R3G_OK; }
-        return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
-    }
-    return R3G_OK;
+    for (int i = 0; i < LC_COUNT; ++i)
+        if (!strcmp(name, kCounterNames[i])) {
+            *value = i == LC_DEVICE_BYTES_LIVE ? g_device_bytes_live.load() : g_counters[i].load(std::memory_order_relaxed);
+            return R3G_OK;
+        }
+    return fail(R3G_ERR_INVALID, "r3g_get_counter: unknown counter '%s'", name);
 }
+
+const char* r3g_counter_name(int index) { return index >= 0 && index < LC_COUNT ? kCounterNames[index] : nullptr; }
 
 int r3g_model_trim(r3g_ctx* ctx) {
     NEED_MODEL("r3g_model_trim");
@@ -1653,10 +1690,10 @@ int r3g_op_gemm(const uint16_t* d_a, int64_t lda, const uint16_t* d_w, int64_t l
     GemmArgs p{};
     p.A = d_a; p.lda = lda; p.W = d_w; p.ldw = ldw; p.bias = d_bias; p.C = d_c; p.ldc = ldc; p.gate = d_gate;
     p.M = m_; p.N = n_; p.K = k_; p.epi = epilogue;
-    const bool staging = gemm_glds();      // the process-wide mode (r3g_set_staging) comes back after this launch
-    gemm_set_glds(use_lds_dma != 0);
+    const int staging = g_gemm_glds;      // the process-wide mode (r3g_set_staging) comes back after this launch
+    g_gemm_glds = use_lds_dma != 0;
     hipError_t e = gemm_launch(p, 1, (hipStream_t)stream);
-    gemm_set_glds(staging);
+    g_gemm_glds = staging;
     if (e != hipSuccess) return hip_fail(e, "r3g_op_gemm");
     return R3G_OK;
 }
@@ -1745,10 +1782,10 @@ int r3g_op_attention(const uint16_t* d_q, const uint16_t* d_k, const uint16_t* d
     p.Q = d_q; p.K = d_k; p.Vt = d_vt; p.O = d_o; p.ldo = (int64_t)heads * 64; p.strideO = (int64_t)lq * heads * 64;
     p.B = batch; p.H = heads; p.Lq = lq; p.Lq_pad = lq_pad; p.Lk = lk; p.Lk_pad = lk_pad;
     p.kv_batch_stride_zero = shared_kv; p.scale = 0.125f;
-    const bool staging = attn_glds();
-    attn_set_glds(use_lds_dma != 0);
+    const int staging = g_attn_glds;
+    g_attn_glds = use_lds_dma != 0;
     hipError_t e = attention_launch(p, (hipStream_t)stream);
-    attn_set_glds(staging);
+    g_attn_glds = staging;
     if (e != hipSuccess) return hip_fail(e, "r3g_op_attention");
     return R3G_OK;
 }
@@ -2004,117 +2041,24 @@ int r3g_prof_read_bytes(double* bytes, int n) {
     return R3G_OK;
 }
 
-// the "geo_kv_*" options take validated values (a refused value leaves the setting as it was)
-static int kv_set_option(const char* what, int value) {
-    const std::string n = what;
-    if (n == "topk") {
-        if (value < -1) return fail(R3G_ERR_INVALID, "r3g_set_option: geo_kv_topk is 0 (exact), a key count, or -1 (upstream's rule)");
-        g_geo_kv_topk = value;
-    } else if (n == "group") {
-        if (value < 256 || value % 256) return fail(R3G_ERR_INVALID, "r3g_set_option: geo_kv_group must be a multiple of 256, at least 256");
-        g_geo_kv_group = value;
-    } else if (n == "stride") {
-        if (value < 1) return fail(R3G_ERR_INVALID, "r3g_set_option: geo_kv_stride must be at least 1");
-        g_geo_kv_stride = value;
-    } else {
-        return fail(R3G_ERR_INVALID, "r3g_set_option: unknown option 'geo_kv_%s'", what);
-    }
-    return R3G_OK;
-}
-
 int r3g_set_option(const char* name, int value) {
     if (!name) return fail(R3G_ERR_INVALID, "r3g_set_option: null name");
-    if (!strncmp(name, "geo_kv_", 7)) return kv_set_option(name + 7, value);     // (nothing cached depends on them: no new epoch)
-    if (!strcmp(name, "geo_narrow_fused")) { g_geo_narrow_fused = value != 0; return R3G_OK; }     // (behind the cached query side: no new epoch)
-    ++g_option_epoch;
-    if (!strcmp(name, "fuse_qkv")) g_fuse_qkv = value != 0;
-    else if (!strcmp(name, "batch_mods")) g_batch_mods = value != 0;
-    else if (!strcmp(name, "cfg_dedup")) g_cfg_dedup = value != 0;
-    else if (!strcmp(name, "skip_zero_step")) g_skip_zero_step = value != 0;
-    else if (!strcmp(name, "geo_q_cache")) g_geo_q_cache = value != 0;
-    else if (!strcmp(name, "geo_q_cache_gb")) g_geo_q_cache_bytes = value < 0 ? -1 : (long long)value << 30;
-    else if (!strcmp(name, "geo_resid_bf16")) g_geo_resid_bf16 = value != 0;
-    else if (!strcmp(name, "dit_resid_f16")) g_dit_resid_f16 = value != 0;
-    else if (!strcmp(name, "dit_f16_guard")) g_dit_f16_guard = value != 0;
-    else if (!strcmp(name, "gelu_pk")) gemm_set_gelu_pk(value != 0);
-    else if (!strcmp(name, "geo_fp8")) g_geo_fp8 = value >= 0 && value <= 3 ? value : 0;
-    else if (!strcmp(name, "group_streams")) g_group_streams = value != 0;
-    else if (!strcmp(name, "overlap_mlp")) g_overlap_mlp = value != 0;
-    else if (!strcmp(name, "gemm_waves")) gemm_set_config(value);
-    else if (!strcmp(name, "gemm_raster")) gemm_set_raster(value);
-    else if (!strcmp(name, "gemm_auto_rule")) gemm_set_auto_rule(value, 0);
-    else if (!strcmp(name, "gemm_num_cu")) gemm_set_auto_rule(-1, value);
-    else if (!strcmp(name, "gemm_wide_epilogue")) gemm_set_wide_epilogue(value != 0);
-    else if (!strcmp(name, "gemm_phased")) gemm_set_phased(value != 0);
-    else if (!strcmp(name, "gemm_persistent")) gemm_set_persistent(value != 0);
-    else if (!strcmp(name, "gemm_persistent_resid")) gemm_set_persistent_resid(value);
-    else if (!strcmp(name, "gemm_splitk")) gemm_set_splitk(value != 0);
-    else if (!strcmp(name, "gemm_splitk128")) gemm_set_splitk128(value != 0);
-    else if (!strcmp(name, "conv_implicit")) gemm_set_conv_implicit(value != 0);
-    else if (!strcmp(name, "gemm_xcd_walk")) gemm_set_xcd_walk(value != 0);
-    else if (!strcmp(name, "ln_modes")) ln_set_modes(value != 0);
-    else if (!strcmp(name, "geo_lnd_fused")) g_geo_lnd_fused = value != 0;
-    else if (!strcmp(name, "geo_ln3_fold")) g_geo_ln3_fold = value != 0;
-    else if (!strcmp(name, "attn_variant")) attn_set_variant(value);
-    else if (!strcmp(name, "attn_interleave")) attn_set_interleave(value);
-    else if (!strcmp(name, "attn_async_stage")) attn_set_async_stage(value);
-    else if (!strcmp(name, "gemm_epi_slices")) gemm_set_epi_slices(value != 0);
-    else if (!strcmp(name, "gemm_mixed")) gemm_set_mixed(value != 0);
-    else if (!strcmp(name, "gemm_persistent_qkv")) gemm_set_persistent_qkv(value != 0);
-    else if (!strcmp(name, "flow_first_step")) g_flow_first_step = value;
-    else if (!strcmp(name, "flow_last_step")) g_flow_last_step = value < 0 ? (1 << 30) : value;
-    else if (!strcmp(name, "attn_pipelined")) attn_set_pipelined(value != 0);
-    else if (!strcmp(name, "attn_ablate")) attn_set_ablate(value);
-    else if (!strcmp(name, "attn_generation")) attn_set_generation(value);
-    else if (!strcmp(name, "attn_stamps")) attn_set_stamps(value);
-    else if (!strcmp(name, "attn_prio")) attn_set_prio(value);
-    else if (!strcmp(name, "attn_wide_min")) attn_set_wide_min(value);
-    else if (!strcmp(name, "ln_rows")) ln_set_rows_per_wave(value);
-    else if (!strcmp(name, "ln_rows4_min")) ln_set_rows4_min(value);
-    else if (!strcmp(name, "ln_fixed")) ln_set_fixed_count(value != 0);
-    else if (!strcmp(name, "floater_by_vertex")) mesh_set_floater_by_vertex(value != 0);
-    else if (!strcmp(name, "mc_rows")) mc_set_rows_per_wave(value);
-    else if (!strcmp(name, "mc_deferred")) mc_set_deferred(value != 0);
-    else if (!strcmp(name, "lds_dma")) { gemm_set_glds(value != 0); attn_set_glds(value != 0); }
-    else return fail(R3G_ERR_INVALID, "r3g_set_option: unknown option '%s'", name);
-    return R3G_OK;
+    const Option* o = find_option(name);
+    // (a refused value or an unknown name starts a new epoch as well; an unknown "geo_kv_*" name does not, like the three known ones)
+    if (o ? o->new_epoch : strncmp(name, "geo_kv_", 7) != 0) ++g_option_epoch;
+    return store(o, name, value);
 }
 
 int r3g_get_option(const char* name, int* value) {
     if (!name || !value) return fail(R3G_ERR_INVALID, "r3g_get_option: null argument");
-    if (!strcmp(name, "geo_kv_topk")) *value = g_geo_kv_topk;
-    else if (!strcmp(name, "geo_kv_group")) *value = g_geo_kv_group;
-    else if (!strcmp(name, "geo_kv_stride")) *value = g_geo_kv_stride;
-    else if (!strcmp(name, "geo_narrow_fused")) *value = g_geo_narrow_fused ? 1 : 0;
-    else if (!strcmp(name, "fuse_qkv")) *value = g_fuse_qkv ? 1 : 0;
-    else if (!strcmp(name, "batch_mods")) *value = g_batch_mods ? 1 : 0;
-    else if (!strcmp(name, "cfg_dedup")) *value = g_cfg_dedup ? 1 : 0;
-    else if (!strcmp(name, "skip_zero_step")) *value = g_skip_zero_step ? 1 : 0;
-    else if (!strcmp(name, "geo_q_cache")) *value = g_geo_q_cache ? 1 : 0;
-    else if (!strcmp(name, "geo_q_cache_gb")) *value = g_geo_q_cache_bytes < 0 ? -1 : (int)(g_geo_q_cache_bytes >> 30);
-    else if (!strcmp(name, "geo_resid_bf16")) *value = g_geo_resid_bf16 ? 1 : 0;
-    else if (!strcmp(name, "dit_resid_f16")) *value = g_dit_resid_f16 ? 1 : 0;
-    else if (!strcmp(name, "dit_f16_guard")) *value = g_dit_f16_guard ? 1 : 0;
-    else if (!strcmp(name, "geo_fp8")) *value = g_geo_fp8;
-    else if (!strcmp(name, "group_streams")) *value = g_group_streams ? 1 : 0;
-    else if (!strcmp(name, "overlap_mlp")) *value = g_overlap_mlp ? 1 : 0;
-    else if (!strcmp(name, "geo_lnd_fused")) *value = g_geo_lnd_fused ? 1 : 0;
-    else if (!strcmp(name, "geo_ln3_fold")) *value = g_geo_ln3_fold ? 1 : 0;
-    else if (!strcmp(name, "flow_first_step")) *value = g_flow_first_step;
-    else if (!strcmp(name, "flow_last_step")) *value = g_flow_last_step >= (1 << 30) ? -1 : g_flow_last_step;
-    else if (!strcmp(name, "floater_by_vertex")) *value = mesh_get_floater_by_vertex() ? 1 : 0;
-    else if (!strcmp(name, "mc_rows")) *value = mc_get_rows_per_wave();
-    else if (!strcmp(name, "mc_deferred")) *value = mc_get_deferred() ? 1 : 0;
-    else if (!strcmp(name, "lds_dma")) *value = gemm_glds() && attn_glds() ? 1 : 0;
-    else if (gemm_get_option(name, value) || attn_get_option(name, value) || ln_get_option(name, value)) return R3G_OK;
-    else return fail(R3G_ERR_INVALID, "r3g_get_option: unknown option '%s'", name);
+    const Option* o = find_option(name);
+    if (!o) return fail(R3G_ERR_INVALID, "r3g_get_option: unknown option '%s'", name);
+    *value = o->slot2 ? *o->slot && *o->slot2 : *o->slot;
     return R3G_OK;
 }
 
-int r3g_set_staging(int use_lds_dma) {
-    gemm_set_glds(use_lds_dma != 0);
-    attn_set_glds(use_lds_dma != 0);
-    return R3G_OK;
-}
+const char* r3g_option_name(int index) { return index >= 0 && index < (int)options().size() ? options()[index]->name : nullptr; }
+
+int r3g_set_staging(int use_lds_dma) { return option_store("lds_dma", use_lds_dma); }
 
 }  // extern "C"

@@ -28,8 +28,5 @@ hipError_t orient_round(char* ws, const OrientLayout& lay, int64_t n, int k, hip
 hipError_t orient_finish(char* ws, const OrientLayout& lay, const float* normals, int64_t n, int k, int8_t* sign, int32_t* tree,
                          hipStream_t s);
 
-void orient_add_rounds(int64_t n);      // r3g_get_counter("orient_rounds")
-int64_t orient_rounds_total();
-
 }  // namespace r3g
 #endif

@@ -7,8 +7,6 @@
 // the trees and carries the parities.  Integer atomics only: the forest is unique, so their order decides nothing.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_RC_HD static __host__ __device__ __forceinline__
@@ -152,8 +150,6 @@ __global__ __launch_bounds__(kT) void or_frustrated(const int32_t* __restrict__ 
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&sm->frustrated, bad);
 }
 
-std::atomic<int64_t> g_rounds{0};
-
 template <class T>
 T* at(char* ws, size_t off) {
     return (T*)(ws + off);
@@ -224,8 +220,5 @@ hipError_t orient_finish(char* ws, const OrientLayout& lay, const float* normals
     hipLaunchKernelGGL(or_frustrated, g, b, 0, s, at<int32_t>(ws, lay.off_idx), k, n, sign, at<float>(ws, lay.off_unit), sm);
     return hipGetLastError();
 }
-
-void orient_add_rounds(int64_t n) { g_rounds += n; }
-int64_t orient_rounds_total() { return g_rounds.load(); }
 
 }  // namespace r3g

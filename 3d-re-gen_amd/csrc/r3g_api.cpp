@@ -271,7 +271,7 @@ int r3g_create(int device, r3g_ctx** out) {
     if (!c) return fail(R3G_ERR_HIP, "out of host memory");
     c->device = device;
     c->num_cu = prop.multiProcessorCount;
-    gemm_set_auto_rule(-1, c->num_cu);
+    (void)option_store("gemm_num_cu", c->num_cu);      // (ignored unless positive)
     if (const int rc = c->h_small.grow(64, nullptr, "read-back buffer")) {
         delete c;
         return rc;
@@ -419,7 +419,7 @@ int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, fl
     GridCsrSmall sm;
     int rc = grid_small(c, c->meshdist.ws.p, c->meshdist.lay, "meshdist", s, &sm);
     if (rc) return rc;
-    meshdist_add_tests((int64_t)sm.tests);
+    counter_add(LC_MESHDIST_TESTS, (int64_t)sm.tests);
     return R3G_OK;
 }
 
@@ -481,7 +481,7 @@ int r3g_cloud_knn(r3g_ctx* ctx, const float* d_queries, int64_t n_queries, int k
     GridCsrSmall sm;
     int rc = grid_small(c, c->cloud.ws.p, c->cloud.lay, "cloud", s, &sm);
     if (rc) return rc;
-    cloud_add_tests((int64_t)sm.tests);
+    counter_add(LC_CLOUD_TESTS, (int64_t)sm.tests);
     return R3G_OK;
 }
 
@@ -522,7 +522,7 @@ int r3g_cloud_orient(r3g_ctx* ctx, const float* d_points, const float* d_normals
     }
     if ((e = orient_finish(ws, lay, d_normals, n_points, k, d_sign, d_tree, s)) != hipSuccess) return hip_fail(e, "orient_finish");
     if ((rc = small(&sm))) return rc;
-    orient_add_rounds(rounds);
+    counter_add(LC_ORIENT_ROUNDS, rounds);
     if (report) {
         const int64_t r[r3g_or::kReport] = {(int64_t)sm.usable, (int64_t)sm.trees, (int64_t)sm.flipped, rounds, (int64_t)sm.frustrated, 0, 0, 0};
         memcpy(report, r, sizeof r);
@@ -577,7 +577,7 @@ int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, doub
     if ((rc = grid_small(c, st->ws.p, lay, "dbscan", s, &sm))) return rc;
     const int64_t usable = n_points - (int64_t)sm.skipped;
     if (usable <= 0) {              // nothing to cluster: every label is -1 already
-        dbscan_add_launches(launches);
+        counter_add(LC_DBSCAN_LAUNCHES, launches);
         return done();
     }
     float lo[3], hi[3];
@@ -598,8 +598,8 @@ int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, doub
     st->grid = g;
     st->built = true;
     c->dbscan_timed = true;
-    dbscan_add_launches(launches);
-    dbscan_add_tests((int64_t)ds.tests);
+    counter_add(LC_DBSCAN_LAUNCHES, launches);
+    counter_add(LC_DBSCAN_TESTS, (int64_t)ds.tests);
     rep[0] = usable, rep[1] = (int64_t)ds.n_core, rep[2] = (int64_t)ds.n_border, rep[3] = usable - rep[1] - rep[2];
     rep[4] = (int64_t)ds.n_clusters, rep[5] = r3g_db::best_label(ds.best), rep[6] = r3g_db::best_size(ds.best), rep[7] = g.res;
     return done();
@@ -675,7 +675,7 @@ int r3g_recon_solve(r3g_ctx* ctx, int cycles, float* d_b_out, float* d_chi_out, 
     e = hipStreamSynchronize(s);      // a fault would surface here, before the state counts as solved
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(recon_solve)");
     st->solved = true;
-    recon_add_counters(1, cycles);
+    counter_add(LC_RECON_SOLVES), counter_add(LC_RECON_CYCLES, cycles);
     return R3G_OK;
 }
 
@@ -724,8 +724,8 @@ static int meshfit_accumulate(Ctx* c, const float* d_points, int64_t n, const fl
                                 d_points, n, d_weights, x, mode, md2, s);
     if (e != hipSuccess) return hip_fail(e, "meshfit_step");
     if ((rc = read_back(c->h_fit, c->meshfit_ws.p, out, sizeof(MeshfitRecord), "meshfit", s))) return rc;
-    meshfit_add_steps(1);
-    meshdist_add_tests((int64_t)out->tests);
+    counter_add(LC_MESHFIT_STEPS);
+    counter_add(LC_MESHDIST_TESTS, (int64_t)out->tests);
     return R3G_OK;
 }
 
@@ -833,7 +833,7 @@ int r3g_meshinside_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, 
     GridCsrSmall sm;
     int rc = grid_small(c, c->meshinside.ws.p, c->meshinside.lay, "meshinside", s, &sm);
     if (rc) return rc;
-    meshinside_add_tests((int64_t)sm.tests);
+    counter_add(LC_MESHINSIDE_TESTS, (int64_t)sm.tests);
     return R3G_OK;
 }
 
@@ -862,7 +862,7 @@ static int meshtopo_build(Ctx* c, const char* who, const float* d_verts, int64_t
     int rounds = 0;
     for (;;) {
         if (rounds == r3g_mt::kMaxRounds) {
-            meshtopo_add_counters(0, rounds);
+            counter_add(LC_MESHTOPO_ROUNDS, rounds);
             return fail(R3G_ERR_INVALID, "%s: the body labels still move after %d rounds; no labelling is returned", who, rounds);
         }
         e = meshtopo_round(c->meshtopo_ws.p, lay, n_faces, s);
@@ -874,7 +874,7 @@ static int meshtopo_build(Ctx* c, const char* who, const float* d_verts, int64_t
     e = meshtopo_finish(c->meshtopo_ws.p, lay, d_verts, d_faces, n_faces, s);
     if (e != hipSuccess) return hip_fail(e, "meshtopo_finish");
     if ((rc = meshtopo_small(c, s, &sm))) return rc;      // (also: the caller may free its buffers, a fault would surface here)
-    meshtopo_add_counters(1, rounds);
+    counter_add(LC_MESHTOPO_BUILDS), counter_add(LC_MESHTOPO_ROUNDS, rounds);
     int64_t* r = c->meshtopo_report;
     r[0] = (int64_t)sm.usable, r[1] = (int64_t)sm.skipped, r[2] = (int64_t)sm.vref, r[3] = (int64_t)sm.edges;
     r[4] = (int64_t)sm.boundary, r[5] = (int64_t)sm.clash, r[6] = (int64_t)sm.nonmanifold;
@@ -992,7 +992,7 @@ int r3g_meshfill_plan(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const
         if (e != hipSuccess) return hip_fail(e, "meshfill_plan");
         if ((rc = read_back(c->h_small, c->meshfill_ws.p + lay.off_small, &sm, sizeof sm, "meshfill", s))) return rc;
     }
-    meshfill_add_counters(1, 2 * (int64_t)rounds);
+    counter_add(LC_MESHFILL_PLANS), counter_add(LC_MESHFILL_ROUNDS, 2 * (int64_t)rounds);
     const int64_t verts_added = mode == r3g_mf::kModeCentroid ? (int64_t)sm.filled : 0;
     if (n_verts + verts_added >= (1ll << 31))
         return fail(R3G_ERR_INVALID, "r3g_meshfill_plan: the added vertices do not fit an int32 index");

@@ -45,9 +45,5 @@ hipError_t recon_solve(ReconState* st, int cycles, hipStream_t s);
 hipError_t recon_sample(ReconState* st, int field, const float* points, const float* normals, int64_t n, float* values_out,
                         hipStream_t s);
 
-void recon_add_counters(int64_t solves, int64_t cycles);        // r3g_get_counter("recon_solves" / "recon_cycles")
-int64_t recon_solves_total();
-int64_t recon_cycles_total();
-
 }  // namespace r3g
 #endif

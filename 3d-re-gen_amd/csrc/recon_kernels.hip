@@ -6,8 +6,6 @@
 // writes x once; the six neighbours come from cache), so nothing is fused through LDS.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define R3G_RC_HD static __host__ __device__ __forceinline__
@@ -123,8 +121,6 @@ __global__ __launch_bounds__(kT) void rc_sample(Load load, const float* __restri
     if ((threadIdx.x & 63) == 0 && used) atomicAdd(&sm->usable, used), atomicAdd(&sm->sum, sum);
 }
 
-std::atomic<int64_t> g_solves{0}, g_cycles{0};
-
 }  // namespace
 
 hipError_t recon_splat(ReconState* st, const float* points, const float* normals, int64_t n, hipStream_t s) {
@@ -179,9 +175,5 @@ hipError_t recon_sample(ReconState* st, int field, const float* points, const fl
                            values_out, sm);
     return hipGetLastError();
 }
-
-void recon_add_counters(int64_t solves, int64_t cycles) { g_solves += solves, g_cycles += cycles; }
-int64_t recon_solves_total() { return g_solves.load(); }
-int64_t recon_cycles_total() { return g_cycles.load(); }
 
 }  // namespace r3g

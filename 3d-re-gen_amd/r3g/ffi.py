@@ -131,6 +131,8 @@ SYMBOLS = {
     "r3g_set_option": (_I, [ctypes.c_char_p, _I]),
     "r3g_get_option": (_I, [ctypes.c_char_p, _P]),
     "r3g_get_counter": (_I, [ctypes.c_char_p, _P]),
+    "r3g_option_name": (ctypes.c_char_p, [_I]),
+    "r3g_counter_name": (ctypes.c_char_p, [_I]),
     "r3g_prof_enable": (_I, [_I]),
     "r3g_prof_read": (_I, [_P, _P, _P, _I]),
     "r3g_prof_read_bytes": (_I, [_P, _I]),

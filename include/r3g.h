@@ -974,6 +974,8 @@ int r3g_set_option(const char* name, int value);
  * while both the GEMM and the attention kernels stage through LDS-DMA.  A value that r3g_set_option clamped or refused reads back as
  * what is in force.  Host state only (no GPU needed).  Unknown name: R3G_ERR_INVALID. */
 int r3g_get_option(const char* name, int* value);
+/* The names r3g_set_option accepts, one per index from 0 on, in no particular order; NULL for an index below 0 or past the last name. */
+const char* r3g_option_name(int index);
 /* Process-wide event counters (round 6).  "dit_f16_fallbacks": launch groups of r3g_flow_sample_batch whose fp16 residual stream
  * produced non-finite latents and that therefore ran a second time on the fp32 stream ("dit_f16_guard"; such a group costs twice its
  * time -- bench.py and the stage report carry the count so that a slow run says why).  "dit_groups": launch groups run so far.
@@ -1016,6 +1018,8 @@ int r3g_get_option(const char* name, int* value);
  * r3g_flow_sample_batch is SYNCHRONOUS while the guard is on (one 4-byte read-back per group) and must not be captured into a
  * hipGraph then; with "dit_f16_guard" 0 or "dit_resid_f16" 0 it only enqueues work.  Unknown name: R3G_ERR_INVALID. */
 int r3g_get_counter(const char* name, int64_t* value);
+/* The names r3g_get_counter accepts ("device_bytes_live" included), enumerated like r3g_option_name: NULL outside [0, count). */
+const char* r3g_counter_name(int index);
 /* operand staging of the MFMA kernels: 1 = LDS-DMA (global_load_lds, default), 0 = through registers */
 int r3g_set_staging(int use_lds_dma);
 

@@ -15,14 +15,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def option_names_in_source():
-    """the names r3g_set_option accepts, read off csrc/model.cpp as tests/test_abi.py does: its strcmp chain plus kv_set_option's"""
-    src = open(os.path.join(ROOT, "3d-re-gen_amd", "csrc", "model.cpp")).read()
-    body = src[src.index("int r3g_set_option("):]
-    body = body[:body.index("\n}\n")]
-    names = re.findall(r'strcmp\(name, "([a-z0-9_]+)"\)', body)
-    kv = src[src.index("static int kv_set_option("):]
-    kv = kv[:kv.index("\n}\n")]
-    names += ["geo_kv_" + n for n in re.findall(r'n == "([a-z0-9_]+)"', kv)]
+    """the names r3g_set_option accepts, as the library enumerates them (r3g_option_name), like tests/test_abi.py does"""
+    from r3g import ffi
+    L, names = ffi.lib(), []
+    while L.r3g_option_name(len(names)) is not None:
+        names.append(L.r3g_option_name(len(names)).decode())
     assert len(names) == len(set(names)) and len(names) >= 50
     return names
 
@@ -123,6 +120,12 @@ def test_kernel_choice_counters_exist_and_start_readable(lib):
     assert len(names) >= 20
     for n in names:
         assert T.get_counter(L, ffi, n) >= 0
+        assert '"%s"' % n in doc, "counter without documentation in include/r3g.h: " + n
+    listed = []
+    while L.r3g_counter_name(len(listed)) is not None:
+        listed.append(L.r3g_counter_name(len(listed)).decode())
+    assert set(names) <= set(listed)
+    for n in listed:                                            # every counter the library enumerates, not only the table's
         assert '"%s"' % n in doc, "counter without documentation in include/r3g.h: " + n
     v = ctypes.c_int64(0)
     assert L.r3g_get_counter(b"no_such_counter", ctypes.byref(v)) == -1
