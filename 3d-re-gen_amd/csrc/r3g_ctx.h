@@ -75,6 +75,10 @@ struct Ctx {
     int64_t hier_count = 0;
     bool hier_selected = false;
 
+    // 3 x 3 convolutions: 256 bytes of zeros, where conv_gemm_kernel points the taps that lie outside the image.  Made on first use
+    // (r3g_unet_create, r3g_op_conv3x3), never written afterwards
+    DevBuf conv_zero;
+
     void* model = nullptr;  // r3g::Model (model.cpp)
     void release_model();
     void* unet = nullptr;   // r3g::Unet (unet.cpp)

@@ -51,7 +51,7 @@ struct Unet {
     uint16_t *ctxK = nullptr, *ctxVt = nullptr;
     float *vec = nullptr;                  // [4][max_channels] small vectors
     double* gn_partial = nullptr;
-    const uint16_t* zeros = nullptr;       // 256 bytes of zeros (the implicit convolution's taps outside the image)
+    const uint16_t* zeros = nullptr;       // the context's 256 bytes of zeros (Ctx::conv_zero: the implicit convolution's taps outside the image)
     float* splitws = nullptr;              // split-K workspace of the 3 x 3 convolutions (kSplitWsElems floats, GemmArgs::split_ws)
     // whole-model forward (r3g_unet_forward): the concatenated input of an up-block resnet, two hidden-state buffers, the
     // time embedding, and the stack of skip connections (allocated on first use for the resolution at hand)
@@ -138,29 +138,69 @@ static int u_check_shape(const Unet& u, int H, int W, int C, const char* what, i
     return R3G_OK;
 }
 
-// conv 3x3 (pad 1) of bf16 rows src [H*W][Cin] -> epilogue(dst [Ho*Wo][Cout])
-// pad 1: zero padding 1 all round; pad 0: F.pad(x, (0, 1, 0, 1)) (the VAE encoder's stride-2 Downsample2D)
-// nb samples stacked as rows: the im2col runs per sample (a 3x3 window must not reach into the neighbour), the GEMM over all
-static int u_conv3x3(Unet& u, const uint16_t* src, int H, int W, int Cin, int stride, const ULin& l, const float* bias, void* dst,
-                     int epi, hipStream_t s, int pad = 1, int nb = 1) {
-    const int Ho = (H + pad - 2) / stride + 1, Wo = (W + pad - 2) / stride + 1;
-    const int M = nb * Ho * Wo;
+// One 3 x 3 convolution of bf16 rows x [nb][H*W][Cin] with weights w [N][ky][kx][Cin] (row stride ldw = K) -> epilogue(C [M][ldc]):
+// the dispatch of the texture models' convolutions, shared by u_conv3x3 (the UNet's own buffers) and r3g_op_conv3x3 (the caller's).
+// pad 1: zero padding 1 all round; pad 0: F.pad(x, (0, 1, 0, 1)) (the VAE encoder's stride-2 Downsample2D).
+// nb samples stacked as rows: a 3 x 3 window must not reach into the neighbour, the GEMM runs over all of them.
+struct Conv3x3 {
+    const uint16_t* x = nullptr;
+    int nb = 1, H = 0, W = 0, Cin = 0, stride = 1, pad = 1;
+    const uint16_t* w = nullptr;
+    int N = 0, K = 0;                      // K = 9 Cin, and the row stride of w
+    const float* bias = nullptr;
+    void* C = nullptr;
+    int64_t ldc = 0;
+    int epi = EPI_F32;
+    uint16_t* col = nullptr;               // im2col matrix [M][9 Cin] for the launches that need it (col_elems elements)
+    int64_t col_elems = 0;
+    float* ws = nullptr;                   // split-K workspace (ws_elems floats); null or too small: no split
+    int64_t ws_elems = 0;
+    const uint16_t* zero = nullptr;        // 256 bytes of zeros: the implicit convolution's taps outside the image
+};
+
+// *implicit (may be null): conv_gemm_kernel ran; *slices (may be null): the K slices the launch really used (1: no split)
+static int conv3x3_run(const Conv3x3& a, hipStream_t s, int* implicit = nullptr, int* slices = nullptr) {
+    // a window that lies in the padding alone (H = 1 under pad 0) is what PyTorch refuses: "kernel size can't be greater than actual input size"
+    if (a.nb < 1 || a.H < 1 || a.W < 1 || (a.stride != 1 && a.stride != 2) || (a.pad != 0 && a.pad != 1) || a.H + a.pad < 2 || a.W + a.pad < 2)
+        return fail(R3G_ERR_INVALID, "conv3x3: %d x %d x %d, stride %d, pad %d is not a 3 x 3 convolution this library runs (stride 1 | 2, pad 0 | 1, H + pad >= 2, W + pad >= 2)",
+                    a.nb, a.H, a.W, a.stride, a.pad);
+    const int Ho = (a.H + a.pad - 2) / a.stride + 1, Wo = (a.W + a.pad - 2) / a.stride + 1;
+    const int M = a.nb * Ho * Wo;
     // round 5: implicit GEMM -- the 128 x 128 kernel gathers the nine shifted rows itself (conv_gemm_kernel); the im2col matrix is
     // written only for the problems the tile rule gives to the 256 x 256 kernels (N % 256 == 0 on a grid that fills the chip)
-    if (gemm_conv_implicit() && (epi == EPI_F32 || epi == EPI_RESID_F32) && Cin % 64 == 0 && l.K == 9 * Cin && !gemm_auto_takes_256(M, l.N, l.K)) {
-        GemmArgs p{};
-        p.W = l.w; p.ldw = l.K; p.bias = bias; p.C = dst; p.ldc = l.N;
-        p.M = M; p.N = l.N; p.K = l.K; p.epi = epi;
-        p.split_ws = u.splitws; p.split_ws_elems = kSplitWsElems;
-        p.conv.x = src; p.conv.zero = u.zeros; p.conv.H = H; p.conv.W = W; p.conv.Cin = Cin; p.conv.stride = stride; p.conv.pad = pad;
-        p.conv.Ho = Ho; p.conv.Wo = Wo;
-        hipError_t e = gemm_launch(p, 1, s);
-        if (e != hipSuccess) return hip_fail(e, "gemm_launch(unet implicit convolution)");
-        return R3G_OK;
-    }
-    U_TRY(im2col3x3_launch(src, H, W, Cin, stride, pad, u.col, s, nb));       // every sample of the call in one launch
+    const bool imp = gemm_conv_implicit() && (a.epi == EPI_F32 || a.epi == EPI_RESID_F32) && a.Cin % 64 == 0 && a.K == 9 * a.Cin &&
+                     !gemm_auto_takes_256(M, a.N, a.K);
+    if (!imp && (!a.col || (int64_t)M * 9 * a.Cin > a.col_elems))
+        return fail(R3G_ERR_INVALID, "conv3x3: this launch needs an im2col matrix of %lld elements", (long long)M * 9 * a.Cin);
+    GemmArgs p{};
+    p.W = a.w; p.ldw = a.K; p.bias = a.bias; p.C = a.C; p.ldc = a.ldc;
+    p.M = M; p.N = a.N; p.K = a.K; p.epi = a.epi;
     // few rows over a deep K (the coarse levels): slices of K side by side, summed in a fixed order (gemm.hip: split-K of the 128x128 kernel)
-    return u_gemm(u.col, 9 * (int64_t)Cin, l, bias, dst, l.N, M, epi, s, u.splitws);
+    p.split_ws = a.ws; p.split_ws_elems = a.ws ? a.ws_elems : 0;
+    if (imp) {
+        p.conv.x = a.x; p.conv.zero = a.zero; p.conv.H = a.H; p.conv.W = a.W; p.conv.Cin = a.Cin; p.conv.stride = a.stride; p.conv.pad = a.pad;
+        p.conv.Ho = Ho; p.conv.Wo = Wo;
+    } else {
+        U_TRY(im2col3x3_launch(a.x, a.H, a.W, a.Cin, a.stride, a.pad, a.col, s, a.nb));       // every sample of the call in one launch
+        p.A = a.col; p.lda = 9 * (int64_t)a.Cin;
+    }
+    hipError_t e = gemm_launch(p, 1, s);
+    if (e != hipSuccess) return hip_fail(e, imp ? "gemm_launch(implicit convolution)" : "gemm_launch(convolution over im2col rows)");
+    if (implicit) *implicit = imp ? 1 : 0;
+    if (slices) *slices = gemm_last_splitk_slices();
+    return R3G_OK;
+}
+
+// conv 3x3 of bf16 rows src [nb][H*W][Cin] -> epilogue(dst [nb*Ho*Wo][Cout]) on the UNet's own im2col matrix and split-K workspace
+static int u_conv3x3(Unet& u, const uint16_t* src, int H, int W, int Cin, int stride, const ULin& l, const float* bias, void* dst,
+                     int epi, hipStream_t s, int pad = 1, int nb = 1) {
+    Conv3x3 a;
+    a.x = src; a.nb = nb; a.H = H; a.W = W; a.Cin = Cin; a.stride = stride; a.pad = pad;
+    a.w = l.w; a.N = l.N; a.K = l.K; a.bias = bias; a.C = dst; a.ldc = l.N; a.epi = epi;
+    a.col = u.col; a.col_elems = (int64_t)u.c.max_hw * 9 * u.c.max_channels;
+    a.ws = u.splitws; a.ws_elems = kSplitWsElems;
+    a.zero = u.zeros;
+    return conv3x3_run(a, s);
 }
 
 // GroupNorm (+ SiLU) per sample of f32 rows [nb][hw][C] -> bf16
@@ -691,12 +731,29 @@ static int vae_encode(Unet& u, const float* img, int H, int W, float* out, hipSt
     return u_gemm(u.xn, 64, qc, qc.b, out, zp, hh * ww, EPI_F32, s);
 }
 
+// the context's page of zeros (Ctx::conv_zero), allocated and cleared once
+static int conv_zero_page(Ctx* ctx, const uint16_t** out) {
+    if (!ctx->conv_zero) {
+        U_RC(ctx->conv_zero.grow(256, nullptr, "convolution zero page"));
+        hipError_t e = hipMemset(ctx->conv_zero.p, 0, 256);
+        if (e == hipSuccess) e = hipDeviceSynchronize();      // whatever stream the first launch is on sees the zeros
+        if (e != hipSuccess) {
+            ctx->conv_zero.release();
+            return hip_fail(e, "hipMemset(convolution zero page)");
+        }
+    }
+    *out = ctx->conv_zero.as<const uint16_t>();
+    return R3G_OK;
+}
+
 static int unet_create(Ctx* ctx, const r3g_unet_config* cfg) {
     ctx->release_unet();
     const r3g_unet_config& c = *cfg;
     if (c.max_hw < 1 || c.max_channels < 64 || c.max_channels % 64 || c.max_channels > 3072 || c.temb_dim < 1 || c.temb_dim % 8 ||
         c.ctx_dim % 64 || c.ctx_tokens < 1 || c.groups < 1 || c.groups > 256)
         return fail(R3G_ERR_INVALID, "r3g_unet_create: bad configuration");
+    const uint16_t* zero_page = nullptr;
+    U_RC(conv_zero_page(ctx, &zero_page));
     Unet* u = new Unet();
     u->c = c;
     const int64_t hw = c.max_hw, hwp = rup(hw, 128) + 128 * kMaxViews, C = c.max_channels, heads = C / 64, ckp = rup(c.ctx_tokens, 64);
@@ -708,7 +765,7 @@ static int unet_create(Ctx* ctx, const r3g_unet_config* cfg) {
                  o_ck = carve(2 * heads * ckp * 64 * 2), o_cv = carve(2 * heads * ckp * 64 * 2),   /* two contexts: the guidance pair */ o_vec = carve(4 * C * 4),
                  o_gn = carve((int64_t)kMaxViews * (256LL * 256 * 2 * 8 + 256 * 2 * 4)), o_cat = carve(hw * C * 4), o_hb0 = carve(hw * C * 4), o_hb1 = carve(hw * C * 4),
                  o_emb = carve((int64_t)(c.temb_dim + 2 * C) * 4), o_vecn = carve((int64_t)kMaxViews * C * 4),
-                 o_embn = carve((int64_t)kMaxViews * c.temb_dim * 4), o_gate = carve(2 * C * 4), o_split = carve(kSplitWsElems * 4), o_zero = carve(256);
+                 o_embn = carve((int64_t)kMaxViews * c.temb_dim * 4), o_gate = carve(2 * C * 4), o_split = carve(kSplitWsElems * 4);
     if (const int rc = u->arena.grow(off, nullptr, "unet arena")) { delete u; return rc; }
     const hipError_t e = hipMemset(u->arena.p, 0, off);      // padded rows must start finite
     if (e != hipSuccess) { delete u; return hip_fail(e, "hipMemset(unet arena)"); }
@@ -720,7 +777,7 @@ static int unet_create(Ctx* ctx, const r3g_unet_config* cfg) {
     u->catbuf = (float*)(a + o_cat); u->hb[0] = (float*)(a + o_hb0); u->hb[1] = (float*)(a + o_hb1); u->emb = (float*)(a + o_emb);
     u->vecn = (float*)(a + o_vecn); u->embn = (float*)(a + o_embn); u->gate = (float*)(a + o_gate);
     u->splitws = (float*)(a + o_split);
-    u->zeros = (const uint16_t*)(a + o_zero);      // the arena is zero-filled above and nothing writes here
+    u->zeros = zero_page;
     ctx->unet = u;
     return R3G_OK;
 }
@@ -880,6 +937,42 @@ int r3g_aekl_encode(r3g_ctx* ctx, const float* d_image, int height, int width, f
     NEED_UNET("r3g_aekl_encode");
     if (!d_image || !d_moments) return fail(R3G_ERR_INVALID, "r3g_aekl_encode: null argument");
     return vae_encode(*u, d_image, height, width, d_moments, (hipStream_t)stream);
+}
+
+// ---- single-kernel entry points of the texture stage (tests/test_conv_edges_gpu.py).  The contract of include/r3g.h is checked here:
+// the model's own launches meet it by construction.
+int r3g_op_conv3x3(r3g_ctx* ctx, const uint16_t* d_x, int nb, int height, int width, int cin, int stride, int pad, const uint16_t* d_w,
+                   int cout, const float* d_bias, float* d_c, int64_t ldc, int epilogue, uint16_t* d_col, int64_t col_elems, float* d_ws,
+                   int64_t ws_elems, int* implicit, int* slices, void* stream) {
+    auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+    const char* bad = nullptr;
+    if (!ctx || !d_x || !d_w || !d_c) bad = "ctx, d_x, d_w and d_c non-null";
+    else if (epilogue != EPI_F32 && epilogue != EPI_RESID_F32) bad = "an fp32 epilogue (3 or 4)";
+    else if (nb < 1 || height < 1 || width < 1 || (int64_t)nb * height * width > INT32_MAX / 16) bad = "nb, height, width >= 1 and nb * height * width < 2^27";
+    else if ((stride != 1 && stride != 2) || (pad != 0 && pad != 1)) bad = "stride 1 | 2 and pad 0 | 1";
+    else if (height + pad < 2 || width + pad < 2) bad = "height + pad >= 2 and width + pad >= 2 (a window must hold one pixel of the image)";
+    else if (cin < 64 || cin % 64 || cin > INT32_MAX / 9) bad = "cin % 64 == 0, cin >= 64";
+    else if (cout < 4 || cout % 4) bad = "cout % 4 == 0, cout >= 4";
+    else if ((ldc & 3) || ldc < cout) bad = "ldc % 4 == 0 and ldc >= cout";
+    else if (misaligned(d_x) || misaligned(d_w) || misaligned(d_c) || misaligned(d_bias)) bad = "d_x, d_w, d_c and d_bias 16-byte aligned";
+    else if (misaligned(d_col) || misaligned(d_ws) || col_elems < 0 || ws_elems < 0) bad = "d_col and d_ws 16-byte aligned, their sizes not negative";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_conv3x3: needs %s", bad);
+    Conv3x3 a;
+    a.x = d_x; a.nb = nb; a.H = height; a.W = width; a.Cin = cin; a.stride = stride; a.pad = pad;
+    a.w = d_w; a.N = cout; a.K = 9 * cin; a.bias = d_bias; a.C = d_c; a.ldc = ldc; a.epi = epilogue;
+    a.col = d_col; a.col_elems = d_col ? col_elems : 0;
+    a.ws = d_ws; a.ws_elems = d_ws ? ws_elems : 0;
+    U_RC(conv_zero_page(reinterpret_cast<Ctx*>(ctx), &a.zero));
+    return conv3x3_run(a, (hipStream_t)stream, implicit, slices);
+}
+
+int r3g_op_upsample2x(const float* d_x, int height, int width, int channels, uint16_t* d_y, void* stream) {
+    if (!d_x || !d_y || height < 1 || width < 1 || channels < 4 || channels % 4 || (reinterpret_cast<uintptr_t>(d_x) & 15) ||
+        (reinterpret_cast<uintptr_t>(d_y) & 7))
+        return fail(R3G_ERR_INVALID, "r3g_op_upsample2x: needs non-null d_x (16-byte aligned) and d_y (8-byte aligned), height, width >= 1, channels %% 4 == 0");
+    hipError_t e = upsample2x_launch(d_x, height, width, channels, d_y, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_upsample2x");
+    return R3G_OK;
 }
 
 int r3g_sched_model_input(const float* d_latent, int channels, const float* d_cond, int cond_channels, int64_t pixels, float sigma,

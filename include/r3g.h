@@ -773,6 +773,30 @@ int r3g_op_gemm(const uint16_t* d_a, int64_t lda, const uint16_t* d_w, int64_t l
 int r3g_op_gemm_splitk(const uint16_t* d_a, int64_t lda, const uint16_t* d_w, int64_t ldw, const float* d_bias, float* d_c, int64_t ldc,
                        const float* d_gate, int m, int n, int k, int epilogue, float* d_ws, int64_t ws_elems, int* slices,
                        void* stream);
+/* One 3 x 3 convolution of the texture models through the dispatch their own blocks use (csrc/unet.cpp: conv3x3_run), on caller-owned
+ * operands (tests/test_conv_edges_gpu.py).  d_x bf16 [nb][height*width][cin] (samples stacked as rows, a pixel's channels contiguous),
+ * d_w bf16 [cout][ky][kx][cin] (row stride 9 cin), d_bias f32 [cout] or null -> d_c f32 [nb*Ho*Wo][ldc], Ho = (height + pad - 2) / stride
+ * + 1, Wo likewise; epilogue 4: c = conv + bias, 3: c += conv + bias.  stride 1 | 2; pad 1: zero padding all round, pad 0: one row below
+ * and one column to the right only, F.pad(x, (0, 1, 0, 1)).  A window never reads the neighbouring sample.
+ * The launch is conv_gemm_kernel (the 128 x 128 kernel gathers its A operand itself, taps outside the image from a page of zeros the
+ * context owns) while "conv_implicit" is on, LDS-DMA staging and the automatic tile rule are in force and that rule does not give the
+ * problem to the 256 x 256 kernels; otherwise im2col3x3_kernel writes d_col [nb*Ho*Wo][9 cin] (col_elems elements, caller-owned) and the
+ * ordinary GEMM runs on it -- same bits.  Either form splits k as r3g_op_gemm_splitk states when d_ws (ws_elems floats, caller-owned)
+ * holds S * nb*Ho*Wo * cout floats; d_ws null or too small: one launch walks all of k.  *implicit (may be null) = 1 when
+ * conv_gemm_kernel ran, *slices (may be null) = the slices the launch really used.
+ * Contract, checked; a violation is R3G_ERR_INVALID with nothing launched or written: ctx, d_x, d_w, d_c non-null; nb, height, width
+ * >= 1 (nb * height * width < 2^27); height + pad >= 2 and width + pad >= 2 (a window that lies in the padding alone is what PyTorch
+ * refuses too); cin % 64 == 0; cout % 4 == 0; ldc % 4 == 0, ldc >= cout; d_x, d_w, d_c, d_bias, d_col and d_ws 16-byte aligned;
+ * epilogue 3 or 4; a launch that needs the im2col matrix while d_col is null or col_elems < nb*Ho*Wo * 9 cin.  Nothing outside
+ * [nb*Ho*Wo) x [cout) of d_c, past nb*Ho*Wo * 9 cin elements of d_col or past S * nb*Ho*Wo * cout floats of d_ws is written; nothing
+ * in front of d_x, past its nb * height * width rows or past row cout of d_w is read. */
+int r3g_op_conv3x3(r3g_ctx* ctx, const uint16_t* d_x, int nb, int height, int width, int cin, int stride, int pad, const uint16_t* d_w,
+                   int cout, const float* d_bias, float* d_c, int64_t ldc, int epilogue, uint16_t* d_col, int64_t col_elems, float* d_ws,
+                   int64_t ws_elems, int* implicit, int* slices, void* stream);
+/* Nearest-neighbour 2 x upsampling in front of Upsample2D's convolution (upsample2x_kernel): d_x f32 [height][width][channels] -> d_y
+ * bf16 [2 height][2 width][channels], y[oy][ox] = bf16(x[oy / 2][ox / 2]) rounded to nearest even.  channels % 4 == 0, height, width
+ * >= 1, d_x 16-byte and d_y 8-byte aligned, both non-null; a violation is R3G_ERR_INVALID with nothing written. */
+int r3g_op_upsample2x(const float* d_x, int height, int width, int channels, uint16_t* d_y, void* stream);
 /* softmax(Q K^T / 8) V for head_dim 64: Q bf16 [B][H][lq_pad][64] (plain q: this entry point folds the softmax scale
  * in itself), K bf16 [B][H][lk_pad][64], Vt bf16 [B][H][64][lk_pad] -> O bf16 [B][lq][H*64].
  * Vt holds V transposed with the keys of each row in the kernel's operand order: inside every aligned group of 16 keys
