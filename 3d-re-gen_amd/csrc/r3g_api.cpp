@@ -286,6 +286,8 @@ void r3g_destroy(r3g_ctx* ctx) {
     (void)hipSetDevice(c->device);      // before anything is freed: the buffers below belong to this device
     if (c->dbscan_ev_made)
         for (hipEvent_t e : c->dbscan_ev) (void)hipEventDestroy(e);
+    if (c->plane_ev_made)
+        for (hipEvent_t e : c->plane_ev) (void)hipEventDestroy(e);
     c->release_model();
     c->release_unet();
     delete c;                           // every buffer of the context goes with its DevBuf member
@@ -613,6 +615,108 @@ int r3g_cloud_dbscan_times(r3g_ctx* ctx, double* ms) {
         float t = 0.0f;
         hipError_t e = hipEventElapsedTime(&t, c->dbscan_ev[p], c->dbscan_ev[p + 1]);
         if (e != hipSuccess) return hip_fail(e, "hipEventElapsedTime(dbscan)");
+        ms[p] = (double)t;
+    }
+    return R3G_OK;
+}
+
+// ---- plane fit: batched RANSAC and the moments of a masked set -----------------------------------------
+static int plane_reserve(Ctx* c, int64_t n_points, int64_t n_hyp, bool own_count, bool own_mask, PlaneLayout* lay, hipStream_t s) {
+    if (const int rc = c->h_plane.grow(sizeof(PlaneSmall), s, "plane read-back buffer")) return rc;
+    return c->plane_ws.grow(plane_workspace_bytes(n_points, n_hyp, own_count, own_mask, lay), s, "plane workspace");
+}
+
+// out[0..5]: centroid and the "up" normal; val: the eigenvalues ascending; *few: fewer than 3 rows in the set
+static void plane_solve(const r3g_pl::Moments& m, double centroid[3], double normal[3], double val[3], int* few) {
+    for (int a = 0; a < 3; ++a) centroid[a] = m.c[a];
+    r3g_pl::plane_of(m, val, normal, few);
+}
+
+int r3g_plane_ransac(r3g_ctx* ctx, const float* d_points, int64_t n_points, const int32_t* d_triples, int n_hyp, double threshold,
+                     uint32_t* d_count, uint8_t* d_mask, int64_t* report, double* plane, void* stream) {
+    if (!(threshold > 0.0) || !(threshold - threshold == 0.0)) return fail(R3G_ERR_INVALID, "r3g_plane_ransac: threshold must be finite and > 0");
+    if (n_hyp < 0 || n_hyp > r3g_pl::kMaxHyp) return fail(R3G_ERR_INVALID, "r3g_plane_ransac: n_hyp outside [0, %d]", r3g_pl::kMaxHyp);
+    if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_plane_ransac: n_points outside [0, 2^31 - 1]");
+    if (!report || !plane || (n_points && !d_points) || (n_hyp && !d_triples)) return fail(R3G_ERR_INVALID, "r3g_plane_ransac: null buffer");
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_plane_ransac: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    c->plane_timed = false;
+    if (!c->plane_ev_made) {
+        for (int i = 0; i <= r3g_pl::kPasses; ++i) {
+            hipError_t he = hipEventCreate(&c->plane_ev[i]);
+            if (he != hipSuccess) {      // all or none: the next call starts over, and nothing made here is left behind
+                while (i-- > 0) (void)hipEventDestroy(c->plane_ev[i]);
+                return hip_fail(he, "hipEventCreate(plane)");
+            }
+        }
+        c->plane_ev_made = true;
+    }
+    PlaneLayout lay;
+    if (const int rc = plane_reserve(c, n_points, n_hyp, !d_count, !d_mask, &lay, s)) return rc;
+    char* ws = c->plane_ws.p;
+    uint32_t* count = d_count ? d_count : (uint32_t*)(ws + lay.off_count);
+    uint8_t* mask = d_mask ? d_mask : (uint8_t*)(ws + lay.off_mask);
+    auto mark = [&](int i) { return hipEventRecord(c->plane_ev[i], s); };
+    hipError_t e;
+    if ((e = mark(0)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((e = plane_table(ws, lay, d_points, n_points, d_triples, n_hyp, count, s)) != hipSuccess) return hip_fail(e, "plane_table");
+    if ((e = mark(1)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((e = plane_count(ws, lay, d_points, n_points, n_hyp, threshold, count, c->num_cu, s)) != hipSuccess) return hip_fail(e, "plane_count");
+    if ((e = mark(2)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((e = plane_winner(ws, lay, d_points, n_points, n_hyp, threshold, count, mask, s)) != hipSuccess) return hip_fail(e, "plane_winner");
+    if ((e = mark(3)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((e = plane_moments(ws, lay, d_points, n_points, mask, s)) != hipSuccess) return hip_fail(e, "plane_moments");
+    if ((e = mark(4)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    PlaneSmall sm;      // (its sync: the caller may free its buffers, and a fault would surface here)
+    if (const int rc = read_back(c->h_plane, ws + lay.off_small, &sm, sizeof sm, "plane", s)) return rc;
+    c->plane_timed = true;
+    int few = 0;
+    double centroid[3], normal[3], val[3];
+    plane_solve(sm.mom, centroid, normal, val, &few);
+    const int64_t rep[r3g_pl::kReport] = {(int64_t)sm.usable, (int64_t)sm.valid, r3g_pl::key_h(sm.key), (int64_t)r3g_pl::key_count(sm.key), few, 0, 0, 0};
+    memcpy(report, rep, sizeof rep);
+    for (int a = 0; a < 3; ++a) {
+        plane[a] = sm.best.p0[a], plane[3 + a] = sm.best.n[a];
+        plane[6 + a] = centroid[a], plane[9 + a] = normal[a], plane[12 + a] = val[a];
+    }
+    plane[15] = 0.0;
+    return R3G_OK;
+}
+
+int r3g_plane_moments(r3g_ctx* ctx, const float* d_points, int64_t n_points, const uint8_t* d_mask, double* out, int64_t* report, void* stream) {
+    if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_plane_moments: n_points outside [0, 2^31 - 1]");
+    if (!out || !report || (n_points && !d_points)) return fail(R3G_ERR_INVALID, "r3g_plane_moments: null buffer");
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_plane_moments: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    PlaneLayout lay;
+    if (const int rc = plane_reserve(c, n_points, 0, false, false, &lay, s)) return rc;
+    char* ws = c->plane_ws.p;
+    hipError_t e = hipMemsetAsync(ws + lay.off_small, 0, sizeof(PlaneSmall), s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(plane)");
+    if ((e = plane_moments(ws, lay, d_points, n_points, d_mask, s)) != hipSuccess) return hip_fail(e, "plane_moments");
+    PlaneSmall sm;
+    if (const int rc = read_back(c->h_plane, ws + lay.off_small, &sm, sizeof sm, "plane moments", s)) return rc;
+    int few = 0;
+    double centroid[3], normal[3], val[3];
+    plane_solve(sm.mom, centroid, normal, val, &few);
+    out[0] = (double)sm.mom.n;
+    for (int a = 0; a < 3; ++a) out[1 + a] = centroid[a], out[10 + a] = val[a], out[13 + a] = normal[a];
+    for (int a = 0; a < 6; ++a) out[4 + a] = sm.mom.s[a];
+    const int64_t rep[r3g_pl::kMomReport] = {(int64_t)sm.mom.n, (int64_t)sm.mom.skipped, few, 0};
+    memcpy(report, rep, sizeof rep);
+    return R3G_OK;
+}
+
+int r3g_plane_times(r3g_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return fail(R3G_ERR_INVALID, "r3g_plane_times: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->plane_timed) return fail(R3G_ERR_STATE, "r3g_plane_times: no complete r3g_plane_ransac on this context");
+    for (int p = 0; p < r3g_pl::kPasses; ++p) {
+        float t = 0.0f;
+        hipError_t e = hipEventElapsedTime(&t, c->plane_ev[p], c->plane_ev[p + 1]);
+        if (e != hipSuccess) return hip_fail(e, "hipEventElapsedTime(plane)");
         ms[p] = (double)t;
     }
     return R3G_OK;

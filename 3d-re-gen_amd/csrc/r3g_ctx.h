@@ -18,6 +18,7 @@
 #include "meshinside_kernels.h"
 #include "meshtopo_kernels.h"
 #include "orient_kernels.h"
+#include "plane_kernels.h"
 #include "recon_kernels.h"
 
 namespace r3g {
@@ -52,6 +53,13 @@ struct Ctx {
     hipEvent_t dbscan_ev[kDbscanPasses + 2] = {};
     bool dbscan_ev_made = false;
     bool dbscan_timed = false;
+    // plane fit: the table, counts, mask and partial sums of one r3g_plane_ransac / r3g_plane_moments (nothing is kept between calls
+    // but the buffer); h_plane is the pinned buffer its record is read back through (it does not fit h_small), made on first use;
+    // the events bracket the passes of the last r3g_plane_ransac (plane_timed: a complete run)
+    DevBuf plane_ws, h_plane{true};
+    hipEvent_t plane_ev[r3g_pl::kPasses + 1] = {};
+    bool plane_ev_made = false;
+    bool plane_timed = false;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
     // fit h_small), made on first use

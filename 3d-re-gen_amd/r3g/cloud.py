@@ -397,6 +397,14 @@ class PointCloud:
         return PointCloud(self.vertices[keep], None if self.colors is None else self.colors[keep],
                           None if self.normals is None else self.normals[keep])
 
+    def fit_plane(self, iterations=2000, threshold=0.05, device="cuda", **kw):
+        """r3g.plane.fit_floor of the vertices on the GPU (the reference's floor-plane choice among PCA, RANSAC and total least
+        squares) -> its dict with normal [3], point [1,3] and mask [N] as numpy arrays"""
+        from . import plane
+        p = torch.from_numpy(np.ascontiguousarray(self.vertices, np.float32)).to(device)
+        fit = plane.fit_floor(p, iterations, threshold, **kw)
+        return dict(fit, normal=fit["normal"].cpu().numpy(), point=fit["point"].cpu().numpy(), mask=fit["mask"].cpu().numpy())
+
     def export(self, path=None, file_type="ply"):
         if file_type != "ply" or (path is not None and not str(path).lower().endswith(".ply")):
             raise ValueError("PointCloud.export writes PLY only")

@@ -376,6 +376,41 @@ int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, doub
                      uint32_t* d_count, int64_t* report, void* stream);
 int r3g_cloud_dbscan_times(r3g_ctx* ctx, double* ms);
 
+/* ---- point clouds: plane fit ---------------------------------------------------------------------
+ * The initialisation of the reference's pose matching: fit_plane_ransac_refined as one batch of hypotheses, and the moments
+ * behind fit_plane_svd and the PCA test of extract_and_fit_floor_plane.  A point is usable when its three coordinates are finite.
+ * Hypothesis h is a triple of row indices (i0, i1, i2); with every coordinate widened to float64, one rounding per operation, no
+ * contraction: v1 = p[i1] - p[i0], v2 = p[i2] - p[i0], c = v1 x v2, len = sqrt((cx*cx + cy*cy) + cz*cz).  It is valid when the
+ * three indices lie in [0, n_points), the three points are usable and len >= 1e-6; its unit normal is c / len.  q is an inlier
+ * of h iff |((qx-p0x)*nx + (qy-p0y)*ny) + (qz-p0z)*nz| < threshold in float64; an unusable point is never an inlier.  count[h] =
+ * the inliers of h, 0 for an invalid hypothesis.  The winner is the valid hypothesis with the largest count, the lowest h on a
+ * tie.  The moments of a set of rows are n, sum p, the centroid sum p / n and the scatter sum (p - c)(p - c)^T, float64 sums in
+ * the one fixed order written in csrc/plane_core.h (it depends on n_points alone); the eigenpairs of the scatter come from the
+ * cyclic Jacobi of that header, run on the host.  The normal of a set is the eigenvector of its smallest eigenvalue, turned so
+ * that n_y >= 0; a set of fewer than 3 rows gets (0, 1, 0), zero eigenvalues and a flag.  tests/emu/plane_emu.cpp reproduces
+ * every bit on the host.
+ *
+ * r3g_plane_ransac: d_points float32 [n_points][3], d_triples int32 [n_hyp][3] -> where not NULL, d_count uint32 [n_hyp] and d_mask
+ *   uint8 [n_points] (1 for the winner's inliers, all 0 without a winner).  report (int64 [8]): usable points, valid hypotheses,
+ *   the winner h (-1 without one), its count, 1 when the refinement saw fewer than 3 rows, 0, 0, 0.  plane (double [16], host): the
+ *   winner's p0 [0..2] and unit normal [3..5] (zeros without one), the inliers' centroid [6..8], the refined normal [9..11], the
+ *   eigenvalues of their scatter ascending [12..14], 0.  The number of kernel launches does not depend on the data: the table,
+ *   the count pass (every point is tested against every valid hypothesis; counts by ballot, combined with integer atomics), the
+ *   arg-max, the mask and four for the moments.  threshold not finite or <= 0, n_hyp < 0 or above 65536, n_points < 0 or above
+ *   2^31 - 1, report or plane NULL, d_points NULL with n_points > 0, d_triples NULL with n_hyp > 0: R3G_ERR_INVALID before any
+ *   launch.  n_points == 0, n_hyp == 0 and a table without a valid entry succeed with winner -1.  Synchronises `stream` once.
+ * r3g_plane_moments: the rows of d_points with d_mask[i] != 0 (every row when d_mask is NULL) -> out (double [16], host): n, the
+ *   centroid [1..3], the scatter xx, xy, xz, yy, yz, zz [4..9], the eigenvalues ascending [10..12], the normal [13..15].  report
+ *   (int64 [4]): rows in the set, selected rows left out as unusable, 1 for fewer than 3 rows, 0.  n_points < 0 or above 2^31 - 1,
+ *   out or report NULL, d_points NULL with n_points > 0: R3G_ERR_INVALID before any launch.  Synchronises `stream` once.
+ * r3g_plane_times: milliseconds of the last complete r3g_plane_ransac on this context between HIP events on its stream, ms double
+ *   [4]: table, count pass, winner and mask, moments.  Without such a call: R3G_ERR_STATE. */
+int r3g_plane_ransac(r3g_ctx* ctx, const float* d_points, int64_t n_points, const int32_t* d_triples, int n_hyp, double threshold,
+                     uint32_t* d_count, uint8_t* d_mask, int64_t* report, double* plane, void* stream);
+int r3g_plane_moments(r3g_ctx* ctx, const float* d_points, int64_t n_points, const uint8_t* d_mask, double* out, int64_t* report,
+                      void* stream);
+int r3g_plane_times(r3g_ctx* ctx, double* ms);
+
 /* ---- point clouds: Poisson surface on a uniform lattice -----------------------------------------
  * Oriented points -> an implicit function chi whose level set is the surface (r3g/recon.py runs marching cubes on it).  The
  * lattice has n = 2^depth + 1 nodes per axis over the cube (centre, side), node (i0, i1, i2) stored [i0][i1][i2].  Every value is
