@@ -737,7 +737,9 @@ hipError_t qkv_split_launch(const QkvSplitArgs& p, hipStream_t s) {
 
 hipError_t gemv_launch(const float* x, int B, int K, const uint16_t* W, int64_t ldw, const float* bias, float* y,
                        int N, int act_silu_in, int act_silu_out, hipStream_t s) {
-    if (B > 8 || K % 8 || (size_t)B * K * 4 > 64 * 1024) return hipErrorInvalidValue;
+    if (N <= 0) return hipSuccess;
+    // a lane reads 16 bytes of W at W + n * ldw + k, k % 8 == 0: every row must start on a 16-byte boundary
+    if (B < 1 || B > 8 || K < 0 || K % 8 || (size_t)B * K * 4 > 64 * 1024 || (ldw & 7) || ((uintptr_t)W & 15)) return hipErrorInvalidValue;
     const int blocks = N >= 1024 ? 256 : (N + 3) / 4;
     ProfScope ps(PC_GEMV, 2.0 * (double)N * K, s);
     hipLaunchKernelGGL(gemv_kernel, dim3(blocks), dim3(256), (size_t)B * K * 4, s, x, B, K, W, ldw, bias, y, N,
@@ -747,7 +749,8 @@ hipError_t gemv_launch(const float* x, int B, int K, const uint16_t* W, int64_t 
 
 hipError_t gemv_multi_launch(const float* x, int B, int K, const GemvJob* d_jobs, int njobs, float* y, int silu_in,
                              hipStream_t s) {
-    if (B > 2 || K % 8 || njobs <= 0) return hipErrorInvalidValue;
+    // (the jobs' own W / ldw live on the device: whoever builds the table answers for ldw % 8 == 0 and 16-byte aligned W, as build_mod_jobs does)
+    if (B < 1 || B > 2 || K < 0 || K % 8 || (size_t)B * K * 4 > 64 * 1024 || njobs <= 0 || njobs > 65535) return hipErrorInvalidValue;
     ProfScope ps(PC_GEMV, 0.0, s);
     hipLaunchKernelGGL(gemv_multi_kernel, dim3(64, njobs), dim3(256), (size_t)B * K * 4, s, x, B, K, d_jobs, y, silu_in);
     return hipGetLastError();
@@ -755,6 +758,7 @@ hipError_t gemv_multi_launch(const float* x, int B, int K, const GemvJob* d_jobs
 
 hipError_t timestep_embedding_launch(const float* t, float t_scalar, int B, float time_factor, float* out,
                                      hipStream_t s) {
+    if (B <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(timestep_embedding_kernel, dim3(B), dim3(256), 0, s, t, t_scalar, B, time_factor, out);
     return hipGetLastError();
@@ -762,6 +766,7 @@ hipError_t timestep_embedding_launch(const float* t, float t_scalar, int B, floa
 
 hipError_t cast_pad_launch(const float* in, int64_t ldi, uint16_t* out, int64_t ldo, int rows, int C, int Cpad,
                            float scale, hipStream_t s) {
+    if (rows <= 0 || Cpad <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(cast_pad_kernel, dim3(blocks_for((int64_t)rows * Cpad, 256)), dim3(256), 0, s, in, ldi, out, ldo,
                        rows, C, Cpad, scale);
@@ -769,12 +774,14 @@ hipError_t cast_pad_launch(const float* in, int64_t ldi, uint16_t* out, int64_t 
 }
 
 hipError_t fill_rows_launch(float* dst, int64_t ld, int rows, int C, const float* vals, hipStream_t s) {
+    if (rows <= 0 || C <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(fill_rows_kernel, dim3(blocks_for((int64_t)rows * C, 256)), dim3(256), 0, s, dst, ld, rows, C, vals);
     return hipGetLastError();
 }
 
 hipError_t cfg_euler_launch(float* latents, const float* v2, int64_t n, float guidance, float dsigma, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(cfg_euler_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, latents, v2, n, guidance, dsigma);
     return hipGetLastError();
@@ -800,6 +807,7 @@ hipError_t vec_add_launch(float* y, const float* x, int n, hipStream_t s) {
 }
 
 hipError_t nonfinite_flag_launch(const float* x, int64_t n, int* flag, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     const int blocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
     hipLaunchKernelGGL(nonfinite_flag_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, s, x, n, flag);
@@ -816,7 +824,8 @@ hipError_t swiglu_launch(const uint16_t* in, int64_t ldi, uint16_t* out, int64_t
 
 hipError_t fourier_grid_launch(uint16_t* out, int64_t start, int count, int R, double bound, int num_freqs,
                                int include_pi, hipStream_t s) {
-    if (3 + 6 * num_freqs > 64) return hipErrorInvalidValue;
+    if (num_freqs < 0 || 3 + 6 * num_freqs > 64) return hipErrorInvalidValue;
+    if (count <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(fourier_grid_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, s, out, start, count, R, bound,
                        num_freqs, include_pi);
@@ -825,7 +834,8 @@ hipError_t fourier_grid_launch(uint16_t* out, int64_t start, int count, int R, d
 
 hipError_t fourier_points_launch(uint16_t* out, const int32_t* list, int count, int rows, int R, double bound, int num_freqs,
                                  int include_pi, hipStream_t s) {
-    if (3 + 6 * num_freqs > 64 || count > rows) return hipErrorInvalidValue;
+    if (num_freqs < 0 || 3 + 6 * num_freqs > 64 || count > rows) return hipErrorInvalidValue;
+    if (rows <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, (double)rows * 128 + (double)count * 4, s);
     hipLaunchKernelGGL(fourier_points_kernel, dim3(blocks_for((int64_t)rows * 8, 256)), dim3(256), 0, s, out, list, count, rows, R,
                        bound, num_freqs, include_pi);
@@ -1047,6 +1057,7 @@ hipError_t quant_fp8_rows_launch(const uint16_t* x, int64_t ldx, int rows, int K
 }
 
 hipError_t im2col_launch(const float* img, int S, int ps, uint16_t* out, int Kpad, hipStream_t s) {
+    if (S <= 0 || ps <= 0 || ps > S || Kpad <= 0) return hipSuccess;
     const int P = S / ps;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(im2col_kernel, dim3(blocks_for((int64_t)P * P * Kpad, 256)), dim3(256), 0, s, img, S, ps, out, Kpad);
@@ -1054,12 +1065,14 @@ hipError_t im2col_launch(const float* img, int S, int ps, uint16_t* out, int Kpa
 }
 
 hipError_t add_rows_launch(float* x, int64_t ldx, const float* pos, int64_t ldp, int rows, int C, hipStream_t s) {
+    if (rows <= 0 || C <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(add_rows_kernel, dim3(blocks_for((int64_t)rows * C, 256)), dim3(256), 0, s, x, ldx, pos, ldp, rows, C);
     return hipGetLastError();
 }
 
 hipError_t f32_to_bf16_launch(const float* in, uint16_t* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
     ProfScope prof_scope_(PC_ELEMWISE, 0.0, s);
     hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, in, out, n);
     return hipGetLastError();

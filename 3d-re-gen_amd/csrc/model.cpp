@@ -389,6 +389,9 @@ static int build_mod_jobs(Model& m) {
         int rc = get_lin(m, base, true, &l);
         if (rc) return rc;
         if (l.N != mult * m.H) return fail(R3G_ERR_INVALID, "'%s' has N=%d, expected %d", base.c_str(), l.N, mult * m.H);
+        // gemv_multi_kernel reads 16 bytes of w per lane; the table lives on the device, where gemv_multi_launch cannot look
+        if ((l.ldw & 7) || (reinterpret_cast<uintptr_t>(l.w) & 15))
+            return fail(R3G_ERR_INVALID, "'%s': the modulation GEMV needs ldw %% 8 == 0 and a 16-byte aligned matrix", base.c_str());
         jobs.push_back(GemvJob{l.w, l.b, l.ldw, l.N, off});
         m.mod_off.push_back(off);
         off += 2LL * l.N;  // [B<=2][N]
@@ -1988,6 +1991,163 @@ int r3g_op_swiglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ld
     if (const char* bad = glu_contract(d_in, ldi, d_out, ldo, rows, f)) return fail(R3G_ERR_INVALID, "r3g_op_swiglu: needs %s", bad);
     hipError_t e = swiglu_launch(d_in, ldi, d_out, ldo, rows, f, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "r3g_op_swiglu");
+    return R3G_OK;
+}
+
+// ---- the small kernels of the sampler step and of input staging (GEMV, embeddings, Euler updates, casts and copies), one launch each.
+// The contract of include/r3g.h is checked here, as above; tests/test_vec_kernels_gpu.py drives them.
+static const char* gemv_contract(const float* d_x, int b, int k, int max_b) {
+    if (!d_x) return "x";
+    if (b < 1 || b > max_b) return max_b == 8 ? "1 <= b <= 8" : "1 <= b <= 2";
+    if (k < 8 || k % 8 || (int64_t)b * k * 4 > 65536) return "k % 8 == 0, k >= 8, b * k * 4 <= 65536 (the inputs are held in LDS)";
+    return nullptr;
+}
+
+static const char* gemv_matrix_contract(const void* w, int64_t ldw, int k, int n) {
+    if (!w || n < 1) return "a matrix and n >= 1";
+    if (ldw < k || (ldw & 7) || op_misaligned(w, 15)) return "16 bytes of w per lane: ldw % 8 == 0, ldw >= k, w 16-byte aligned";
+    return nullptr;
+}
+
+int r3g_op_gemv(const float* d_x, int b, int k, const uint16_t* d_w, int64_t ldw, const float* d_bias, float* d_y, int n, int silu_in,
+                int silu_out, void* stream) {
+    const char* bad = gemv_contract(d_x, b, k, 8);
+    if (!bad) bad = gemv_matrix_contract(d_w, ldw, k, n);
+    if (!bad && !d_y) bad = "y";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_gemv: needs %s", bad);
+    hipError_t e = gemv_launch(d_x, b, k, d_w, ldw, d_bias, d_y, n, silu_in, silu_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_gemv");
+    return R3G_OK;
+}
+
+int r3g_op_gemv_multi(const float* d_x, int b, int k, const void* const* w, const void* const* bias, const int64_t* ldw, const int* n,
+                      const int64_t* out_off, int njobs, float* d_y, int silu_in, void* stream) {
+    const char* bad = gemv_contract(d_x, b, k, 2);
+    if (!bad && (!w || !ldw || !n || !out_off || !d_y)) bad = "the host arrays w, ldw, n, out_off and y";
+    if (!bad && (njobs < 1 || njobs > 65535)) bad = "1 <= njobs <= 65535";
+    for (int j = 0; !bad && j < njobs; ++j) {
+        bad = gemv_matrix_contract(w[j], ldw[j], k, n[j]);
+        if (!bad && out_off[j] < 0) bad = "out_off >= 0";
+    }
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_gemv_multi: needs %s", bad);
+    std::vector<GemvJob> jobs;
+    for (int j = 0; j < njobs; ++j)
+        jobs.push_back(GemvJob{static_cast<const uint16_t*>(w[j]), bias ? static_cast<const float*>(bias[j]) : nullptr, ldw[j], n[j], out_off[j]});
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf table;      // the table the model builds once per checkpoint: here per call (a test hook; synchronous)
+    R3G_RC(table.grow(jobs.size() * sizeof(GemvJob), s, "r3g_op_gemv_multi jobs"));
+    R3G_TRY(hipMemcpy(table.p, jobs.data(), jobs.size() * sizeof(GemvJob), hipMemcpyHostToDevice));
+    hipError_t e = gemv_multi_launch(d_x, b, k, table.as<GemvJob>(), njobs, d_y, silu_in, s);
+    const hipError_t e2 = hipStreamSynchronize(s);      // (before the table goes)
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_gemv_multi");
+    if (e2 != hipSuccess) return hip_fail(e2, "r3g_op_gemv_multi");
+    return R3G_OK;
+}
+
+int r3g_op_timestep_embedding(const float* d_t, float t_scalar, int b, float time_factor, float* d_out, void* stream) {
+    if (b < 1 || !d_out) return fail(R3G_ERR_INVALID, "r3g_op_timestep_embedding: needs b >= 1 and out");
+    hipError_t e = timestep_embedding_launch(d_t, t_scalar, b, time_factor, d_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_timestep_embedding");
+    return R3G_OK;
+}
+
+static const char* fourier_contract(const uint16_t* d_out, int r, int num_freqs) {
+    if (!d_out) return "out";
+    if (r < 1) return "r >= 1";
+    if (num_freqs < 0 || 3 + 6 * num_freqs > 64) return "0 <= num_freqs, 3 + 6 num_freqs <= 64";
+    return nullptr;
+}
+
+int r3g_op_fourier_grid(uint16_t* d_out, int64_t start, int count, int r, double bound, int num_freqs, int include_pi, void* stream) {
+    const char* bad = fourier_contract(d_out, r, num_freqs);
+    if (!bad && (start < 0 || count < 1)) bad = "start >= 0, count >= 1";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_fourier_grid: needs %s", bad);
+    hipError_t e = fourier_grid_launch(d_out, start, count, r, bound, num_freqs, include_pi, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_fourier_grid");
+    return R3G_OK;
+}
+
+int r3g_op_fourier_points(uint16_t* d_out, const int32_t* d_list, int count, int rows, int r, double bound, int num_freqs, int include_pi,
+                          void* stream) {
+    const char* bad = fourier_contract(d_out, r, num_freqs);
+    if (!bad && (count < 1 || rows < 1 || count > rows)) bad = "1 <= count <= rows";
+    if (!bad && !d_list) bad = "list";
+    if (!bad && op_misaligned(d_out, 15)) bad = "out 16-byte aligned (eight channels per store)";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_fourier_points: needs %s", bad);
+    hipError_t e = fourier_points_launch(d_out, d_list, count, rows, r, bound, num_freqs, include_pi, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_fourier_points");
+    return R3G_OK;
+}
+
+int r3g_op_cfg_euler(float* d_lat, const float* d_v2, int64_t n, float guidance, float dsigma, void* stream) {
+    if (!d_lat || !d_v2 || n < 1) return fail(R3G_ERR_INVALID, "r3g_op_cfg_euler: needs lat, v2 and n >= 1");
+    hipError_t e = cfg_euler_launch(d_lat, d_v2, n, guidance, dsigma, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_cfg_euler");
+    return R3G_OK;
+}
+
+int r3g_op_euler_step(float* d_lat, const float* d_v, int64_t n, float dsigma, void* stream) {
+    if (!d_lat || !d_v || n < 1) return fail(R3G_ERR_INVALID, "r3g_op_euler_step: needs lat, v and n >= 1");
+    hipError_t e = euler_step_launch(d_lat, d_v, n, dsigma, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_euler_step");
+    return R3G_OK;
+}
+
+int r3g_op_nonfinite_flag(const float* d_x, int64_t n, int* d_flag, void* stream) {
+    if (!d_x || !d_flag || n < 1) return fail(R3G_ERR_INVALID, "r3g_op_nonfinite_flag: needs x, flag and n >= 1");
+    hipError_t e = nonfinite_flag_launch(d_x, n, d_flag, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_nonfinite_flag");
+    return R3G_OK;
+}
+
+int r3g_op_cast_pad(const float* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int c, int cpad, float scale, void* stream) {
+    const char* bad = nullptr;
+    if (!d_in || !d_out) bad = "in and out";
+    else if (rows < 1 || c < 1 || cpad < c) bad = "rows >= 1, 1 <= c <= cpad";
+    else if (ldi < c || ldo < cpad) bad = "ldi >= c, ldo >= cpad";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_cast_pad: needs %s", bad);
+    hipError_t e = cast_pad_launch(d_in, ldi, d_out, ldo, rows, c, cpad, scale, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_cast_pad");
+    return R3G_OK;
+}
+
+int r3g_op_fill_rows(float* d_dst, int64_t ld, int rows, int c, const float* d_vals, void* stream) {
+    if (!d_dst || !d_vals || rows < 1 || c < 1 || ld < c) return fail(R3G_ERR_INVALID, "r3g_op_fill_rows: needs dst, vals, rows >= 1, c >= 1, ld >= c");
+    hipError_t e = fill_rows_launch(d_dst, ld, rows, c, d_vals, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_fill_rows");
+    return R3G_OK;
+}
+
+int r3g_op_add_rows(float* d_x, int64_t ldx, const float* d_pos, int64_t ldp, int rows, int c, void* stream) {
+    if (!d_x || !d_pos || rows < 1 || c < 1 || ldx < c || ldp < c)
+        return fail(R3G_ERR_INVALID, "r3g_op_add_rows: needs x, pos, rows >= 1, c >= 1, ldx >= c, ldp >= c");
+    hipError_t e = add_rows_launch(d_x, ldx, d_pos, ldp, rows, c, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_add_rows");
+    return R3G_OK;
+}
+
+int r3g_op_f32_to_bf16(const float* d_in, uint16_t* d_out, int64_t n, void* stream) {
+    if (!d_in || !d_out || n < 1) return fail(R3G_ERR_INVALID, "r3g_op_f32_to_bf16: needs in, out and n >= 1");
+    hipError_t e = f32_to_bf16_launch(d_in, d_out, n, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_f32_to_bf16");
+    return R3G_OK;
+}
+
+int r3g_op_patch_rows(const float* d_img, int s, int ps, uint16_t* d_out, int kpad, void* stream) {
+    const char* bad = nullptr;
+    if (!d_img || !d_out) bad = "img and out";
+    else if (s < 1 || ps < 1 || ps > 1024 || s % ps) bad = "s >= 1, 1 <= ps <= 1024, s % ps == 0";
+    else if (kpad < 3 * ps * ps) bad = "kpad >= 3 ps^2";
+    if (bad) return fail(R3G_ERR_INVALID, "r3g_op_patch_rows: needs %s", bad);
+    hipError_t e = im2col_launch(d_img, s, ps, d_out, kpad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_patch_rows");
+    return R3G_OK;
+}
+
+int r3g_op_vec_add_inplace(float* d_y, const float* d_x, int n, void* stream) {
+    if (!d_y || !d_x || n < 1) return fail(R3G_ERR_INVALID, "r3g_op_vec_add_inplace: needs y, x and n >= 1");
+    hipError_t e = vec_add_launch(d_y, d_x, n, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_vec_add_inplace");
     return R3G_OK;
 }
 

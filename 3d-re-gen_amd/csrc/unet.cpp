@@ -975,6 +975,14 @@ int r3g_op_upsample2x(const float* d_x, int height, int width, int channels, uin
     return R3G_OK;
 }
 
+int r3g_op_vec_add(const float* d_a, const float* d_b, float* d_out, int n, void* stream) {
+    // (a null operand is a vector of zeros, as for the resnet block whose conv1 has no bias)
+    if (!d_out || n < 1) return fail(R3G_ERR_INVALID, "r3g_op_vec_add: needs out and n >= 1");
+    hipError_t e = vec_add_launch(d_a, d_b, d_out, n, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "r3g_op_vec_add");
+    return R3G_OK;
+}
+
 int r3g_sched_model_input(const float* d_latent, int channels, const float* d_cond, int cond_channels, int64_t pixels, float sigma,
                           float* d_out, void* stream) {
     if (!d_latent || !d_cond || !d_out || channels < 1 || cond_channels < 1 || pixels < 1 || !(sigma >= 0.0f))

@@ -132,6 +132,21 @@ SYMBOLS = {
     "r3g_op_softmax_rows": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, ctypes.c_float, _P]),
     "r3g_op_geglu": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P]),
     "r3g_op_swiglu": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P]),
+    "r3g_op_gemv": (_I, [_P, _I, _I, _P, ctypes.c_int64, _P, _P, _I, _I, _I, _P]),
+    "r3g_op_gemv_multi": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "r3g_op_timestep_embedding": (_I, [_P, ctypes.c_float, _I, ctypes.c_float, _P, _P]),
+    "r3g_op_fourier_grid": (_I, [_P, ctypes.c_int64, _I, _I, _D, _I, _I, _P]),
+    "r3g_op_fourier_points": (_I, [_P, _P, _I, _I, _I, _D, _I, _I, _P]),
+    "r3g_op_cfg_euler": (_I, [_P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P]),
+    "r3g_op_euler_step": (_I, [_P, _P, ctypes.c_int64, ctypes.c_float, _P]),
+    "r3g_op_nonfinite_flag": (_I, [_P, ctypes.c_int64, _P, _P]),
+    "r3g_op_cast_pad": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _I, ctypes.c_float, _P]),
+    "r3g_op_fill_rows": (_I, [_P, ctypes.c_int64, _I, _I, _P, _P]),
+    "r3g_op_add_rows": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P]),
+    "r3g_op_f32_to_bf16": (_I, [_P, _P, ctypes.c_int64, _P]),
+    "r3g_op_patch_rows": (_I, [_P, _I, _I, _P, _I, _P]),
+    "r3g_op_vec_add_inplace": (_I, [_P, _P, _I, _P]),
+    "r3g_op_vec_add": (_I, [_P, _P, _P, _I, _P]),
     "r3g_set_staging": (_I, [_I]),
     "r3g_set_option": (_I, [ctypes.c_char_p, _I]),
     "r3g_get_option": (_I, [ctypes.c_char_p, _P]),

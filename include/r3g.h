@@ -903,6 +903,52 @@ int r3g_op_group_norm(const float* d_x, int rows, int c, int groups, const float
 int r3g_op_softmax_rows(const float* d_s, int64_t lds, uint16_t* d_p, int64_t ldp, int rows, int n, float scale, void* stream);
 int r3g_op_geglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f, void* stream);
 int r3g_op_swiglu(const uint16_t* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int f, void* stream);
+/* The small kernels every sampling step and every staged input passes through, one launch each (csrc/elem.hip; vec_add:
+ * csrc/conv_kernels.hip).  Test hooks (tests/test_vec_kernels_gpu.py).  The whole contract is checked in the entry point; a violation
+ * is R3G_ERR_INVALID with nothing launched or written.  Common to all: every pointer named non-null unless stated, every size (b, k, n,
+ * rows, c, count, njobs, s, ps) >= 1, a leading dimension at least the width.  All f32 unless stated.
+ *
+ * gemv: y [b][n] = act_out(act_in(x [b][k]) . w[row][:] + bias[row]), w bf16 [n][ldw], bias (may be null) [n]; act = SiLU where the
+ *   flag is set.  1 <= b <= 8, k % 8 == 0, b * k * 4 <= 65536, ldw % 8 == 0, ldw >= k, w 16-byte aligned (16 bytes of w per lane).
+ * gemv_multi: njobs matrices over ONE input, 1 <= b <= 2: job j writes y[out_off[j] + bi * n[j] + row] (no output activation).  w, bias
+ *   (null, or an array whose entries may be null), ldw, n, out_off are HOST arrays of njobs entries, w[j] / bias[j] device pointers; per
+ *   job the demands of gemv, and out_off[j] >= 0.  The entry point builds the device table itself and is synchronous.
+ * timestep_embedding: out [b][256] = cos | sin (128 each) of t * time_factor * exp(-ln(10000) j / 128); d_t [b], or null: every row
+ *   uses t_scalar.
+ * fourier_grid: out bf16 [count][64] = rows start .. start + count - 1 of the dense lattice, point idx = (i (r + 1) + j) (r + 1) + k
+ *   with coordinates np.linspace(-bound, bound, r + 1, dtype=float32); channels [x y z | sin(x_c 2^f [pi]), c major, f minor | cos
+ *   likewise | zeros]; a row at or past (r + 1)^3 is the embedding of the origin.  r >= 1, start >= 0, 0 <= num_freqs, 3 + 6 num_freqs
+ *   <= 64.
+ * fourier_points: the same rows for listed points: row i < count is point d_list[i] (int32; bit for bit fourier_grid's row for that
+ *   index), rows [count, rows) are the origin's.  1 <= count <= rows, out 16-byte aligned.  The list ENTRIES are the caller's
+ *   responsibility (>= 0; an entry at or past (r + 1)^3 gives the origin's row): they are not read on the host.
+ * cfg_euler: lat[i] += dsigma (vu + guidance (vc - vu)), vc = v2[i], vu = v2[n + i] (conditional half first), i < n.
+ * euler_step: lat[i] += dsigma v[i]; float4 accesses when both pointers are 16-byte aligned, one element per lane otherwise.
+ * nonfinite_flag: *d_flag |= 1 when x[0 .. n) holds a NaN or an infinity; never cleared.
+ * cast_pad: out bf16 [rows][ldo]: out[r][col] = bf16(in[r][col] * scale) for col < c, 0 for c <= col < cpad; c <= cpad, ldi >= c, ldo >= cpad.
+ * fill_rows: dst[r][col] = vals[col];  add_rows: x[r][col] += pos[r][col];  over [rows) x [c).
+ * f32_to_bf16: out bf16 [n] = in [n], round to nearest even.
+ * patch_rows: img [3][s][s] -> out bf16 [(s / ps)^2][kpad]: patch (py, px), column (ch ps + dy) ps + dx = img[ch][py ps + dy][px ps + dx],
+ *   columns [3 ps^2, kpad) zero.  s % ps == 0, ps <= 1024, kpad >= 3 ps^2.
+ * vec_add_inplace: y[i] += x[i];  vec_add: out[i] = a[i] + b[i], a null a or b standing for zeros (0.0f + b[i]);  i < n. */
+int r3g_op_gemv(const float* d_x, int b, int k, const uint16_t* d_w, int64_t ldw, const float* d_bias, float* d_y, int n, int silu_in,
+                int silu_out, void* stream);
+int r3g_op_gemv_multi(const float* d_x, int b, int k, const void* const* w, const void* const* bias, const int64_t* ldw, const int* n,
+                      const int64_t* out_off, int njobs, float* d_y, int silu_in, void* stream);
+int r3g_op_timestep_embedding(const float* d_t, float t_scalar, int b, float time_factor, float* d_out, void* stream);
+int r3g_op_fourier_grid(uint16_t* d_out, int64_t start, int count, int r, double bound, int num_freqs, int include_pi, void* stream);
+int r3g_op_fourier_points(uint16_t* d_out, const int32_t* d_list, int count, int rows, int r, double bound, int num_freqs, int include_pi,
+                          void* stream);
+int r3g_op_cfg_euler(float* d_lat, const float* d_v2, int64_t n, float guidance, float dsigma, void* stream);
+int r3g_op_euler_step(float* d_lat, const float* d_v, int64_t n, float dsigma, void* stream);
+int r3g_op_nonfinite_flag(const float* d_x, int64_t n, int* d_flag, void* stream);
+int r3g_op_cast_pad(const float* d_in, int64_t ldi, uint16_t* d_out, int64_t ldo, int rows, int c, int cpad, float scale, void* stream);
+int r3g_op_fill_rows(float* d_dst, int64_t ld, int rows, int c, const float* d_vals, void* stream);
+int r3g_op_add_rows(float* d_x, int64_t ldx, const float* d_pos, int64_t ldp, int rows, int c, void* stream);
+int r3g_op_f32_to_bf16(const float* d_in, uint16_t* d_out, int64_t n, void* stream);
+int r3g_op_patch_rows(const float* d_img, int s, int ps, uint16_t* d_out, int kpad, void* stream);
+int r3g_op_vec_add_inplace(float* d_y, const float* d_x, int n, void* stream);
+int r3g_op_vec_add(const float* d_a, const float* d_b, float* d_out, int n, void* stream);
 /* FP8 operands (BASELINE.json configs[3]).  Test / benchmark hooks; the model uses the same kernels for the geo decoder under
  * r3g_set_option("geo_fp8", 1).
  * quant_fp8: bf16 [rows][k] -> OCP e4m3 bytes [rows][k] + one fp32 scale per row; k % 8 == 0, ldx % 8 == 0, ldq % 8 == 0.
