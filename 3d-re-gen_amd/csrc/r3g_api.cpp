@@ -1158,8 +1158,10 @@ int r3g_tex_rasterize(r3g_ctx* ctx, const float* d_pos_clip, int64_t n_verts, co
 
 int r3g_tex_interpolate(r3g_ctx* ctx, const float* d_attr, int channels, const int32_t* d_tri, const int32_t* d_findices,
                         const float* d_bary, int64_t n_pixels, float* d_out, void* stream) {
-    if (!ctx || !d_attr || !d_tri || !d_findices || !d_bary || !d_out) return fail(R3G_ERR_INVALID, "r3g_tex_interpolate: null argument");
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_tex_interpolate: null argument");
     if (channels < 1 || channels > 64 || n_pixels < 0) return fail(R3G_ERR_INVALID, "r3g_tex_interpolate: bad sizes");
+    if (n_pixels == 0) return R3G_OK;      // nothing to do and no launch; an empty image may come with null buffers
+    if (!d_attr || !d_tri || !d_findices || !d_bary || !d_out) return fail(R3G_ERR_INVALID, "r3g_tex_interpolate: null argument");
     hipError_t e = tex_interpolate(d_attr, channels, d_tri, d_findices, d_bary, n_pixels, d_out, (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "tex_interpolate");
 }
@@ -1176,9 +1178,11 @@ int r3g_tex_view_weight(r3g_ctx* ctx, const int32_t* d_findices, const float* d_
 
 int r3g_tex_bake(r3g_ctx* ctx, const float* d_image, const float* d_weight, const int32_t* d_findices, const float* d_bary,
                  const float* d_uv, const int32_t* d_uv_tri, int64_t n_pixels, int tex_size, uint64_t* d_acc, void* stream) {
-    if (!ctx || !d_image || !d_weight || !d_findices || !d_bary || !d_uv || !d_uv_tri || !d_acc)
-        return fail(R3G_ERR_INVALID, "r3g_tex_bake: null argument");
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_tex_bake: null argument");
     if (tex_size < 1 || tex_size > 16384 || n_pixels < 0) return fail(R3G_ERR_INVALID, "r3g_tex_bake: bad sizes");
+    if (n_pixels == 0) return R3G_OK;      // nothing to do and no launch; an empty view may come with null buffers
+    if (!d_image || !d_weight || !d_findices || !d_bary || !d_uv || !d_uv_tri || !d_acc)
+        return fail(R3G_ERR_INVALID, "r3g_tex_bake: null argument");
     hipError_t e = tex_bake(d_image, d_weight, d_findices, d_bary, d_uv, d_uv_tri, n_pixels, tex_size, (unsigned long long*)d_acc,
                             (hipStream_t)stream);
     return e == hipSuccess ? R3G_OK : hip_fail(e, "tex_bake");

@@ -8,7 +8,8 @@
 //
 //   tex_rasterize      clip-space triangles -> per pixel {face id + 1, perspective-correct barycentrics}; z-buffer by a 64-bit
 //                      atomicMin on (depth bits << 32 | face id + 1): nearest wins, ties go to the smaller face id, so the
-//                      image does not depend on scheduling.  One wave per face, lanes over its bounding box.
+//                      image does not depend on scheduling.  One wave per face, lanes over its bounding box.  Coverage by
+//                      three inclusive edge functions, each evaluated in a canonical endpoint order (watertight).
 //   tex_interpolate    per-pixel attribute = sum of barycentric * per-corner attribute (any index array: positions, uv).
 //   tex_view_weight    per-pixel baking weight: view_weight * cos^power, zero below a cosine threshold and on depth edges.
 //   tex_bake_gather    texel-centric baking (the pipeline's default): each covered texel projects itself into the view,
@@ -52,16 +53,37 @@ __device__ __forceinline__ ScreenTri screen_tri(const float* __restrict__ pos4, 
         t.w[k] = w;
     }
     t.area = (t.x[1] - t.x[0]) * (t.y[2] - t.y[0]) - (t.x[2] - t.x[0]) * (t.y[1] - t.y[0]);
-    t.ok = t.ok && t.area != 0.f && t.area == t.area;
+    t.ok = t.ok && t.area != 0.f && fabsf(t.area) < __builtin_inff();      // finite (false for a NaN) and not zero
     return t;
 }
 
-// screen-space barycentrics of the pixel centre (px, py); returns false outside
-__device__ __forceinline__ bool bary_at(const ScreenTri& t, float px, float py, float (&b)[3]) {
-    b[0] = ((t.x[1] - px) * (t.y[2] - py) - (t.x[2] - px) * (t.y[1] - py)) / t.area;
-    b[1] = ((t.x[2] - px) * (t.y[0] - py) - (t.x[0] - px) * (t.y[2] - py)) / t.area;
-    b[2] = 1.f - b[0] - b[1];
-    return b[0] >= 0.f && b[1] >= 0.f && b[2] >= 0.f;
+// screen-space barycentrics of the pixel centre (px, py).  A centre the edge tests admit may round to a barycentric just
+// below 0: clamped, so that what leaves is >= 0 and sums to 1 (the comparisons send a NaN to 0).
+__device__ __forceinline__ void bary_at(const ScreenTri& t, float px, float py, float (&b)[3]) {
+    const float b0 = ((t.x[1] - px) * (t.y[2] - py) - (t.x[2] - px) * (t.y[1] - py)) / t.area;
+    const float b1 = ((t.x[2] - px) * (t.y[0] - py) - (t.x[0] - px) * (t.y[2] - py)) / t.area;
+    b[0] = b0 > 0.f ? b0 : 0.f;
+    b[1] = b1 > 0.f ? b1 : 0.f;
+    const float b2 = 1.f - b[0] - b[1];
+    b[2] = b2 > 0.f ? b2 : 0.f;
+}
+
+// Edge function of the pixel centre against the edge {a, b}, > 0 on the left of a -> b.  It is EVALUATED from the endpoints
+// in lexicographic (x, y) order and negated when that swaps them: the two faces that share an edge get the same float with
+// opposite signs whatever their windings, so a centre that one of them rejects the other admits (watertight coverage).
+__device__ __forceinline__ float edge_fn(float ax, float ay, float bx, float by, float px, float py) {
+    const bool swap = bx < ax || (bx == ax && by < ay);
+    const float x0 = swap ? bx : ax, y0 = swap ? by : ay, x1 = swap ? ax : bx, y1 = swap ? ay : by;
+    const float e = (x1 - x0) * (py - y0) - (y1 - y0) * (px - x0);
+    return swap ? -e : e;
+}
+
+// inclusive coverage: the three edge functions have the sign of the area or are zero (a NaN admits nothing)
+__device__ __forceinline__ bool covers(const ScreenTri& t, float px, float py) {
+    const float e0 = edge_fn(t.x[1], t.y[1], t.x[2], t.y[2], px, py);
+    const float e1 = edge_fn(t.x[2], t.y[2], t.x[0], t.y[0], px, py);
+    const float e2 = edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], px, py);
+    return t.area > 0.f ? (e0 >= 0.f && e1 >= 0.f && e2 >= 0.f) : (e0 <= 0.f && e1 <= 0.f && e2 <= 0.f);
 }
 
 __global__ __launch_bounds__(256) void fill_u64(unsigned long long* p, int64_t n, unsigned long long v) {
@@ -78,15 +100,19 @@ __global__ __launch_bounds__(64) void raster_faces(const float* __restrict__ pos
     const float minx = fminf(t.x[0], fminf(t.x[1], t.x[2])), maxx = fmaxf(t.x[0], fmaxf(t.x[1], t.x[2]));
     const float miny = fminf(t.y[0], fminf(t.y[1], t.y[2])), maxy = fmaxf(t.y[0], fmaxf(t.y[1], t.y[2]));
     if (!(maxx >= 0.f && maxy >= 0.f && minx <= (float)W && miny <= (float)H)) return;
-    const int ix0 = max(0, (int)floorf(minx) - 1), ix1 = min(W - 1, (int)floorf(maxx) + 1);
-    const int iy0 = max(0, (int)floorf(miny) - 1), iy1 = min(H - 1, (int)floorf(maxy) + 1);
+    // one pixel of margin, clamped in float BEFORE the conversion: after the rejection above both ends land in [0, W - 1]
+    // whatever the magnitudes (a finite coordinate may exceed 2^31 pixels)
+    const int ix0 = (int)fmaxf(floorf(minx) - 1.f, 0.f), ix1 = (int)fminf(floorf(maxx) + 1.f, (float)(W - 1));
+    const int iy0 = (int)fmaxf(floorf(miny) - 1.f, 0.f), iy1 = (int)fminf(floorf(maxy) + 1.f, (float)(H - 1));
     if (ix1 < ix0 || iy1 < iy0) return;
     const int bw = ix1 - ix0 + 1;
     const int64_t n = (int64_t)bw * (iy1 - iy0 + 1);
     for (int64_t i = threadIdx.x; i < n; i += 64) {
         const int ix = ix0 + (int)(i % bw), iy = iy0 + (int)(i / bw);
+        const float px = (float)ix + 0.5f, py = (float)iy + 0.5f;
+        if (!covers(t, px, py)) continue;
         float b[3];
-        if (!bary_at(t, (float)ix + 0.5f, (float)iy + 0.5f, b)) continue;
+        bary_at(t, px, py, b);
         const float depth = b[0] * t.z[0] + b[1] * t.z[1] + b[2] * t.z[2];
         if (!(depth >= 0.f && depth <= 1.f)) continue;
         const unsigned long long token = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned)(f + 1);
@@ -106,7 +132,7 @@ __global__ __launch_bounds__(256) void raster_resolve(const float* __restrict__ 
         id = (int)(unsigned)(token & 0xFFFFFFFFull);
         const ScreenTri t = screen_tri(pos4, tri, id - 1, H, W);
         float b[3];
-        (void)bary_at(t, (float)(i % W) + 0.5f, (float)(i / W) + 0.5f, b);
+        bary_at(t, (float)(i % W) + 0.5f, (float)(i / W) + 0.5f, b);
         // perspective correction: divide by clip w, renormalise
         const float c0 = b[0] / t.w[0], c1 = b[1] / t.w[1], c2 = b[2] / t.w[2];
         const float s = c0 + c1 + c2;
@@ -159,14 +185,20 @@ __global__ __launch_bounds__(256) void view_weight_kernel(const int32_t* __restr
     weight[i] = wgt;
 }
 
+// texel of a texture coordinate: round(u (T-1)), clamped to [0, T-1] in float before the conversion; -1 for a coordinate
+// that is NaN (also inf at T == 1, where inf * 0 is NaN): the caller skips that sample
 __device__ __forceinline__ int texel_of(float u, int T) {
-    const int t = (int)(u * (float)(T - 1) + 0.5f);
-    return t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
+    const float t = u * (float)(T - 1) + 0.5f;
+    if (t != t) return -1;
+    return (int)(t > 0.f ? (t < (float)(T - 1) ? t : (float)(T - 1)) : 0.f);
 }
+// colour -> 16.16 fixed point, clamped to [0, 1] by comparisons (a NaN gives 0; the bakers skip such a sample whole)
 __device__ __forceinline__ unsigned q16(float c) {
-    const float cc = c < 0.f ? 0.f : (c > 1.f ? 1.f : c);
+    const float cc = c > 0.f ? (c < 1.f ? c : 1.f) : 0.f;
     return (unsigned)(cc * 65536.f + 0.5f);
 }
+// baking weight (> 0, not NaN) -> 16.16 fixed point, clamped at 65535 so that it fits 32 bits
+__device__ __forceinline__ unsigned weight_q(float w) { return (unsigned)(fminf(w, 65535.f) * 65536.f + 0.5f); }
 
 __global__ __launch_bounds__(256) void bake_kernel(const float* __restrict__ image, const float* __restrict__ weight,
                                                    const int32_t* __restrict__ findices, const float* __restrict__ bary,
@@ -177,15 +209,20 @@ __global__ __launch_bounds__(256) void bake_kernel(const float* __restrict__ ima
     const int id = findices[i];
     const float w = weight[i];
     if (id <= 0 || !(w > 0.f)) return;
-    const unsigned wq = (unsigned)(fminf(w, 65535.f) * 65536.f + 0.5f) >> 0;
+    const float c0 = image[3 * i], c1 = image[3 * i + 1], c2 = image[3 * i + 2];
+    if (c0 != c0 || c1 != c1 || c2 != c2) return;      // a NaN colour contributes nothing
+    const unsigned wq = weight_q(w);
     if (wq == 0u) return;
     const int32_t* t = uv_tri + 3 * (int64_t)(id - 1);
     const float b0 = bary[3 * i], b1 = bary[3 * i + 1], b2 = bary[3 * i + 2];
     const float u = b0 * uv[2 * (int64_t)t[0]] + b1 * uv[2 * (int64_t)t[1]] + b2 * uv[2 * (int64_t)t[2]];
     const float v = b0 * uv[2 * (int64_t)t[0] + 1] + b1 * uv[2 * (int64_t)t[1] + 1] + b2 * uv[2 * (int64_t)t[2] + 1];
-    const int64_t tex = (int64_t)texel_of(v, T) * T + texel_of(u, T);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) atomicAdd(&acc[4 * tex + c], (unsigned long long)wq * q16(image[3 * i + c]));
+    const int tu = texel_of(u, T), tv = texel_of(v, T);
+    if (tu < 0 || tv < 0) return;                      // a NaN texture coordinate contributes nothing
+    const int64_t tex = (int64_t)tv * T + tu;
+    atomicAdd(&acc[4 * tex], (unsigned long long)wq * q16(c0));
+    atomicAdd(&acc[4 * tex + 1], (unsigned long long)wq * q16(c1));
+    atomicAdd(&acc[4 * tex + 2], (unsigned long long)wq * q16(c2));
     atomicAdd(&acc[4 * tex + 3], (unsigned long long)wq);
 }
 
@@ -213,12 +250,12 @@ __global__ __launch_bounds__(256) void bake_gather_kernel(const int32_t* __restr
     const float sx = (p[0] / p[3] * 0.5f + 0.5f) * (float)(W - 1) + 0.5f;
     const float sy = (p[1] / p[3] * 0.5f + 0.5f) * (float)(H - 1) + 0.5f;
     const float z = p[2] / p[3];
+    if (!(sx >= 0.f && sy >= 0.f && sx < (float)W && sy < (float)H)) return;     // also a NaN; no conversion before it
     const int px = (int)floorf(sx), py = (int)floorf(sy);
-    if (px < 0 || py < 0 || px >= W || py >= H) return;
     const int64_t pix = (int64_t)py * W + px;
     const float w = weight[pix];
-    if (findices[pix] <= 0 || !(w > 0.f) || z > depth[pix] + depth_eps) return;
-    const unsigned wq = (unsigned)(fminf(w, 65535.f) * 65536.f + 0.5f);
+    if (findices[pix] <= 0 || !(w > 0.f) || !(z <= depth[pix] + depth_eps)) return;
+    const unsigned wq = weight_q(w);
     if (wq == 0u) return;
     // bilinear sample at the pixel-centre coordinates (sx - 0.5, sy - 0.5), clamped at the border
     const float fx = sx - 0.5f, fy = sy - 0.5f;
@@ -227,13 +264,17 @@ __global__ __launch_bounds__(256) void bake_gather_kernel(const int32_t* __restr
     int x1 = x0 + 1, y1 = y0 + 1;
     x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0); x1 = x1 < 0 ? 0 : (x1 > W - 1 ? W - 1 : x1);
     y0 = y0 < 0 ? 0 : (y0 > H - 1 ? H - 1 : y0); y1 = y1 < 0 ? 0 : (y1 > H - 1 ? H - 1 : y1);
+    float col[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float c00 = image[3 * ((int64_t)y0 * W + x0) + c], c01 = image[3 * ((int64_t)y0 * W + x1) + c];
         const float c10 = image[3 * ((int64_t)y1 * W + x0) + c], c11 = image[3 * ((int64_t)y1 * W + x1) + c];
         const float top = c00 + (c01 - c00) * ax, bot = c10 + (c11 - c10) * ax;
-        acc[4 * i + c] += (unsigned long long)wq * q16(top + (bot - top) * ay);
+        col[c] = top + (bot - top) * ay;
     }
+    if (col[0] != col[0] || col[1] != col[1] || col[2] != col[2]) return;        // a NaN sample contributes nothing
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[4 * i + c] += (unsigned long long)wq * q16(col[c]);
     acc[4 * i + 3] += (unsigned long long)wq;
 }
 
@@ -264,7 +305,8 @@ __device__ __forceinline__ int64_t corner_texel(const float* uv, const int32_t* 
     const float cv = ((uv[2 * j0 + 1] + uv[2 * j1 + 1]) + uv[2 * j2 + 1]) * third;
     const float pu = uv[2 * j] * 0.75f + cu * 0.25f;
     const float pv = uv[2 * j + 1] * 0.75f + cv * 0.25f;
-    return (int64_t)texel_of(pv, T) * T + texel_of(pu, T);
+    const int tu = texel_of(pu, T), tv = texel_of(pv, T);
+    return tu < 0 || tv < 0 ? -1 : (int64_t)tv * T + tu;      // -1: the corner's UV is NaN, it owns nothing
 }
 
 __global__ __launch_bounds__(256) void vertex_owner_kernel(const uint8_t* __restrict__ mask, int T, const float* __restrict__ uv,
@@ -272,7 +314,8 @@ __global__ __launch_bounds__(256) void vertex_owner_kernel(const uint8_t* __rest
                                                            int64_t ncorner, unsigned* __restrict__ owner) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= ncorner) return;
-    if (mask[corner_texel(uv, uv_tri, c, T)]) atomicMin(&owner[pos_tri[c]], (unsigned)c);
+    const int64_t t = corner_texel(uv, uv_tri, c, T);
+    if (t >= 0 && mask[t]) atomicMin(&owner[pos_tri[c]], (unsigned)c);
 }
 
 __global__ __launch_bounds__(256) void vertex_gather_kernel(const float* __restrict__ tex, int T, const float* __restrict__ uv,
@@ -283,7 +326,7 @@ __global__ __launch_bounds__(256) void vertex_gather_kernel(const float* __restr
     const unsigned c = owner[v];
     float r = 0.f, g = 0.f, b = 0.f;
     if (c != 0xFFFFFFFFu) {
-        const int64_t t = corner_texel(uv, uv_tri, c, T);
+        const int64_t t = corner_texel(uv, uv_tri, c, T);      // >= 0: only a corner with a texel becomes an owner
         r = tex[3 * t]; g = tex[3 * t + 1]; b = tex[3 * t + 2];
     }
     vcolor[3 * v] = r; vcolor[3 * v + 1] = g; vcolor[3 * v + 2] = b;
@@ -306,8 +349,9 @@ __global__ __launch_bounds__(256) void propagate_edges_kernel(const float* __res
         const float dx = verts[3 * (int64_t)a] - verts[3 * (int64_t)b], dy = verts[3 * (int64_t)a + 1] - verts[3 * (int64_t)b + 1],
                     dz = verts[3 * (int64_t)a + 2] - verts[3 * (int64_t)b + 2];
         const float w = 1.f / (dx * dx + dy * dy + dz * dz + 1e-6f);
-        const unsigned long long wq = (unsigned long long)(w * 1024.f + 0.5f);
-        if (!wq) continue;
+        const float wf = w * 1024.f + 0.5f;
+        if (!(wf >= 1.f)) continue;                    // below the weight's resolution, or NaN: no edge
+        const unsigned long long wq = (unsigned long long)wf;
 #pragma unroll
         for (int k = 0; k < 3; ++k) atomicAdd(&acc[4 * (int64_t)a + k], wq * q16(vcolor[3 * (int64_t)b + k]));
         atomicAdd(&acc[4 * (int64_t)a + 3], wq);
@@ -391,6 +435,7 @@ hipError_t tex_rasterize(const float* pos4, const int32_t* tri, int F, int H, in
 
 hipError_t tex_interpolate(const float* attr, int C, const int32_t* tri, const int32_t* findices, const float* bary,
                            int64_t npix, float* out, hipStream_t s) {
+    if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(interpolate_kernel, blocks(npix), dim3(256), 0, s, attr, C, tri, findices, bary, npix, out);
     return hipGetLastError();
 }
@@ -405,6 +450,7 @@ hipError_t tex_view_weight(const int32_t* findices, const float* depth, const fl
 
 hipError_t tex_bake(const float* image, const float* weight, const int32_t* findices, const float* bary, const float* uv,
                     const int32_t* uv_tri, int64_t npix, int T, unsigned long long* acc, hipStream_t s) {
+    if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(bake_kernel, blocks(npix), dim3(256), 0, s, image, weight, findices, bary, uv, uv_tri, npix, T, acc);
     return hipGetLastError();
 }

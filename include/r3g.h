@@ -451,7 +451,15 @@ int r3g_recon_sample(r3g_ctx* ctx, int field, const float* d_points, const float
  *   rasterize     ~ custom_rasterizer.rasterize(pos, tri, (H, W)): pos_clip float32 [V][4], tri int32 [F][3] ->
  *                   findices int32 [H][W] (face + 1, 0 = empty), bary float32 [H][W][3] (perspective-correct).  Pixel
  *                   (ix, iy) samples (ix + 0.5, iy + 0.5) of the screen x = (x/w/2 + 1/2)(W-1) + 1/2; nearest depth wins, equal
- *                   depths go to the smaller face index (result independent of scheduling).
+ *                   depths go to the smaller face index (result independent of scheduling).  A face is drawn when all its
+ *                   w > 0, its screen area is finite and not zero, and its depth z/w * 0.49999 + 1/2 lies in [0, 1].
+ *                   COVERAGE is watertight: a sample belongs to a face when its three edge functions have the sign of the
+ *                   face's area or are zero (inclusive), and each edge function is evaluated from the edge's two endpoints
+ *                   in lexicographic screen (x, y) order, so that the two faces sharing an edge compute the same float with
+ *                   opposite signs: no sample on or next to a shared edge is rejected by both.  The barycentrics written are
+ *                   clamped at 0 before the perspective division: all three are >= 0 and they sum to 1.  The bounding box is
+ *                   clamped in float before it is converted, so a finite coordinate of any size (a vertex with a small
+ *                   positive w) is drawn.  With height == 1 or width == 1 the screen scale is 0 and nothing is drawn.
  *   interpolate   ~ custom_rasterizer.interpolate(attr, findices, bary, tri): out[p] = sum_k bary[p][k] attr[tri[f][k]].
  *   view_weight   baking weight of a view: view_weight * cos^power of the view-space normal, 0 below cos_threshold, on
  *                   the silhouette and where the depth jumps by more than depth_edge between 4-neighbours.
@@ -466,7 +474,17 @@ int r3g_recon_sample(r3g_ctx* ctx, int field, const float* d_points, const float
  *   inpaint       ~ mesh_processor.meshVerticeInpaint + the dilation upstream does with cv2: vertex colours from painted
  *                   texels, propagation along mesh edges (weights 1/(d^2 + 1e-6), Jacobi rounds until nothing changes),
  *                   unpainted covered texels from the vertex colours (mask 2), `dilate_iters` steps into empty texels (mask
- *                   3).  findices_uv / bary_uv = rasterize() of the mesh in UV space.  Synchronises the stream. */
+ *                   3).  findices_uv / bary_uv = rasterize() of the mesh in UV space.  Synchronises the stream.
+ * NaN AND OUT-OF-RANGE VALUES are handled by explicit comparisons; no result depends on converting a NaN or an out-of-range
+ * float to an integer.  A pixel or texel whose colour, weight or coordinate is NaN contributes NOTHING (neither colour nor
+ * weight): a NaN weight (view_weight gives one for a negative cosine with a fractional power) or a weight <= 0 is skipped, a
+ * NaN colour channel or bilinear sample skips the whole sample, a NaN texture coordinate, clip position or depth skips it, a
+ * corner whose UV is NaN seeds no vertex, an edge whose length is NaN carries no colour.  Finite values are clamped: colours
+ * to [0, 1], weights at 65535, texels to [0, T-1] (in float, before the conversion).
+ * ZERO SIZES: interpolate and bake with n_pixels == 0 return R3G_OK without a launch (their buffers may then be null);
+ * rasterize accepts n_faces == 0 (an empty image).
+ * INDEX ARRAYS (tri, uv_tri, pos_tri, findices) must be in range: face ids in [0, n_faces], vertex ids inside their arrays.
+ * They are NOT checked on the device; an index out of range reads or writes outside the buffers. */
 int r3g_tex_rasterize(r3g_ctx* ctx, const float* d_pos_clip, int64_t n_verts, const int32_t* d_tri, int64_t n_faces, int height,
                       int width, int32_t* d_findices, float* d_bary, void* stream);
 int r3g_tex_interpolate(r3g_ctx* ctx, const float* d_attr, int channels, const int32_t* d_tri, const int32_t* d_findices,
