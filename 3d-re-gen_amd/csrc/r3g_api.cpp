@@ -288,6 +288,8 @@ void r3g_destroy(r3g_ctx* ctx) {
         for (hipEvent_t e : c->dbscan_ev) (void)hipEventDestroy(e);
     if (c->plane_ev_made)
         for (hipEvent_t e : c->plane_ev) (void)hipEventDestroy(e);
+    if (c->softras_ev_made)
+        for (hipEvent_t e : c->softras_ev) (void)hipEventDestroy(e);
     c->release_model();
     c->release_unet();
     delete c;                           // every buffer of the context goes with its DevBuf member
@@ -717,6 +719,122 @@ int r3g_plane_times(r3g_ctx* ctx, double* ms) {
         float t = 0.0f;
         hipError_t e = hipEventElapsedTime(&t, c->plane_ev[p], c->plane_ev[p + 1]);
         if (e != hipSuccess) return hip_fail(e, "hipEventElapsedTime(plane)");
+        ms[p] = (double)t;
+    }
+    return R3G_OK;
+}
+
+// ---- soft silhouette: K-nearest soft rasteriser and its gradient to the vertices -------------------------
+static int softras_args(const char* who, int64_t n_verts, int64_t n_faces, int height, int width, int K, double sigma, double blur_radius,
+                        SoftrasGeom* g) {
+    if (K < 1 || K > r3g_sr::kMaxK) return fail(R3G_ERR_INVALID, "%s: K outside [1, %d]", who, r3g_sr::kMaxK);
+    const float sg = (float)sigma, br = (float)blur_radius;
+    if (!(sg > 0.0f) || !(sg - sg == 0.0f)) return fail(R3G_ERR_INVALID, "%s: sigma must be finite and > 0 in float32", who);
+    if (!(br >= 0.0f)) return fail(R3G_ERR_INVALID, "%s: blur_radius must be >= 0", who);
+    if (height < 1 || width < 1 || height > r3g_sr::kMaxSide || width > r3g_sr::kMaxSide)
+        return fail(R3G_ERR_INVALID, "%s: height and width must lie in [1, %d]", who, r3g_sr::kMaxSide);
+    if (n_verts < 0 || n_verts >= (1ll << 31) || n_faces < 0 || n_faces > (1ll << 29)) return fail(R3G_ERR_INVALID, "%s: mesh sizes out of range", who);
+    g->height = height, g->width = width, g->K = K;
+    g->tiles_x = (width + r3g_sr::kTile - 1) / r3g_sr::kTile, g->tiles_y = (height + r3g_sr::kTile - 1) / r3g_sr::kTile;
+    g->sigma = sg, g->blur_radius = br, g->blur_reach = sqrtf(br);
+    return R3G_OK;
+}
+
+static int softras_events(Ctx* c) {
+    if (c->softras_ev_made) return R3G_OK;
+    for (int i = 0; i < 6; ++i) {
+        hipError_t he = hipEventCreate(&c->softras_ev[i]);
+        if (he != hipSuccess) {      // all or none, as for the plane fit
+            while (i-- > 0) (void)hipEventDestroy(c->softras_ev[i]);
+            return hip_fail(he, "hipEventCreate(softras)");
+        }
+    }
+    c->softras_ev_made = true;
+    return R3G_OK;
+}
+
+int r3g_softras_forward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, const int32_t* d_tri, int64_t n_faces, int height, int width, int K,
+                        double sigma, double blur_radius, float* d_alpha, int32_t* d_face, float* d_dist, float* d_zbuf, int64_t* report,
+                        void* stream) {
+    SoftrasGeom g;
+    if (const int rc = softras_args("r3g_softras_forward", n_verts, n_faces, height, width, K, sigma, blur_radius, &g)) return rc;
+    if (!d_alpha || !d_face || !d_dist || !d_zbuf || !report || (n_faces && !d_tri) || (n_verts && !d_pos))
+        return fail(R3G_ERR_INVALID, "r3g_softras_forward: null buffer");
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_softras_forward: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    c->softras_fwd_timed = false;
+    if (const int rc = softras_events(c)) return rc;
+    SoftrasLayout lay;
+    if (const int rc = c->softras_ws.grow(softras_workspace_bytes(height, width, &lay), s, "softras workspace")) return rc;
+    char* ws = c->softras_ws.p;
+    hipError_t e;
+    if ((e = hipEventRecord(c->softras_ev[0], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if ((e = softras_bin_count(ws, lay, g, d_pos, n_verts, d_tri, n_faces, s)) != hipSuccess) return hip_fail(e, "softras_bin_count");
+    static_assert(sizeof(SoftrasSmall) <= 64, "the pinned read-back buffer");
+    SoftrasSmall sm;      // (the call's one sync: the pair list is sized from it, and it is the report)
+    if (const int rc = read_back(c->h_small, ws + lay.off_small, &sm, sizeof sm, "softras", s)) return rc;
+    if (sm.pairs > 0x7fffffffull) return fail(R3G_ERR_INVALID, "r3g_softras_forward: %llu (face, tile) pairs, more than 2^31 - 1", sm.pairs);
+    if (const int rc = c->softras_pairs.grow(4 * (size_t)sm.pairs, s, "softras pairs")) return rc;
+    if ((e = softras_bin_fill(ws, lay, g, d_pos, n_verts, d_tri, n_faces, c->softras_pairs.as<int32_t>(), (unsigned)sm.pairs, s)) != hipSuccess)
+        return hip_fail(e, "softras_bin_fill");
+    if ((e = hipEventRecord(c->softras_ev[1], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if ((e = softras_forward(ws, lay, g, d_pos, n_verts, d_tri, n_faces, c->softras_pairs.as<const int32_t>(), d_alpha, d_face, d_dist, d_zbuf, s)) !=
+        hipSuccess)
+        return hip_fail(e, "softras_forward");
+    if ((e = hipEventRecord(c->softras_ev[2], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    c->softras_fwd_timed = true;
+    const int64_t rep[r3g_sr::kFwdReport] = {(int64_t)sm.pairs, (int64_t)sm.used, (int64_t)sm.skipped, lay.tiles, 0, 0, 0, 0};
+    memcpy(report, rep, sizeof rep);
+    return R3G_OK;
+}
+
+int r3g_softras_backward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, const int32_t* d_tri, int64_t n_faces, int height, int width, int K,
+                         double sigma, double blur_radius, const int32_t* d_face, const float* d_dist, const float* d_grad_alpha,
+                         const int32_t* d_corner_start, const int32_t* d_corner_ids, float* d_grad_face, float* d_grad_pos, int64_t* report,
+                         void* stream) {
+    SoftrasGeom g;
+    if (const int rc = softras_args("r3g_softras_backward", n_verts, n_faces, height, width, K, sigma, blur_radius, &g)) return rc;
+    if (!d_face || !d_dist || !d_grad_alpha || !report || (n_faces && (!d_tri || !d_grad_face || !d_corner_ids)) ||
+        (n_verts && (!d_pos || !d_grad_pos || !d_corner_start)))
+        return fail(R3G_ERR_INVALID, "r3g_softras_backward: null buffer");
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_softras_backward: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    c->softras_bwd_timed = false;
+    if (const int rc = softras_events(c)) return rc;
+    SoftrasLayout lay;
+    if (const int rc = c->softras_ws.grow(softras_workspace_bytes(height, width, &lay), s, "softras workspace")) return rc;
+    char* ws = c->softras_ws.p;
+    hipError_t e;
+    if ((e = hipEventRecord(c->softras_ev[3], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if ((e = softras_backward(ws, lay, g, d_pos, n_verts, d_tri, n_faces, d_face, d_dist, d_grad_alpha, d_grad_face, s)) != hipSuccess)
+        return hip_fail(e, "softras_backward");
+    if ((e = hipEventRecord(c->softras_ev[4], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if ((e = softras_gather(d_grad_face, d_corner_start, d_corner_ids, n_verts, n_faces, d_grad_pos, s)) != hipSuccess)
+        return hip_fail(e, "softras_gather");
+    if ((e = hipEventRecord(c->softras_ev[5], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    SoftrasSmall sm;      // (its sync: the caller may free its buffers, and a fault would surface here)
+    if (const int rc = read_back(c->h_small, ws + lay.off_small, &sm, sizeof sm, "softras backward", s)) return rc;
+    c->softras_bwd_timed = true;
+    const int64_t rep[r3g_sr::kBwdReport] = {(int64_t)sm.found, 0, 0, 0};
+    memcpy(report, rep, sizeof rep);
+    return R3G_OK;
+}
+
+int r3g_softras_times(r3g_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return fail(R3G_ERR_INVALID, "r3g_softras_times: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->softras_fwd_timed) return fail(R3G_ERR_STATE, "r3g_softras_times: no complete r3g_softras_forward on this context");
+    hipError_t e = hipEventSynchronize(c->softras_ev[2]);      // (the forward returns before its last kernel has run)
+    if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize(softras)");
+    for (int p = 0; p < r3g_sr::kPasses; ++p) {
+        ms[p] = -1.0;
+        if (p >= 2 && !c->softras_bwd_timed) continue;
+        const int a = p < 2 ? p : p + 1;
+        float t = 0.0f;
+        e = hipEventElapsedTime(&t, c->softras_ev[a], c->softras_ev[a + 1]);
+        if (e != hipSuccess) return hip_fail(e, "hipEventElapsedTime(softras)");
         ms[p] = (double)t;
     }
     return R3G_OK;

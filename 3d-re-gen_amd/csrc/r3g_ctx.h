@@ -20,6 +20,7 @@
 #include "orient_kernels.h"
 #include "plane_kernels.h"
 #include "recon_kernels.h"
+#include "softras_kernels.h"
 
 namespace r3g {
 
@@ -60,6 +61,13 @@ struct Ctx {
     hipEvent_t plane_ev[r3g_pl::kPasses + 1] = {};
     bool plane_ev_made = false;
     bool plane_timed = false;
+    // soft silhouette: the record, per-tile counts, starts and cursors of one r3g_softras_forward / _backward, and the (face, tile)
+    // pairs of the forward (nothing is kept between calls but the buffers); events [0..2] bracket the bin and forward passes of the
+    // last forward, [3..5] the backward and gather passes of the last backward (softras_fwd_timed / _bwd_timed: a complete call)
+    DevBuf softras_ws, softras_pairs;
+    hipEvent_t softras_ev[6] = {};
+    bool softras_ev_made = false;
+    bool softras_fwd_timed = false, softras_bwd_timed = false;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
     // fit h_small), made on first use

@@ -66,6 +66,9 @@ SYMBOLS = {
     "r3g_plane_ransac": (_I, [_P, _P, ctypes.c_int64, _P, _I, _D, _P, _P, _I64P, ctypes.POINTER(_D), _P]),
     "r3g_plane_moments": (_I, [_P, _P, ctypes.c_int64, _P, ctypes.POINTER(_D), _I64P, _P]),
     "r3g_plane_times": (_I, [_P, ctypes.POINTER(_D)]),
+    "r3g_softras_forward": (_I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _I, _D, _D, _P, _P, _P, _P, _I64P, _P]),
+    "r3g_softras_backward": (_I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P, _P, _I64P, _P]),
+    "r3g_softras_times": (_I, [_P, ctypes.POINTER(_D)]),
     "r3g_recon_splat": (_I, [_P, _P, _P, ctypes.c_int64, _I, _P, _D, _P, _I64P, _P]),
     "r3g_recon_solve": (_I, [_P, _I, _P, _P, _P]),
     "r3g_recon_sample": (_I, [_P, _I, _P, _P, ctypes.c_int64, _P, _I64P, _I64P, _P]),

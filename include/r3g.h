@@ -411,6 +411,48 @@ int r3g_plane_moments(r3g_ctx* ctx, const float* d_points, int64_t n_points, con
                       void* stream);
 int r3g_plane_times(r3g_ctx* ctx, double* ms);
 
+/* ---- soft silhouettes: differentiable K-nearest rasteriser ------------------------------------------
+ * The renderer of the reference's planar pose fit (pytorch3d's MeshRasterizer with a blur radius and SoftSilhouetteShader), and
+ * its gradient to the vertices.  d_pos float32 [n_verts][3] = (x, y, z): x, y in pixels, pixel (row i, column j) samples the
+ * point (j + 0.5, i + 0.5), row 0 is the top; z is the view depth.  d_tri int32 [n_faces][3].  All arithmetic is float32, one
+ * rounding per operation, no contraction; the definition is the text of csrc/softras_core.h and tests/emu/softras_emu.cpp
+ * reproduces every bit on the host.
+ *   A face is skipped when an index lies outside [0, n_verts), when one of its nine coordinates is NaN, infinite or larger than
+ *   1e15 in magnitude, when its edge function |area| <= 1e-8, or when its three z are < 0.  At pixel centre p a face has the
+ *   barycentrics b_i = edge_i(p) / area; clipped, c_i = max(b_i, 0) / max(sum, 1e-5); pz = (c0 z0 + c1 z1) + c2 z2; inside = all
+ *   b_i > 0; d2 = the smallest squared distance from p to the three segments (v0 v1), (v1 v2), (v2 v0), the first on a tie, with
+ *   t = dot(v1 - v0, p - v0) / |v1 - v0|^2 clamped to [0, 1] and an edge with |v1 - v0|^2 <= 1e-8 measured to v1; dist = inside ?
+ *   -d2 : d2.  The fragment is kept when (inside or d2 < blur_radius) and not pz < 0.  A pixel keeps the K fragments with the
+ *   smallest key (pz, face index), in ascending order.  alpha = 1 - prod_k (1 - s_k) in list order, s_k = sr_sigmoid(-dist_k /
+ *   sigma), sr_sigmoid(x) = 1 / (1 + sr_exp(-clamp(x, -80, 80))).
+ * r3g_softras_forward: -> d_alpha float32 [height][width], d_face int32 [height][width][K] (-1: empty slot), d_dist and d_zbuf
+ *   float32 [height][width][K] (-1 in an empty slot).  report (int64 [8]): (face, 8 x 8 tile) pairs of the bin pass, faces drawn
+ *   whose box meets the image, faces skipped, tiles, 0, 0, 0, 0.  Launches: count, the scan's three, fill, forward.  Synchronises
+ *   `stream` once, after the count (the pair list is sized from it); the forward kernel is queued behind it.  n_faces == 0
+ *   gives alpha 0 and face -1 everywhere.  More than 2^31 - 1 pairs: R3G_ERR_INVALID.
+ * r3g_softras_backward: d_face, d_dist as the forward wrote them for the same mesh and arguments, d_grad_alpha float32
+ *   [height][width] -> d_grad_face float32 [n_faces][3][2] (the gradient to the xy of each face's corners) and d_grad_pos float32
+ *   [n_verts][3] (z column 0).  d alpha / d dist_k = -(s_k (1 - s_k) prod_{j != k} (1 - s_j)) / sigma, the exclusive product
+ *   multiplied out in list order; d dist / d xy follows the forward's branch (the winning edge, t clamped or not, the sign of
+ *   inside).  A pixel whose grad_alpha is NaN or infinite contributes nothing.  One workgroup per face sums in the fixed order of
+ *   csrc/softras_core.h; a vertex sums its corners d_corner_ids[d_corner_start[v] .. d_corner_start[v + 1]) (int32; corner 3 f +
+ *   a, ascending) sequentially: no floating-point atomics, the same bits on every call.  report (int64 [4]): (pixel, face)
+ *   fragments found in the stored lists, 0, 0, 0.  Synchronises `stream` once.
+ * Both: K outside 1 .. 32, sigma not finite or <= 0 (as float32), blur_radius negative or NaN, height or width outside
+ *   [1, 16384], n_verts or n_faces negative, n_faces above 2^29, a NULL buffer with a non-zero size, report NULL: R3G_ERR_INVALID
+ *   before any launch.
+ * r3g_softras_times: milliseconds between HIP events of the last complete calls on this context, ms double [4]: bin (with its
+ *   read-back), forward, backward, gather; -1 for the last two while no backward has run.  Waits for the forward's kernel.
+ *   Without a forward: R3G_ERR_STATE. */
+int r3g_softras_forward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, const int32_t* d_tri, int64_t n_faces, int height, int width,
+                        int K, double sigma, double blur_radius, float* d_alpha, int32_t* d_face, float* d_dist, float* d_zbuf,
+                        int64_t* report, void* stream);
+int r3g_softras_backward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, const int32_t* d_tri, int64_t n_faces, int height, int width,
+                         int K, double sigma, double blur_radius, const int32_t* d_face, const float* d_dist, const float* d_grad_alpha,
+                         const int32_t* d_corner_start, const int32_t* d_corner_ids, float* d_grad_face, float* d_grad_pos,
+                         int64_t* report, void* stream);
+int r3g_softras_times(r3g_ctx* ctx, double* ms);
+
 /* ---- point clouds: Poisson surface on a uniform lattice -----------------------------------------
  * Oriented points -> an implicit function chi whose level set is the surface (r3g/recon.py runs marching cubes on it).  The
  * lattice has n = 2^depth + 1 nodes per axis over the cube (centre, side), node (i0, i1, i2) stored [i0][i1][i2].  Every value is
