@@ -1,30 +1,18 @@
-"""ctypes loader for tests/emu/cloud_emu.cpp (host run of csrc/cloud_core.h; test-only)."""
+"""ctypes loader for tests/emu/cloud_emu.cpp (host run of the product's cloud core; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_CSRC = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-_SRC = os.path.join(_HERE, "cloud_emu.cpp")
-_DEPS = [_SRC] + [os.path.join(_CSRC, h) for h in ("cloud_core.h", "meshdist_core.h", "grid_csr.h")]
+import emu_build
+
 _LIB = None
 _I64P = ctypes.POINTER(ctypes.c_int64)
-
-
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in _DEPS)
 
 
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_cloud_emu.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w", "-I" + _CSRC, "-o", so, _SRC])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("cloud"))
         lib.r3g_emu_cloud_brute.restype = ctypes.c_int
         lib.r3g_emu_cloud_brute.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
                                             ctypes.c_void_p, ctypes.c_void_p, _I64P]
@@ -71,9 +59,4 @@ def auto_resolution(n_usable, per_cell=0):
 
 def selftest_binary(sanitize=True):
     """the twin with its own main(), as a stand-alone program (host only; -fsanitize=address,undefined) -> path"""
-    exe = os.path.join(_HERE, "cloud_selftest")
-    if _stale(exe):
-        flags = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-w", "-DCLOUD_EMU_MAIN", "-I" + _CSRC] + flags +
-                              ["-o", exe, _SRC])
-    return exe
+    return emu_build.program("cloud", defines=("CLOUD_EMU_MAIN",), sanitize=sanitize)

@@ -1,32 +1,20 @@
-"""ctypes loader for tests/emu/dbscan_emu.cpp (host run of csrc/dbscan_core.h; test-only)."""
+"""ctypes loader for tests/emu/dbscan_emu.cpp (host run of the product's dbscan core; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_CSRC = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-_SRC = os.path.join(_HERE, "dbscan_emu.cpp")
-_DEPS = [_SRC] + [os.path.join(_CSRC, h) for h in ("dbscan_core.h", "cloud_core.h", "meshdist_core.h", "grid_csr.h")]
+import emu_build
+
 _LIB = None
 _I64P = ctypes.POINTER(ctypes.c_int64)
 MUTANTS = {"strict_less": 1, "float32_d2": 2, "not_itself": 3, "border_max": 4, "first_appearance": 5}
 REPORT = ("n_usable", "n_core", "n_border", "n_noise", "n_clusters", "largest", "largest_size")
 
 
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in _DEPS)
-
-
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_dbscan_emu.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w", "-I" + _CSRC, "-o", so, _SRC])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("dbscan"))
         lib.r3g_emu_dbscan.restype = ctypes.c_int
         lib.r3g_emu_dbscan.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double] + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 3 + [_I64P, _I64P]
         lib.r3g_emu_dbscan_auto_resolution.restype = ctypes.c_int
@@ -66,9 +54,4 @@ def auto_resolution(lo, hi, eps, n_usable):
 
 def selftest_binary(sanitize=True):
     """the twin with its own main(), as a stand-alone program (host only; -fsanitize=address,undefined) -> path"""
-    exe = os.path.join(_HERE, "dbscan_selftest")
-    if _stale(exe):
-        flags = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-w", "-DDBSCAN_EMU_MAIN", "-I" + _CSRC] + flags +
-                              ["-o", exe, _SRC])
-    return exe
+    return emu_build.program("dbscan", defines=("DBSCAN_EMU_MAIN",), sanitize=sanitize)

@@ -1,25 +1,17 @@
-"""ctypes loader for tests/emu/dmc_emu.cpp (host emulation of the HIP dual-marching-cubes launch structure; test-only)."""
+"""ctypes loader for tests/emu/dmc_emu.cpp (host emulation of the HIP dual-marching-cubes launch structure; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_CSRC = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
+import emu_build
+
 _LIB = None
 
 
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_dmc_emu.so")
-        deps = [os.path.join(_HERE, "dmc_emu.cpp")] + [os.path.join(_CSRC, h) for h in ("dmc_cell.h", "dmc_luts.h", "surf_common.h")]
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
-                                   "-I" + _CSRC, "-o", so, deps[0]])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("dmc"))
         lib.r3g_emu_dmc.restype = ctypes.c_int
         lib.r3g_emu_dmc.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_int,

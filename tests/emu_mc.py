@@ -1,25 +1,17 @@
-"""ctypes loader for tests/emu/mc_emu.cpp (host emulation of the HIP launch structure; test-only)."""
+"""ctypes loader for tests/emu/mc_emu.cpp (host emulation of the HIP launch structure; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
+import emu_build
+
 _LIB = None
 
 
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_emu.so")
-        csrc = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-        deps = [os.path.join(_HERE, "mc_emu.cpp")] + [os.path.join(csrc, h) for h in ("mc_cell.h", "mc_luts.h", "surf_common.h")]
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
-                                   "-I" + csrc, "-o", so, deps[0]])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("mc"))
         lib.r3g_emu_mc.restype = ctypes.c_int
         lib.r3g_emu_mc.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_int,

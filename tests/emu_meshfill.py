@@ -1,13 +1,11 @@
-"""ctypes loader for tests/emu/meshfill_emu.cpp (host run of csrc/meshfill_core.h over the mate table of
-tests/emu/meshtopo_emu.cpp; test-only)."""
+"""ctypes loader for tests/emu/meshfill_emu.cpp (host run of the product's meshfill core over the mate table of
+tests/emu/meshtopo_emu.cpp; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
+import emu_build
+
 _LIB = None
 
 REPORT_FIELDS = ("boundary", "loops", "tangled", "filled", "oversize", "longest", "loop_edges", "faces_added", "verts_added",
@@ -18,14 +16,7 @@ MODES = {"fan": 0, "centroid": 1}
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_meshfill_emu.so")
-        srcs = [os.path.join(_HERE, "meshfill_emu.cpp"), os.path.join(_HERE, "meshtopo_emu.cpp")]
-        csrc = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-        deps = srcs + [os.path.join(csrc, "meshfill_core.h"), os.path.join(csrc, "meshtopo_core.h")]
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
-                                   "-I" + csrc, "-o", so] + srcs)
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("meshfill"))
         lib.r3g_emu_meshfill_plan.restype = ctypes.c_int
         lib.r3g_emu_meshfill_plan.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p]

@@ -1,12 +1,10 @@
-"""ctypes loader for tests/emu/meshfit_emu.cpp (host run of csrc/meshdist_core.h and csrc/meshfit_core.h; test-only)."""
+"""ctypes loader for tests/emu/meshfit_emu.cpp (host run of the product's meshdist and meshfit cores; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
+import emu_build
+
 _LIB = None
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -21,15 +19,7 @@ IDENTITY = np.array([1.0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0])
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_meshfit_emu.so")
-        src = os.path.join(_HERE, "meshfit_emu.cpp")
-        csrc = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-        deps = [src, os.path.join(csrc, "meshdist_core.h"), os.path.join(csrc, "meshfit_core.h"), os.path.join(csrc, "grid_csr.h"),
-                os.path.join(_HERE, "host_grid.h"), os.path.join(_HERE, "meshdist_host.h")]
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
-                                   "-I" + csrc, "-o", so, src])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("meshfit"))
         lib.r3g_emu_mf_tri_closest.restype = None
         lib.r3g_emu_mf_tri_closest.argtypes = [_P, _P, _L, _P, _P, _P]
         lib.r3g_emu_mf_closest.restype = _I

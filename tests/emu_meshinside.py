@@ -1,12 +1,10 @@
-"""ctypes loader for tests/emu/meshinside_emu.cpp (host run of csrc/meshinside_core.h; test-only)."""
+"""ctypes loader for tests/emu/meshinside_emu.cpp (host run of the product's meshinside core; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
+import emu_build
+
 _LIB = None
 _I64P = ctypes.POINTER(ctypes.c_int64)
 
@@ -14,14 +12,7 @@ _I64P = ctypes.POINTER(ctypes.c_int64)
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_meshinside_emu.so")
-        src = os.path.join(_HERE, "meshinside_emu.cpp")
-        csrc = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-        deps = [src, os.path.join(csrc, "meshinside_core.h"), os.path.join(csrc, "grid_csr.h"), os.path.join(_HERE, "host_grid.h")]
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
-                                   "-I" + csrc, "-o", so, src])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("meshinside"))
         lib.r3g_emu_meshinside_brute.restype = ctypes.c_int
         lib.r3g_emu_meshinside_brute.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _I64P]

@@ -1,33 +1,20 @@
-"""ctypes loader for tests/emu/orient_emu.cpp (host run of csrc/orient_core.h; test-only).  The (k + 1)-rows come from the
+"""ctypes loader for tests/emu/orient_emu.cpp (host run of the product's orient core; test-only; built by tests/emu_build.py).  The (k + 1)-rows come from the
 cloud twin (tests/emu_cloud.py), as the product takes them from r3g_cloud_knn."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 import emu_cloud
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_CSRC = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-_SRC = os.path.join(_HERE, "orient_emu.cpp")
-_DEPS = [_SRC] + [os.path.join(_CSRC, h) for h in ("orient_core.h", "recon_core.h")]
 _LIB = None
 REPORT_FIELDS = ("usable", "trees", "flipped", "rounds", "frustrated")
-
-
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in _DEPS)
 
 
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_orient_emu.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w", "-I" + _CSRC, "-o", so, _SRC])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("orient"))
         lib.r3g_emu_orient.restype = ctypes.c_int
         lib.r3g_emu_orient.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -65,9 +52,4 @@ def orient(points, normals, k, reverse=False):
 
 def selftest_binary(sanitize=True):
     """the twin with its own main(), as a stand-alone program (host only; -fsanitize=address,undefined) -> path"""
-    exe = os.path.join(_HERE, "orient_selftest")
-    if _stale(exe):
-        flags = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-w", "-DORIENT_EMU_MAIN", "-I" + _CSRC] + flags +
-                              ["-o", exe, _SRC])
-    return exe
+    return emu_build.program("orient", defines=("ORIENT_EMU_MAIN",), sanitize=sanitize)

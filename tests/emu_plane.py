@@ -1,15 +1,10 @@
-"""ctypes loader for tests/emu/plane_emu.cpp (host run of csrc/plane_core.h; test-only)."""
+"""ctypes loader for tests/emu/plane_emu.cpp (host run of the product's plane core; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_CSRC = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-_SRC = os.path.join(_HERE, "plane_emu.cpp")
-_DEPS = [_SRC, os.path.join(_CSRC, "plane_core.h")]
+import emu_build
+
 _LIB = None
 _I64P = ctypes.POINTER(ctypes.c_int64)
 _DP = ctypes.POINTER(ctypes.c_double)
@@ -18,17 +13,10 @@ REPORT = ("n_usable", "n_valid", "best", "best_count", "few")
 MOMENTS_REPORT = ("n", "skipped", "few")
 
 
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in _DEPS)
-
-
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_plane_emu.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w", "-I" + _CSRC, "-o", so, _SRC])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("plane"))
         lib.r3g_emu_plane_ransac.restype = ctypes.c_int
         lib.r3g_emu_plane_ransac.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, _I64P, _DP]
@@ -82,9 +70,4 @@ def moments(points, mask=None):
 
 def selftest_binary(sanitize=True):
     """the twin with its own main(), as a stand-alone program (host only; -fsanitize=address,undefined) -> path"""
-    exe = os.path.join(_HERE, "plane_selftest")
-    if _stale(exe):
-        flags = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-w", "-DPLANE_EMU_MAIN", "-I" + _CSRC] + flags +
-                              ["-o", exe, _SRC])
-    return exe
+    return emu_build.program("plane", defines=("PLANE_EMU_MAIN",), sanitize=sanitize)

@@ -1,26 +1,17 @@
-"""ctypes loader for tests/emu/qem_emu.cpp (host run of the product's edge-collapse bodies; test-only)."""
+"""ctypes loader for tests/emu/qem_emu.cpp (host run of the product's edge-collapse bodies; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
+import emu_build
+
 _LIB = None
 
 
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_qem_emu.so")
-        src = os.path.join(_HERE, "qem_emu.cpp")
-        csrc = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-        deps = [src, os.path.join(csrc, "qem_core.h"), os.path.join(csrc, "qem_driver.h")]
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
-                                   "-I" + csrc, "-o", so, src])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("qem"))
         lib.r3g_emu_qem.restype = ctypes.c_int
         lib.r3g_emu_qem.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
                                     ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.POINTER(ctypes.c_int)]

@@ -1,32 +1,20 @@
-"""ctypes loader for tests/emu/recon_emu.cpp (host run of csrc/recon_core.h; test-only)."""
+"""ctypes loader for tests/emu/recon_emu.cpp (host run of the product's recon core; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_CSRC = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-_SRC = os.path.join(_HERE, "recon_emu.cpp")
-_DEPS = [_SRC, os.path.join(_CSRC, "recon_core.h")]
+import emu_build
+
 _LIB = None
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 FIXED = 2.0 ** 30
 
 
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in _DEPS)
-
-
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_recon_emu.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w", "-I" + _CSRC, "-o", so, _SRC])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("recon"))
         lib.r3g_emu_recon_splat.restype = _I64
         lib.r3g_emu_recon_splat.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_double, ctypes.c_int, _P]
         lib.r3g_emu_recon_rhs.restype = ctypes.c_int
@@ -100,9 +88,4 @@ def sample(field, depth, centre, side, points, normals=None, reverse=False):
 
 def selftest_binary(sanitize=True):
     """the twin with its own main(), as a stand-alone program (host only; -fsanitize=address,undefined) -> path"""
-    exe = os.path.join(_HERE, "recon_selftest")
-    if _stale(exe):
-        flags = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-w", "-DRECON_EMU_MAIN", "-I" + _CSRC] + flags +
-                              ["-o", exe, _SRC])
-    return exe
+    return emu_build.program("recon", defines=("RECON_EMU_MAIN",), sanitize=sanitize)

@@ -1,15 +1,10 @@
-"""ctypes loader for tests/emu/softras_emu.cpp (host run of csrc/softras_core.h; test-only)."""
+"""ctypes loader for tests/emu/softras_emu.cpp (host run of the product's softras core; test-only; built by tests/emu_build.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_CSRC = os.path.join(_ROOT, "3d-re-gen_amd", "csrc")
-_SRC = os.path.join(_HERE, "softras_emu.cpp")
-_DEPS = [_SRC, os.path.join(_CSRC, "softras_core.h")]
+import emu_build
+
 _LIB = None
 _I64P = ctypes.POINTER(ctypes.c_int64)
 _P, _I, _F, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
@@ -18,17 +13,10 @@ REPORT = ("pairs", "used", "skipped", "tiles")
 BACK_REPORT = ("found",)
 
 
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in _DEPS)
-
-
 def _lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, "libr3g_softras_emu.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w", "-I" + _CSRC, "-o", so, _SRC])
-        lib = ctypes.CDLL(so)
+        lib = ctypes.CDLL(emu_build.shared("softras"))
         lib.r3g_emu_softras_forward.restype = _I
         lib.r3g_emu_softras_forward.argtypes = [_P, _L, _P, _L, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _I64P]
         lib.r3g_emu_softras_backward.restype = _I
@@ -98,9 +86,4 @@ def backward(pos, tri, size, K, sigma, blur_radius, face, dist, grad_alpha, muta
 
 def selftest_binary(sanitize=True):
     """the twin with its own main(), as a stand-alone program (host only; -fsanitize=address,undefined) -> path"""
-    exe = os.path.join(_HERE, "softras_selftest")
-    if _stale(exe):
-        flags = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-w", "-DSOFTRAS_EMU_MAIN", "-I" + _CSRC] + flags +
-                              ["-o", exe, _SRC])
-    return exe
+    return emu_build.program("softras", defines=("SOFTRAS_EMU_MAIN",), sanitize=sanitize)

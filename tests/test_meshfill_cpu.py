@@ -1,18 +1,17 @@
 """Hole filling without a GPU: the host twin of csrc/meshfill_core.h (tests/emu_meshfill.py) against the
 numpy / Python restatement (tests/meshfill_ref.py), plus literals that depend on neither: restored faces, exact centroids,
 watertightness and Euler numbers of the results."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import emu_meshfill as emu
 import emu_meshtopo as temu
 import meshfill_ref as ref
 import meshtopo_ref as tref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARRAYS = ("loop_start", "loop_verts", "status", "new_faces")
 _CACHE = {}
 
@@ -221,11 +220,7 @@ def test_surface_exists_without_a_gpu():
 
 def test_standalone_program_runs_the_core_header():
     """tests/emu/meshfill_selftest.cpp: its own main over the twin, built and run as a plain program (no sanitizer here)"""
-    emu_dir = os.path.join(ROOT, "tests", "emu")
-    exe = os.path.join(emu_dir, "meshfill_selftest")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "3d-re-gen_amd", "csrc"),
-                           "-o", exe, os.path.join(emu_dir, "meshfill_selftest.cpp"), os.path.join(emu_dir, "meshfill_emu.cpp"),
-                           os.path.join(emu_dir, "meshtopo_emu.cpp")])
+    exe = emu_build.program("meshfill", ["meshfill_selftest.cpp"] + emu_build.TWINS["meshfill"])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "meshfill selftest ok" in out.stdout

@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import emu_build
 import emu_meshtopo as emu
 import meshtopo_ref as ref
 
@@ -293,10 +294,7 @@ def test_api_surface_is_declared():
 
 def test_standalone_program_runs_the_core_header():
     """tests/emu/meshtopo_selftest.cpp: its own main over the twin (cube and Moebius strip), built and run as a plain program"""
-    emu_dir = os.path.join(ROOT, "tests", "emu")
-    exe = os.path.join(emu_dir, "meshtopo_selftest")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "3d-re-gen_amd", "csrc"),
-                           "-o", exe, os.path.join(emu_dir, "meshtopo_selftest.cpp"), os.path.join(emu_dir, "meshtopo_emu.cpp")])
+    exe = emu_build.program("meshtopo", ["meshtopo_selftest.cpp"] + emu_build.TWINS["meshtopo"])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "meshtopo selftest ok" in out.stdout

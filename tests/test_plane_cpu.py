@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import emu_build
 import emu_plane as E
 import plane_ref as R
 
@@ -170,13 +171,10 @@ def test_frame_and_box_definitions():
     assert abs(abs(rot[0, 0]) - np.cos(0.6)) < 0.02 and np.allclose(rot[1], [0, 1, 0])
 
 
-def test_selftest_program_under_sanitizers(tmp_path):
+def test_selftest_program_under_sanitizers():
     """the twin with its own main(), built as a stand-alone program with -fsanitize=address,undefined (runtimes linked
     statically), on a lattice whose layers tie with the threshold; never loaded into Python"""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan"]
-    if subprocess.run(["g++"] + flags + ["-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode != 0:
+    if not emu_build.sanitizers_link():
         pytest.skip("no sanitizer runtime for g++ on this machine")
     # (a compile error of the twin's program is a failure, not a skip: the probe above has shown that the sanitizers link)
     exe = E.selftest_binary(sanitize=True)

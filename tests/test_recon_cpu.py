@@ -12,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "3d-re-gen_amd"))
 
+import emu_build
 import emu_dmc
 import emu_mc
 import emu_recon as emu
@@ -310,5 +311,7 @@ def test_point_cloud_normals_and_to_mesh(monkeypatch):
 
 
 def test_twin_as_a_stand_alone_sanitizer_build():
+    if not emu_build.sanitizers_link():
+        pytest.skip("no sanitizer runtime for g++ on this machine")
     out = subprocess.run([emu.selftest_binary()], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "ok" in out.stdout and "runtime error" not in out.stderr, out.stdout + out.stderr
