@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "dbscan_core.h"
+#include "events.h"
 
 namespace r3g {
 
@@ -36,9 +37,9 @@ size_t dbscan_workspace_bytes(int64_t n, DbscanLayout* lay);
 // label[i] = -1, count[i] = 0 (where given), no core, no root; DbscanSmall cleared.  One launch.
 hipError_t dbscan_begin(char* ws, const DbscanLayout& lay, int64_t n, int32_t* label, uint32_t* count, hipStream_t s);
 // The four passes over the m usable points `sorted` (cell order, grid g, CSR starts).  ev: kDbscanPasses + 1 events recorded
-// around the passes, or null.  -> the number of kernels launched through *launches.
+// around the passes.  -> the number of kernels launched through *launches.
 hipError_t dbscan_run(char* ws, const DbscanLayout& lay, const r3g_cl::Grid& g, const r3g_cl::Pt* sorted, const unsigned* starts,
-                      int64_t m, int64_t n, double eps, uint32_t min_samples, int32_t* label, uint32_t* count, hipEvent_t* ev,
+                      int64_t m, int64_t n, double eps, uint32_t min_samples, int32_t* label, uint32_t* count, const Event* ev,
                       int* launches, hipStream_t s);
 
 }  // namespace r3g

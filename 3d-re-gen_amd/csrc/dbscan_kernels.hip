@@ -167,7 +167,7 @@ hipError_t dbscan_begin(char* ws, const DbscanLayout& lay, int64_t n, int32_t* l
 }
 
 hipError_t dbscan_run(char* ws, const DbscanLayout& lay, const Grid& g, const Pt* sorted, const unsigned* starts, int64_t m, int64_t n,
-                      double eps, uint32_t min_samples, int32_t* label, uint32_t* count, hipEvent_t* ev, int* launches, hipStream_t s) {
+                      double eps, uint32_t min_samples, int32_t* label, uint32_t* count, const Event* ev, int* launches, hipStream_t s) {
     const dim3 gm(nblocks(m, kT)), gn(nblocks(n, kT)), b(kT);
     const double eps2 = eps * eps;
     uint8_t* core = at<uint8_t>(ws, lay.off_core);
@@ -176,7 +176,7 @@ hipError_t dbscan_run(char* ws, const DbscanLayout& lay, const Grid& g, const Pt
     uint32_t* size = at<uint32_t>(ws, lay.off_size);
     DbscanSmall* sm = at<DbscanSmall>(ws, lay.off_small);
     int pass = 0;
-    auto mark = [&]() -> hipError_t { return ev ? hipEventRecord(ev[pass++], s) : hipSuccess; };
+    auto mark = [&] { return hipEventRecord(ev[pass++], s); };
     R3G_HIP(mark());
     if (count)
         hipLaunchKernelGGL((db_count<true>), gm, b, 0, s, g, sorted, starts, m, eps, eps2, min_samples, count, core, root, sm);

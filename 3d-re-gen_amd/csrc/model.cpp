@@ -176,9 +176,10 @@ struct Model {
     int n_mod_jobs = 0;
     DevBuf mod_all;                     // f32 [job][B][N]
     std::vector<int64_t> mod_off;       // per job offset into mod_all
-    // second stream: the MLP half of a single block's linear1 runs beside the attention kernel (see dit_forward_grouped)
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // second stream: the MLP half of a single block's linear1 runs beside the attention kernel (see dit_forward_grouped, which makes
+    // the three on first use: all of them or none)
+    Stream aux;
+    Event ev_fork, ev_join;
     // fp8 mode of the geo decoder (option geo_fp8): e4m3 copies of its weights with one scale per output row, made on
     // first use; per-row scales of the activations LayerNorm quantises; the constant scale vector of the MLP hidden
     struct W8 { DevBuf w8, sw; };                    // e4m3 [N][K], f32 [N rounded up to 64]
@@ -774,10 +775,13 @@ static int dit_forward_grouped(Model& m, const float* x_lat, float t_scalar, flo
     // change.  It paid (-1.1 %) while that GEMM ran 64 KiB workgroups that fit beside attention workgroups; the persistent
     // 256x256 kernel owns a whole CU's LDS.
     const bool overlap = g_overlap_mlp && c.dit_depth_single > 0;
-    if (overlap && !m.aux) {
-        R3G_TRY(hipStreamCreateWithFlags(&m.aux, hipStreamNonBlocking));
-        R3G_TRY(hipEventCreateWithFlags(&m.ev_fork, hipEventDisableTiming));
-        R3G_TRY(hipEventCreateWithFlags(&m.ev_join, hipEventDisableTiming));
+    if (overlap && !m.aux) {      // into locals first: a failure leaves the model without any of the three, and the next forward tries again
+        Stream aux;
+        Event fork, join;
+        R3G_TRY(aux.create(hipStreamNonBlocking));
+        R3G_TRY(fork.create(hipEventDisableTiming));
+        R3G_TRY(join.create(hipEventDisableTiming));
+        m.aux = std::move(aux), m.ev_fork = std::move(fork), m.ev_join = std::move(join);
     }
     for (int i = 0; i < c.dit_depth_single; ++i) {
         const std::string blk = fmt("model.single_blocks.%d", i);
@@ -1289,13 +1293,7 @@ static int cond_encode(Model& m, const float* img, uint16_t* out, hipStream_t s)
 }
 
 // ---- lifetime ----------------------------------------------------------------------------------------
-static void model_free(Model* m) {
-    if (!m) return;
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    if (m->ev_join) (void)hipEventDestroy(m->ev_join);
-    if (m->aux) (void)hipStreamDestroy(m->aux);
-    delete m;      // the buffers go with their DevBuf members
-}
+static void model_free(Model* m) { delete m; }      // the buffers, the stream and the events go with their members
 
 static int model_create(Ctx* ctx, const r3g_model_config* cfg) {
     if (ctx->model) { model_free((Model*)ctx->model); ctx->model = nullptr; }

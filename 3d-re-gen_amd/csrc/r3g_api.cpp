@@ -175,6 +175,41 @@ static int grid_csr_build(Ctx* c, GridCsrState<U::D>* st, const U& user, const f
     return R3G_OK;
 }
 
+// the point cloud's grid (DESIGN.md sections 4k, 4m): its resolution argument, and the one build
+static int cloud_resolution_check(const char* who, int resolution) {
+    if (resolution >= 0 && resolution <= r3g_cl::kMaxRes) return R3G_OK;
+    return fail(R3G_ERR_INVALID, "%s: resolution outside [0, %d] (0 = automatic)", who, r3g_cl::kMaxRes);
+}
+
+// The grid of c->cloud for r3g_cloud_build and r3g_cloud_dbscan: workspace for the most cells, before(), records, read-back (under
+// `name`), box, resolution, grid, points reserve, fill.  The automatic resolution is choose(lo, hi, usable) and at most res_most: it
+// can only fall when points are skipped, so the workspace sized for all of them is enough.  before() is DBSCAN's first event and
+// launch, queued directly in front of the records (the event's interval holds no host work but the launches).  -> *skipped; when
+// that is every point, nothing past the read-back has run and what it means is the caller's to say.  The caller has checked its
+// arguments and cleared c->cloud.built, and sets it behind a sync of its own.
+template <class Choose, class Before>
+static int cloud_grid_build(Ctx* c, const char* name, const float* d_points, int64_t n_points, int resolution, int res_most, Choose choose,
+                            Before before, int64_t* skipped, hipStream_t s) {
+    GridCsrState<3>* st = &c->cloud;
+    const size_t need = grid_csr_workspace_bytes(n_points, sizeof(r3g_cl::Pt), r3g_grid::cells<3>(resolution ? resolution : res_most), &st->lay);
+    const GridCsrLayout& lay = st->lay;
+    int rc = st->ws.grow(need, s, "cloud workspace");
+    if (rc || (rc = before())) return rc;
+    hipError_t e = cloud_records(st->ws.p, lay, d_points, n_points, s);
+    if (e != hipSuccess) return hip_fail(e, "cloud_records");
+    GridCsrSmall sm;
+    if ((rc = grid_small(c, st->ws.p, lay, name, s, &sm))) return rc;
+    *skipped = (int64_t)sm.skipped;
+    const int64_t usable = n_points - *skipped;
+    if (usable <= 0) return R3G_OK;
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) lo[a] = r3g_grid::dec_float(sm.box[a]), hi[a] = r3g_grid::dec_float(sm.box[3 + a]);
+    st->grid = r3g_grid::make_grid(lo, hi, resolution ? resolution : choose(lo, hi, usable));
+    if ((rc = st->pairs.grow(sizeof(r3g_cl::Pt) * (size_t)usable, s, "cloud points"))) return rc;
+    e = cloud_fill(st->ws.p, lay, n_points, st->grid, st->pairs.as<r3g_cl::Pt>(), s);
+    return e == hipSuccess ? R3G_OK : hip_fail(e, "cloud_fill");
+}
+
 // ---- surface extractors: marching cubes and dual marching cubes (one count and one emit driver) -----------------------------
 // what the drivers need to know of their extractor
 struct McExtract {
@@ -283,16 +318,10 @@ int r3g_create(int device, r3g_ctx** out) {
 void r3g_destroy(r3g_ctx* ctx) {
     if (!ctx) return;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    (void)hipSetDevice(c->device);      // before anything is freed: the buffers below belong to this device
-    if (c->dbscan_ev_made)
-        for (hipEvent_t e : c->dbscan_ev) (void)hipEventDestroy(e);
-    if (c->plane_ev_made)
-        for (hipEvent_t e : c->plane_ev) (void)hipEventDestroy(e);
-    if (c->softras_ev_made)
-        for (hipEvent_t e : c->softras_ev) (void)hipEventDestroy(e);
+    (void)hipSetDevice(c->device);      // before anything is freed: the buffers and events below belong to this device
     c->release_model();
     c->release_unet();
-    delete c;                           // every buffer of the context goes with its DevBuf member
+    delete c;                           // every buffer and event of the context goes with its DevBuf or PassTimer member
 }
 
 int r3g_mc_count(r3g_ctx* ctx, const float* d_grid, int n0, int n1, int n2, double level, int use_classic,
@@ -427,46 +456,27 @@ int r3g_meshdist_query(r3g_ctx* ctx, const float* d_points, int64_t n_points, fl
     return R3G_OK;
 }
 
-// ---- mesh registration ------------------------------------------------------------------------
 // ---- point clouds ----------------------------------------------------------------------------------------
 int r3g_cloud_build(r3g_ctx* ctx, const float* d_points, int64_t n_points, int resolution, int* resolution_out, int64_t* skipped_out,
                     void* stream) {
     if (!ctx) return fail(R3G_ERR_INVALID, "r3g_cloud_build: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    GridCsrState<3>* st = &c->cloud;
     hipStream_t s = (hipStream_t)stream;
-    st->built = false;
+    c->cloud.built = false;
     if (n_points <= 0 || n_points > 0x7fffffffll) return fail(R3G_ERR_INVALID, "r3g_cloud_build: n_points outside [1, 2^31 - 1]");
     if (!d_points) return fail(R3G_ERR_INVALID, "r3g_cloud_build: null buffer");
-    if (resolution < 0 || resolution > r3g_cl::kMaxRes)
-        return fail(R3G_ERR_INVALID, "r3g_cloud_build: resolution outside [0, %d] (0 = automatic)", r3g_cl::kMaxRes);
-    // the automatic resolution can only fall when points are skipped: the workspace sized for all of them is enough
-    const int res_most = resolution ? resolution : r3g_cl::auto_resolution(n_points, r3g_cl::kPointsPerCell);
-    GridCsrLayout lay;
-    const size_t need = grid_csr_workspace_bytes(n_points, sizeof(r3g_cl::Pt), r3g_grid::cells<3>(res_most), &lay);
-    int rc = st->ws.grow(need, s, "cloud workspace");
-    if (rc) return rc;
-    st->lay = lay;
-    hipError_t e = cloud_records(st->ws.p, lay, d_points, n_points, s);
-    if (e != hipSuccess) return hip_fail(e, "cloud_records");
-    GridCsrSmall sm;
-    if ((rc = grid_small(c, st->ws.p, lay, "cloud", s, &sm))) return rc;
-    if ((int64_t)sm.skipped >= n_points)
-        return fail(R3G_ERR_INVALID, "r3g_cloud_build: every point has a non-finite coordinate (%lld skipped)", (long long)sm.skipped);
-    const int64_t usable = n_points - (int64_t)sm.skipped;
-    float lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) lo[a] = r3g_grid::dec_float(sm.box[a]), hi[a] = r3g_grid::dec_float(sm.box[3 + a]);
-    const int res = resolution ? resolution : r3g_cl::auto_resolution(usable, r3g_cl::kPointsPerCell);
-    const r3g_cl::Grid g = r3g_grid::make_grid(lo, hi, res);
-    if ((rc = st->pairs.grow(sizeof(r3g_cl::Pt) * (size_t)usable, s, "cloud points"))) return rc;
-    e = cloud_fill(st->ws.p, lay, n_points, g, st->pairs.as<r3g_cl::Pt>(), s);
-    if (e != hipSuccess) return hip_fail(e, "cloud_fill");
-    e = hipStreamSynchronize(s);      // the caller may free its points, and a fault would surface here
+    if (const int rc = cloud_resolution_check("r3g_cloud_build", resolution)) return rc;
+    auto res = [](int64_t n) { return r3g_cl::auto_resolution(n, r3g_cl::kPointsPerCell); };
+    int64_t skipped = 0;
+    auto choose = [&](const float*, const float*, int64_t usable) { return res(usable); };
+    if (const int rc = cloud_grid_build(c, "cloud", d_points, n_points, resolution, res(n_points), choose, [] { return 0; }, &skipped, s)) return rc;
+    if (skipped >= n_points)
+        return fail(R3G_ERR_INVALID, "r3g_cloud_build: every point has a non-finite coordinate (%lld skipped)", (long long)skipped);
+    hipError_t e = hipStreamSynchronize(s);      // the caller may free its points, and a fault would surface here
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(cloud_fill)");
-    st->grid = g;
-    st->built = true;
-    if (resolution_out) *resolution_out = g.res;
-    if (skipped_out) *skipped_out = (int64_t)sm.skipped;
+    c->cloud.built = true;
+    if (resolution_out) *resolution_out = c->cloud.grid.res;
+    if (skipped_out) *skipped_out = skipped;
     return R3G_OK;
 }
 
@@ -497,8 +507,7 @@ int r3g_cloud_orient(r3g_ctx* ctx, const float* d_points, const float* d_normals
     hipStream_t s = (hipStream_t)stream;
     if (n_points <= 0 || n_points > 0x7fffffffll) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: n_points outside [1, 2^31 - 1]");
     if (k < r3g_or::kMinK || k > r3g_or::kMaxK) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: k outside [%d, %d]", r3g_or::kMinK, r3g_or::kMaxK);
-    if (resolution < 0 || resolution > r3g_cl::kMaxRes)
-        return fail(R3G_ERR_INVALID, "r3g_cloud_orient: resolution outside [0, %d] (0 = automatic)", r3g_cl::kMaxRes);
+    if (const int rc = cloud_resolution_check("r3g_cloud_orient", resolution)) return rc;
     if (!d_points || !d_normals || !d_sign || !d_tree) return fail(R3G_ERR_INVALID, "r3g_cloud_orient: null buffer");
     OrientLayout lay;
     int rc = c->orient_ws.grow(orient_workspace_bytes(n_points, k, &lay), s, "orient workspace");
@@ -544,8 +553,8 @@ int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, doub
     if (!(eps > 0.0) || !(eps - eps == 0.0)) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: eps must be finite and > 0");
     if (min_samples < 1) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: min_samples must be >= 1");
     if (n_points < 0 || n_points >= (1ll << 31)) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: n_points outside [0, 2^31 - 1]");
-    if (resolution < 0 || resolution > r3g_cl::kMaxRes)
-        return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: resolution outside [0, %d] (0 = automatic)", r3g_cl::kMaxRes);
+    int rc = cloud_resolution_check("r3g_cloud_dbscan", resolution);
+    if (rc) return rc;
     int64_t rep[r3g_db::kReport] = {0, 0, 0, 0, 0, -1, 0, 0};
     auto done = [&]() {
         if (report) memcpy(report, rep, sizeof rep);
@@ -555,51 +564,35 @@ int r3g_cloud_dbscan(r3g_ctx* ctx, const float* d_points, int64_t n_points, doub
     c->dbscan_timed = false;
     if (n_points == 0) return done();
     if (!d_points || !d_label) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan: null buffer");
-    if (!c->dbscan_ev_made) {
-        for (hipEvent_t& e : c->dbscan_ev) {
-            hipError_t he = hipEventCreate(&e);
-            if (he != hipSuccess) return hip_fail(he, "hipEventCreate(dbscan)");
-        }
-        c->dbscan_ev_made = true;
-    }
+    if ((rc = c->dbscan_ev.make("dbscan"))) return rc;
     DbscanLayout dl;
-    int rc = c->dbscan_ws.grow(dbscan_workspace_bytes(n_points, &dl), s, "dbscan workspace");
+    if ((rc = c->dbscan_ws.grow(dbscan_workspace_bytes(n_points, &dl), s, "dbscan workspace"))) return rc;
+    hipError_t e;
+    auto begin = [&]() -> int {
+        if (const int r = c->dbscan_ev.mark(0, s)) return r;
+        e = dbscan_begin(c->dbscan_ws.p, dl, n_points, d_label, d_count, s);
+        return e == hipSuccess ? R3G_OK : hip_fail(e, "dbscan_begin");
+    };
+    auto choose = [&](const float* lo, const float* hi, int64_t usable) { return r3g_db::auto_resolution(lo, hi, eps, usable); };
+    int64_t skipped = 0;
+    rc = cloud_grid_build(c, "dbscan", d_points, n_points, resolution, r3g_db::auto_resolution_most(n_points), choose, begin, &skipped, s);
     if (rc) return rc;
-    // the automatic resolution can only fall when points are skipped: the workspace sized for all of them is enough
-    const int res_most = resolution ? resolution : r3g_db::auto_resolution_most(n_points);
-    GridCsrLayout lay;
-    const size_t need = grid_csr_workspace_bytes(n_points, sizeof(r3g_cl::Pt), r3g_grid::cells<3>(res_most), &lay);
-    if ((rc = st->ws.grow(need, s, "cloud workspace"))) return rc;
-    st->lay = lay;
-    int64_t launches = 0;
-    hipError_t e = hipEventRecord(c->dbscan_ev[0], s);
-    if (e != hipSuccess) return hip_fail(e, "hipEventRecord(dbscan)");
-    if ((e = dbscan_begin(c->dbscan_ws.p, dl, n_points, d_label, d_count, s)) != hipSuccess) return hip_fail(e, "dbscan_begin");
-    if ((e = cloud_records(st->ws.p, lay, d_points, n_points, s)) != hipSuccess) return hip_fail(e, "cloud_records");
-    launches += 2;
-    GridCsrSmall sm;
-    if ((rc = grid_small(c, st->ws.p, lay, "dbscan", s, &sm))) return rc;
-    const int64_t usable = n_points - (int64_t)sm.skipped;
+    int64_t launches = 2;           // begin, records
+    const int64_t usable = n_points - skipped;
     if (usable <= 0) {              // nothing to cluster: every label is -1 already
         counter_add(LC_DBSCAN_LAUNCHES, launches);
         return done();
     }
-    float lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) lo[a] = r3g_grid::dec_float(sm.box[a]), hi[a] = r3g_grid::dec_float(sm.box[3 + a]);
-    const int res = resolution ? resolution : r3g_db::auto_resolution(lo, hi, eps, usable);
-    const r3g_cl::Grid g = r3g_grid::make_grid(lo, hi, res);
-    if ((rc = st->pairs.grow(sizeof(r3g_cl::Pt) * (size_t)usable, s, "cloud points"))) return rc;
-    if ((e = cloud_fill(st->ws.p, lay, n_points, g, st->pairs.as<r3g_cl::Pt>(), s)) != hipSuccess) return hip_fail(e, "cloud_fill");
     launches += 5;                  // count, the scan's three, fill
+    const r3g_cl::Grid& g = st->grid;
     int run = 0;
-    e = dbscan_run(c->dbscan_ws.p, dl, g, st->pairs.as<const r3g_cl::Pt>(), (const unsigned*)(st->ws.p + lay.off_starts), usable, n_points, eps,
-                   (uint32_t)min_samples, d_label, d_count, c->dbscan_ev + 1, &run, s);
+    e = dbscan_run(c->dbscan_ws.p, dl, g, st->pairs.as<const r3g_cl::Pt>(), (const unsigned*)(st->ws.p + st->lay.off_starts), usable, n_points, eps,
+                   (uint32_t)min_samples, d_label, d_count, c->dbscan_ev.ev + 1, &run, s);
     if (e != hipSuccess) return hip_fail(e, "dbscan_run");
     launches += run;
     static_assert(sizeof(DbscanSmall) <= 64, "the pinned read-back buffer");
     DbscanSmall ds;      // (its sync: the caller may free its points, and a fault would surface here)
     if ((rc = read_back(c->h_small, c->dbscan_ws.p + dl.off_small, &ds, sizeof ds, "dbscan", s))) return rc;
-    st->grid = g;
     st->built = true;
     c->dbscan_timed = true;
     counter_add(LC_DBSCAN_LAUNCHES, launches);
@@ -613,12 +606,8 @@ int r3g_cloud_dbscan_times(r3g_ctx* ctx, double* ms) {
     if (!ctx || !ms) return fail(R3G_ERR_INVALID, "r3g_cloud_dbscan_times: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c->dbscan_timed) return fail(R3G_ERR_STATE, "r3g_cloud_dbscan_times: no complete r3g_cloud_dbscan on this context");
-    for (int p = 0; p <= kDbscanPasses; ++p) {
-        float t = 0.0f;
-        hipError_t e = hipEventElapsedTime(&t, c->dbscan_ev[p], c->dbscan_ev[p + 1]);
-        if (e != hipSuccess) return hip_fail(e, "hipEventElapsedTime(dbscan)");
-        ms[p] = (double)t;
-    }
+    for (int p = 0; p <= kDbscanPasses; ++p)
+        if (const int rc = c->dbscan_ev.elapsed(p, &ms[p])) return rc;
     return R3G_OK;
 }
 
@@ -644,34 +633,26 @@ int r3g_plane_ransac(r3g_ctx* ctx, const float* d_points, int64_t n_points, cons
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     hipStream_t s = (hipStream_t)stream;
     c->plane_timed = false;
-    if (!c->plane_ev_made) {
-        for (int i = 0; i <= r3g_pl::kPasses; ++i) {
-            hipError_t he = hipEventCreate(&c->plane_ev[i]);
-            if (he != hipSuccess) {      // all or none: the next call starts over, and nothing made here is left behind
-                while (i-- > 0) (void)hipEventDestroy(c->plane_ev[i]);
-                return hip_fail(he, "hipEventCreate(plane)");
-            }
-        }
-        c->plane_ev_made = true;
-    }
+    auto& ev = c->plane_ev;
+    int rc = ev.make("plane");
+    if (rc) return rc;
     PlaneLayout lay;
-    if (const int rc = plane_reserve(c, n_points, n_hyp, !d_count, !d_mask, &lay, s)) return rc;
+    if ((rc = plane_reserve(c, n_points, n_hyp, !d_count, !d_mask, &lay, s))) return rc;
     char* ws = c->plane_ws.p;
     uint32_t* count = d_count ? d_count : (uint32_t*)(ws + lay.off_count);
     uint8_t* mask = d_mask ? d_mask : (uint8_t*)(ws + lay.off_mask);
-    auto mark = [&](int i) { return hipEventRecord(c->plane_ev[i], s); };
     hipError_t e;
-    if ((e = mark(0)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((rc = ev.mark(0, s))) return rc;
     if ((e = plane_table(ws, lay, d_points, n_points, d_triples, n_hyp, count, s)) != hipSuccess) return hip_fail(e, "plane_table");
-    if ((e = mark(1)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((rc = ev.mark(1, s))) return rc;
     if ((e = plane_count(ws, lay, d_points, n_points, n_hyp, threshold, count, c->num_cu, s)) != hipSuccess) return hip_fail(e, "plane_count");
-    if ((e = mark(2)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((rc = ev.mark(2, s))) return rc;
     if ((e = plane_winner(ws, lay, d_points, n_points, n_hyp, threshold, count, mask, s)) != hipSuccess) return hip_fail(e, "plane_winner");
-    if ((e = mark(3)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((rc = ev.mark(3, s))) return rc;
     if ((e = plane_moments(ws, lay, d_points, n_points, mask, s)) != hipSuccess) return hip_fail(e, "plane_moments");
-    if ((e = mark(4)) != hipSuccess) return hip_fail(e, "hipEventRecord(plane)");
+    if ((rc = ev.mark(4, s))) return rc;
     PlaneSmall sm;      // (its sync: the caller may free its buffers, and a fault would surface here)
-    if (const int rc = read_back(c->h_plane, ws + lay.off_small, &sm, sizeof sm, "plane", s)) return rc;
+    if ((rc = read_back(c->h_plane, ws + lay.off_small, &sm, sizeof sm, "plane", s))) return rc;
     c->plane_timed = true;
     int few = 0;
     double centroid[3], normal[3], val[3];
@@ -715,12 +696,8 @@ int r3g_plane_times(r3g_ctx* ctx, double* ms) {
     if (!ctx || !ms) return fail(R3G_ERR_INVALID, "r3g_plane_times: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c->plane_timed) return fail(R3G_ERR_STATE, "r3g_plane_times: no complete r3g_plane_ransac on this context");
-    for (int p = 0; p < r3g_pl::kPasses; ++p) {
-        float t = 0.0f;
-        hipError_t e = hipEventElapsedTime(&t, c->plane_ev[p], c->plane_ev[p + 1]);
-        if (e != hipSuccess) return hip_fail(e, "hipEventElapsedTime(plane)");
-        ms[p] = (double)t;
-    }
+    for (int p = 0; p < r3g_pl::kPasses; ++p)
+        if (const int rc = c->plane_ev.elapsed(p, &ms[p])) return rc;
     return R3G_OK;
 }
 
@@ -740,19 +717,6 @@ static int softras_args(const char* who, int64_t n_verts, int64_t n_faces, int h
     return R3G_OK;
 }
 
-static int softras_events(Ctx* c) {
-    if (c->softras_ev_made) return R3G_OK;
-    for (int i = 0; i < 6; ++i) {
-        hipError_t he = hipEventCreate(&c->softras_ev[i]);
-        if (he != hipSuccess) {      // all or none, as for the plane fit
-            while (i-- > 0) (void)hipEventDestroy(c->softras_ev[i]);
-            return hip_fail(he, "hipEventCreate(softras)");
-        }
-    }
-    c->softras_ev_made = true;
-    return R3G_OK;
-}
-
 int r3g_softras_forward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, const int32_t* d_tri, int64_t n_faces, int height, int width, int K,
                         double sigma, double blur_radius, float* d_alpha, int32_t* d_face, float* d_dist, float* d_zbuf, int64_t* report,
                         void* stream) {
@@ -764,12 +728,13 @@ int r3g_softras_forward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, const
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     hipStream_t s = (hipStream_t)stream;
     c->softras_fwd_timed = false;
-    if (const int rc = softras_events(c)) return rc;
+    auto& ev = c->softras_ev;
+    if (const int rc = ev.make("softras")) return rc;
     SoftrasLayout lay;
     if (const int rc = c->softras_ws.grow(softras_workspace_bytes(height, width, &lay), s, "softras workspace")) return rc;
     char* ws = c->softras_ws.p;
     hipError_t e;
-    if ((e = hipEventRecord(c->softras_ev[0], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if (const int rc = ev.mark(0, s)) return rc;
     if ((e = softras_bin_count(ws, lay, g, d_pos, n_verts, d_tri, n_faces, s)) != hipSuccess) return hip_fail(e, "softras_bin_count");
     static_assert(sizeof(SoftrasSmall) <= 64, "the pinned read-back buffer");
     SoftrasSmall sm;      // (the call's one sync: the pair list is sized from it, and it is the report)
@@ -778,11 +743,11 @@ int r3g_softras_forward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, const
     if (const int rc = c->softras_pairs.grow(4 * (size_t)sm.pairs, s, "softras pairs")) return rc;
     if ((e = softras_bin_fill(ws, lay, g, d_pos, n_verts, d_tri, n_faces, c->softras_pairs.as<int32_t>(), (unsigned)sm.pairs, s)) != hipSuccess)
         return hip_fail(e, "softras_bin_fill");
-    if ((e = hipEventRecord(c->softras_ev[1], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if (const int rc = ev.mark(1, s)) return rc;
     if ((e = softras_forward(ws, lay, g, d_pos, n_verts, d_tri, n_faces, c->softras_pairs.as<const int32_t>(), d_alpha, d_face, d_dist, d_zbuf, s)) !=
         hipSuccess)
         return hip_fail(e, "softras_forward");
-    if ((e = hipEventRecord(c->softras_ev[2], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if (const int rc = ev.mark(2, s)) return rc;
     c->softras_fwd_timed = true;
     const int64_t rep[r3g_sr::kFwdReport] = {(int64_t)sm.pairs, (int64_t)sm.used, (int64_t)sm.skipped, lay.tiles, 0, 0, 0, 0};
     memcpy(report, rep, sizeof rep);
@@ -802,18 +767,19 @@ int r3g_softras_backward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, cons
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     hipStream_t s = (hipStream_t)stream;
     c->softras_bwd_timed = false;
-    if (const int rc = softras_events(c)) return rc;
+    auto& ev = c->softras_ev;
+    if (const int rc = ev.make("softras")) return rc;
     SoftrasLayout lay;
     if (const int rc = c->softras_ws.grow(softras_workspace_bytes(height, width, &lay), s, "softras workspace")) return rc;
     char* ws = c->softras_ws.p;
     hipError_t e;
-    if ((e = hipEventRecord(c->softras_ev[3], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if (const int rc = ev.mark(3, s)) return rc;
     if ((e = softras_backward(ws, lay, g, d_pos, n_verts, d_tri, n_faces, d_face, d_dist, d_grad_alpha, d_grad_face, s)) != hipSuccess)
         return hip_fail(e, "softras_backward");
-    if ((e = hipEventRecord(c->softras_ev[4], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if (const int rc = ev.mark(4, s)) return rc;
     if ((e = softras_gather(d_grad_face, d_corner_start, d_corner_ids, n_verts, n_faces, d_grad_pos, s)) != hipSuccess)
         return hip_fail(e, "softras_gather");
-    if ((e = hipEventRecord(c->softras_ev[5], s)) != hipSuccess) return hip_fail(e, "hipEventRecord(softras)");
+    if (const int rc = ev.mark(5, s)) return rc;
     SoftrasSmall sm;      // (its sync: the caller may free its buffers, and a fault would surface here)
     if (const int rc = read_back(c->h_small, ws + lay.off_small, &sm, sizeof sm, "softras backward", s)) return rc;
     c->softras_bwd_timed = true;
@@ -826,16 +792,11 @@ int r3g_softras_times(r3g_ctx* ctx, double* ms) {
     if (!ctx || !ms) return fail(R3G_ERR_INVALID, "r3g_softras_times: null argument");
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c->softras_fwd_timed) return fail(R3G_ERR_STATE, "r3g_softras_times: no complete r3g_softras_forward on this context");
-    hipError_t e = hipEventSynchronize(c->softras_ev[2]);      // (the forward returns before its last kernel has run)
-    if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize(softras)");
+    if (const int rc = c->softras_ev.sync(2)) return rc;      // (the forward returns before its last kernel has run)
     for (int p = 0; p < r3g_sr::kPasses; ++p) {
         ms[p] = -1.0;
         if (p >= 2 && !c->softras_bwd_timed) continue;
-        const int a = p < 2 ? p : p + 1;
-        float t = 0.0f;
-        e = hipEventElapsedTime(&t, c->softras_ev[a], c->softras_ev[a + 1]);
-        if (e != hipSuccess) return hip_fail(e, "hipEventElapsedTime(softras)");
-        ms[p] = (double)t;
+        if (const int rc = c->softras_ev.elapsed(p < 2 ? p : p + 1, &ms[p])) return rc;      // (no pass between events 2 and 3)
     }
     return R3G_OK;
 }

@@ -9,6 +9,7 @@
 #include "dbscan_kernels.h"
 #include "dev_buf.h"
 #include "dmc_kernels.h"
+#include "events.h"
 #include "hier_kernels.h"
 #include "kernels.h"
 #include "mc_kernels.h"
@@ -24,7 +25,8 @@
 
 namespace r3g {
 
-// Every buffer below is a DevBuf (dev_buf.h): it goes with the context, and none of them is released by hand.
+// Every buffer below is a DevBuf (dev_buf.h) and every event a PassTimer's (events.h): they go with the context, and none of them is
+// released by hand.
 struct Ctx {
     int device = 0;
     int num_cu = 0;
@@ -49,24 +51,21 @@ struct Ctx {
     // normal orientation: the rows, labels and parities of one r3g_cloud_orient (nothing is kept between calls but the buffer)
     DevBuf orient_ws;
     // DBSCAN: the flags, roots, numbers and sizes of one r3g_cloud_dbscan (nothing is kept between calls but the buffer), and the
-    // events around the passes of the last call (made on first use; dbscan_timed: they bracket a complete run)
+    // events around the passes of the last call (events.h; made on first use; dbscan_timed: they bracket a complete run)
     DevBuf dbscan_ws;
-    hipEvent_t dbscan_ev[kDbscanPasses + 2] = {};
-    bool dbscan_ev_made = false;
+    PassTimer<kDbscanPasses + 2> dbscan_ev;
     bool dbscan_timed = false;
     // plane fit: the table, counts, mask and partial sums of one r3g_plane_ransac / r3g_plane_moments (nothing is kept between calls
     // but the buffer); h_plane is the pinned buffer its record is read back through (it does not fit h_small), made on first use;
     // the events bracket the passes of the last r3g_plane_ransac (plane_timed: a complete run)
     DevBuf plane_ws, h_plane{true};
-    hipEvent_t plane_ev[r3g_pl::kPasses + 1] = {};
-    bool plane_ev_made = false;
+    PassTimer<r3g_pl::kPasses + 1> plane_ev;
     bool plane_timed = false;
     // soft silhouette: the record, per-tile counts, starts and cursors of one r3g_softras_forward / _backward, and the (face, tile)
     // pairs of the forward (nothing is kept between calls but the buffers); events [0..2] bracket the bin and forward passes of the
     // last forward, [3..5] the backward and gather passes of the last backward (softras_fwd_timed / _bwd_timed: a complete call)
     DevBuf softras_ws, softras_pairs;
-    hipEvent_t softras_ev[6] = {};
-    bool softras_ev_made = false;
+    PassTimer<6> softras_ev;
     bool softras_fwd_timed = false, softras_bwd_timed = false;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not

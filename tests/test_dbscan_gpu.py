@@ -12,6 +12,7 @@ import emu_dbscan as emu
 pytestmark = pytest.mark.gpu
 
 RESOLUTIONS = (1, 3, 16, None)
+ERR_STATE = -4      # R3G_ERR_STATE of include/r3g.h
 NAMES = tuple(R.RANDOM) + tuple(R.fixed_clouds())
 _TWIN = {}
 
@@ -131,6 +132,47 @@ def test_empty_and_unusable_inputs_succeed():
     assert (labels.cpu().numpy() == -1).all() and (counts.cpu().numpy() == 0).all() and report_of(rep) == zero
     with ffi.device_lock(0), pytest.raises(ffi.R3GError):     # such a call leaves the context without a cloud
         cloud.knn(dev(np.zeros((1, 3))), 1)
+
+
+def test_times_belong_to_the_last_complete_run():
+    """r3g_cloud_dbscan_times on a context of its own: R3G_ERR_STATE before any run, five finite non-negative intervals after one
+    (inside the call, so their sum is at most its wall time between two synchronisations), and R3G_ERR_STATE again after a call
+    that clustered nothing (no point, or no usable one: both succeed)"""
+    import time
+    import torch
+    from r3g import cloud, ffi
+    L = ffi.lib()
+    rng = np.random.default_rng(5)
+    blobs = np.concatenate([rng.normal(c, 0.02, (200, 3)) for c in (0.0, 5.0)])      # two blobs of 200 points, 8.7 apart
+    p, nan = dev(blobs), dev(np.full((70, 3), np.nan))
+    lab = torch.zeros(len(blobs), dtype=torch.int32, device="cuda")
+    rep, ms = (ctypes.c_int64 * 8)(), (ctypes.c_double * len(cloud.DBSCAN_PASSES))()
+    ctx = ffi.new_context(0)
+
+    def run(pts, n):
+        return L.r3g_cloud_dbscan(ctx, ctypes.c_void_p(pts.data_ptr()), n, 0.2, 4, 0, ctypes.c_void_p(lab.data_ptr()), None, rep, ffi.stream_ptr())
+
+    try:
+        assert L.r3g_cloud_dbscan_times(ctx, ms) == ERR_STATE
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ffi.check(run(p, len(blobs)))
+        torch.cuda.synchronize()
+        wall_ms = 1e3 * (time.perf_counter() - t0)
+        assert dict(zip(R.REPORT, rep))["n_clusters"] == 2 and sorted(np.bincount(lab.cpu().numpy()).tolist()) == [200, 200]
+        ffi.check(L.r3g_cloud_dbscan_times(ctx, ms))
+        print("dbscan passes (ms):", list(ms), "wall (ms):", wall_ms)
+        assert len(ms) == 5 and all(np.isfinite(v) and v >= 0.0 for v in ms) and sum(ms) <= wall_ms
+        ffi.check(run(p, 0))
+        assert L.r3g_cloud_dbscan_times(ctx, ms) == ERR_STATE
+        ffi.check(run(p, len(blobs)))
+        ffi.check(L.r3g_cloud_dbscan_times(ctx, ms))
+        ffi.check(run(nan, 70))
+        assert L.r3g_cloud_dbscan_times(ctx, ms) == ERR_STATE
+        assert L.r3g_cloud_dbscan_times(ctx, None) == -1 and L.r3g_cloud_dbscan_times(None, ms) == -1
+    finally:
+        torch.cuda.synchronize()
+        L.r3g_destroy(ctx)
 
 
 def test_refusals():

@@ -85,6 +85,44 @@ def _cycle(torch, L, ffi, fixtures):
     return live()
 
 
+def test_a_context_goes_with_its_events_whichever_were_made():
+    """the timing events of a context (csrc/events.h) are made on first use, family by family: a context is destroyed after no use
+    at all, after DBSCAN alone, after a plane fit alone and after a soft-silhouette forward without its backward, and the process
+    goes on to run a call on the shared context"""
+    import torch
+    from r3g import cloud, ffi
+    L = ffi.lib()
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())        # noqa: E731
+    g = torch.Generator().manual_seed(11)
+    pts = torch.rand(256, 3, generator=g).cuda()
+    lab = torch.zeros(256, dtype=torch.int32, device="cuda")
+    triples = torch.randint(0, 256, (32, 3), generator=g).to(torch.int32).cuda()
+    pos = torch.tensor([[4.0, 4.0, 1.0], [28.0, 6.0, 1.0], [10.0, 27.0, 1.0]], device="cuda")
+    tri = torch.tensor([[0, 1, 2]], dtype=torch.int32, device="cuda")
+    alpha, face = torch.empty(32, 32, device="cuda"), torch.empty(32, 32, 2, dtype=torch.int32, device="cuda")
+    dist, zbuf = torch.empty(32, 32, 2, device="cuda"), torch.empty(32, 32, 2, device="cuda")
+    rep, plane = (ctypes.c_int64 * 8)(), (ctypes.c_double * 16)()
+    uses = {
+        "none": lambda ctx: 0,
+        "dbscan": lambda ctx: L.r3g_cloud_dbscan(ctx, ptr(pts), 256, 0.1, 3, 0, ptr(lab), None, rep, ffi.stream_ptr()),
+        "plane": lambda ctx: L.r3g_plane_ransac(ctx, ptr(pts), 256, ptr(triples), 32, 0.05, None, None, rep, plane, ffi.stream_ptr()),
+        "softras": lambda ctx: L.r3g_softras_forward(ctx, ptr(pos), 3, ptr(tri), 1, 32, 32, 2, 1.0, 4.0, ptr(alpha), ptr(face), ptr(dist),
+                                                     ptr(zbuf), rep, ffi.stream_ptr()),
+    }
+    live = ffi.counter("device_bytes_live")
+    for name, use in uses.items():
+        ctx = ffi.new_context(0)
+        try:
+            ffi.check(use(ctx))
+        finally:
+            torch.cuda.synchronize()
+            L.r3g_destroy(ctx)
+        assert ffi.counter("device_bytes_live") == live, name
+    assert float(alpha.max()) > 0.5 and int(rep[1]) == 1      # the triangle was drawn: one face used
+    labels, report = cloud.dbscan(pts, 0.1, 3)               # the shared context, afterwards
+    assert tuple(labels.shape) == (256,) and report["n_usable"] == 256
+
+
 def test_three_create_use_destroy_cycles_leave_the_same_bytes_live():
     import torch
     from oracle import hy3d_torch as H, unet_torch as U
