@@ -5,7 +5,7 @@
 
 Each translation unit is compiled to build/<name>.o and linked into 3d-re-gen_amd/libr3g.so.
 mc_kernels.hip is compiled with -ffp-contract=off (its fp64 ambiguity tests and interpolation must
-reproduce the sequential reference bit-for-bit), dmc_kernels.hip likewise (its positions are fixed to the bit; surf_compact_kernels.hip, the scan and workspace the two share, holds integers only and needs no flag), meshdist_kernels.hip (its distances equal the host twin's) meshinside_kernels.hip (its crossing counts equal the host twin's), meshfit_kernels.hip (its float64 sums equal the host twin's), meshtopo_kernels.hip (its quantised volumes equal the host twin's), meshfill_kernels.hip (its centroids equal the host twin's), recon_kernels.hip (its lattices equal the host twin's), orient_kernels.hip (its edge weights equal the host twin's), dbscan_kernels.hip (its float64 neighbour predicate equals the host twin's), plane_kernels.hip (its float64 inlier test and sums equal the host twin's), softras_kernels.hip (its float32 fragments, sigmoids and gradient sums equal the host twin's), cloud_kernels.hip (its squared distances equal the host twin's; grid_csr_kernels.hip, the workspace layout that meshdist, meshinside and cloud share, and scan_kernels.hip, the exclusive scan that they, the cleaners and meshfill share, hold integers only and need no flag) and r3g_api.cpp (it holds the registration's host solver, csrc/meshfit_core.h, which the twin shares, and the plane fit's eigen solver, csrc/plane_core.h, likewise); the MFMA kernels keep hipcc's default contraction.
+reproduce the sequential reference bit-for-bit), dmc_kernels.hip likewise (its positions are fixed to the bit; surf_compact_kernels.hip, the scan and workspace the two share, holds integers only and needs no flag), meshdist_kernels.hip (its distances equal the host twin's) meshinside_kernels.hip (its crossing counts equal the host twin's), meshfit_kernels.hip (its float64 sums equal the host twin's), meshtopo_kernels.hip (its quantised volumes equal the host twin's), meshfill_kernels.hip (its centroids equal the host twin's), recon_kernels.hip (its lattices equal the host twin's), orient_kernels.hip (its edge weights equal the host twin's), dbscan_kernels.hip (its float64 neighbour predicate equals the host twin's), plane_kernels.hip (its float64 inlier test and sums equal the host twin's), softras_kernels.hip (its float32 fragments, sigmoids and gradient sums equal the host twin's), facecloud_kernels.hip (its point-triangle distances, weights and gradient sums equal the host twin's), cloud_kernels.hip (its squared distances equal the host twin's; grid_csr_kernels.hip, the workspace layout that meshdist, meshinside and cloud share, and scan_kernels.hip, the exclusive scan that they, the cleaners and meshfill share, hold integers only and need no flag) and r3g_api.cpp (it holds the registration's host solver, csrc/meshfit_core.h, which the twin shares, and the plane fit's eigen solver, csrc/plane_core.h, likewise); the MFMA kernels keep hipcc's default contraction.
 hipcc cross-compiles without a GPU, so this also runs in the CPU-only build container.
 
 Staleness is decided by CONTENT, not by mtimes: build/manifest.json records, per object, the SHA-256 of its source,
@@ -32,7 +32,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-missing-
 PER_FILE = {"mc_kernels.hip": ["-ffp-contract=off"], "dmc_kernels.hip": ["-ffp-contract=off"], "tex_kernels.hip": ["-ffp-contract=off"],
             "meshdist_kernels.hip": ["-ffp-contract=off"], "meshinside_kernels.hip": ["-ffp-contract=off"],
             "meshfit_kernels.hip": ["-ffp-contract=off"], "meshtopo_kernels.hip": ["-ffp-contract=off"],
-            "meshfill_kernels.hip": ["-ffp-contract=off"], "cloud_kernels.hip": ["-ffp-contract=off"], "dbscan_kernels.hip": ["-ffp-contract=off"], "plane_kernels.hip": ["-ffp-contract=off"], "softras_kernels.hip": ["-ffp-contract=off"], "recon_kernels.hip": ["-ffp-contract=off"], "orient_kernels.hip": ["-ffp-contract=off"], "r3g_api.cpp": ["-ffp-contract=off"]}
+            "meshfill_kernels.hip": ["-ffp-contract=off"], "cloud_kernels.hip": ["-ffp-contract=off"], "facecloud_kernels.hip": ["-ffp-contract=off"], "dbscan_kernels.hip": ["-ffp-contract=off"], "plane_kernels.hip": ["-ffp-contract=off"], "softras_kernels.hip": ["-ffp-contract=off"], "recon_kernels.hip": ["-ffp-contract=off"], "orient_kernels.hip": ["-ffp-contract=off"], "r3g_api.cpp": ["-ffp-contract=off"]}
 
 
 def sources():

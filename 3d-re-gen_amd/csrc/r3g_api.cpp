@@ -801,6 +801,89 @@ int r3g_softras_times(r3g_ctx* ctx, double* ms) {
     return R3G_OK;
 }
 
+// ---- point clouds: every triangle's nearest point ---------------------------------------------------------
+static int facecloud_sizes(const char* who, int64_t n_verts, int64_t n_faces) {
+    if (n_verts < 0 || n_faces < 0) return fail(R3G_ERR_INVALID, "%s: negative size", who);
+    if (n_verts > 0x7fffffffll) return fail(R3G_ERR_INVALID, "%s: n_verts above 2^31 - 1", who);
+    if (n_faces > r3g_fc::kMaxFaces) return fail(R3G_ERR_INVALID, "%s: n_faces above 2^29", who);
+    return R3G_OK;
+}
+
+int r3g_cloud_faces(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_tri, int64_t n_faces, float* d_dist2,
+                    int32_t* d_index, float* d_weights, float* d_diff, int64_t* report, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_cloud_faces: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = facecloud_sizes("r3g_cloud_faces", n_verts, n_faces)) return rc;
+    if (!report || (n_faces && (!d_tri || !d_dist2 || !d_index || !d_weights || !d_diff)) || (n_verts && !d_verts))
+        return fail(R3G_ERR_INVALID, "r3g_cloud_faces: null buffer");
+    if (!c->cloud.built) return fail(R3G_ERR_STATE, "r3g_cloud_faces: no cloud on this context (r3g_cloud_build, _orient or _dbscan)");
+    int64_t rep[r3g_fc::kReport] = {0, 0, 0, 0};
+    if (n_faces == 0) {
+        memcpy(report, rep, sizeof rep);
+        return R3G_OK;
+    }
+    c->facecloud_fwd_timed = false;
+    auto& ev = c->facecloud_ev;
+    if (const int rc = ev.make("facecloud")) return rc;
+    FacecloudLayout lay;
+    if (const int rc = c->facecloud_ws.grow(facecloud_workspace_bytes(n_faces, &lay), s, "facecloud workspace")) return rc;
+    char* ws = c->facecloud_ws.p;
+    const GridCsrState<3>& cl = c->cloud;
+    const r3g_cl::Pt* sorted = cl.pairs.as<const r3g_cl::Pt>();
+    const unsigned* starts = (const unsigned*)(cl.ws.p + cl.lay.off_starts);
+    hipError_t e;
+    if (const int rc = ev.mark(0, s)) return rc;
+    if ((e = facecloud_classify(ws, lay, cl.grid, d_verts, n_verts, d_tri, n_faces, s)) != hipSuccess) return hip_fail(e, "facecloud_classify");
+    if (const int rc = ev.mark(1, s)) return rc;
+    if ((e = facecloud_narrow(ws, lay, cl.grid, sorted, starts, n_faces, d_dist2, d_index, d_weights, d_diff, s)) != hipSuccess)
+        return hip_fail(e, "facecloud_narrow");
+    if (const int rc = ev.mark(2, s)) return rc;
+    if ((e = facecloud_wide(ws, lay, cl.grid, sorted, starts, n_faces, d_dist2, d_index, d_weights, d_diff, s)) != hipSuccess)
+        return hip_fail(e, "facecloud_wide");
+    if (const int rc = ev.mark(3, s)) return rc;
+    static_assert(sizeof(FacecloudSmall) <= 64, "the pinned read-back buffer");
+    FacecloudSmall sm;      // (the call's one sync)
+    if (const int rc = read_back(c->h_small, ws + lay.off_small, &sm, sizeof sm, "facecloud", s)) return rc;
+    c->facecloud_fwd_timed = true;
+    rep[0] = (int64_t)sm.usable, rep[1] = (int64_t)sm.tests, rep[2] = (int64_t)sm.wide, rep[3] = (int64_t)sm.max_ring;
+    memcpy(report, rep, sizeof rep);
+    return R3G_OK;
+}
+
+int r3g_cloud_faces_backward(r3g_ctx* ctx, int64_t n_verts, int64_t n_faces, const float* d_grad_dist2, const int32_t* d_index,
+                             const float* d_weights, const float* d_diff, const int32_t* d_corner_start, const int32_t* d_corner_ids,
+                             float* d_grad_verts, void* stream) {
+    if (!ctx) return fail(R3G_ERR_INVALID, "r3g_cloud_faces_backward: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = facecloud_sizes("r3g_cloud_faces_backward", n_verts, n_faces)) return rc;
+    if ((n_faces && (!d_grad_dist2 || !d_index || !d_weights || !d_diff || !d_corner_ids)) || (n_verts && (!d_corner_start || !d_grad_verts)))
+        return fail(R3G_ERR_INVALID, "r3g_cloud_faces_backward: null buffer");
+    c->facecloud_bwd_timed = false;
+    if (n_verts == 0) return R3G_OK;
+    auto& ev = c->facecloud_ev;
+    if (const int rc = ev.make("facecloud")) return rc;
+    if (const int rc = ev.mark(4, s)) return rc;
+    const hipError_t e = facecloud_gather(d_grad_dist2, d_index, d_weights, d_diff, d_corner_start, d_corner_ids, n_verts, n_faces, d_grad_verts, s);
+    if (e != hipSuccess) return hip_fail(e, "facecloud_gather");
+    if (const int rc = ev.mark(5, s)) return rc;
+    c->facecloud_bwd_timed = true;
+    return R3G_OK;
+}
+
+int r3g_cloud_faces_times(r3g_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return fail(R3G_ERR_INVALID, "r3g_cloud_faces_times: null argument");
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c->facecloud_fwd_timed) return fail(R3G_ERR_STATE, "r3g_cloud_faces_times: no complete r3g_cloud_faces on this context");
+    for (int p = 0; p < 3; ++p)
+        if (const int rc = c->facecloud_ev.elapsed(p, &ms[p])) return rc;
+    ms[3] = -1.0;
+    if (!c->facecloud_bwd_timed) return R3G_OK;
+    if (const int rc = c->facecloud_ev.sync(5)) return rc;      // (the backward returns before its kernel has run)
+    return c->facecloud_ev.elapsed(4, &ms[3]);
+}
+
 // ---- Poisson surface on a uniform lattice ---------------------------------------------------------------
 static int recon_small(Ctx* c, ReconState* st, const char* what, hipStream_t s, ReconSmall* out) {
     return read_back(c->h_small, st->channels.p + recon_small_offset(st->lat.depth), out, sizeof(ReconSmall), what, s);

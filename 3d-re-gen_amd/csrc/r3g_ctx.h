@@ -10,6 +10,7 @@
 #include "dev_buf.h"
 #include "dmc_kernels.h"
 #include "events.h"
+#include "facecloud_kernels.h"
 #include "hier_kernels.h"
 #include "kernels.h"
 #include "mc_kernels.h"
@@ -67,6 +68,12 @@ struct Ctx {
     DevBuf softras_ws, softras_pairs;
     PassTimer<6> softras_ev;
     bool softras_fwd_timed = false, softras_bwd_timed = false;
+    // face-to-cloud distance: the record, face records and wide list of one r3g_cloud_faces (nothing is kept between calls but the
+    // buffer; the cloud it reads is `cloud` above, which it leaves alone); events [0..3] bracket the classify, narrow and wide passes
+    // of the last forward, [4..5] the gather of the last backward (facecloud_fwd_timed / _bwd_timed: a complete call)
+    DevBuf facecloud_ws;
+    PassTimer<6> facecloud_ev;
+    bool facecloud_fwd_timed = false, facecloud_bwd_timed = false;
     // mesh topology: mates, bodies, flips and sums of the last r3g_meshtopo_build (a state of its own: the distance grid and the
     // columns above may be held at the same time); h_topo is the pinned buffer its counts are read back through (they do not
     // fit h_small), made on first use

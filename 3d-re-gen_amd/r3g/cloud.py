@@ -65,6 +65,94 @@ def nearest(queries, points, resolution=None):
     return d2[:, 0].sqrt(), idx[:, 0]
 
 
+# ---- every triangle's nearest point ---------------------------------------------------------------------------
+FACES_REPORT = ("usable", "tests", "wide", "max_ring")
+FACES_PASSES = ("classify", "narrow", "wide", "gather")
+
+
+def _mesh_arg(verts, faces):
+    if not (torch.is_tensor(verts) and verts.is_cuda and torch.is_tensor(faces) and faces.is_cuda):
+        raise ValueError("verts and faces must live on the GPU (there is no CPU path)")
+    v = verts.detach().to(torch.float32).contiguous()
+    f = faces.detach().to(torch.int32).contiguous()
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError("expected verts [V,3] and faces [F,3]")
+    return v, f
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t.numel() else None)
+
+
+def face_nearest(verts, faces):
+    """r3g_cloud_faces against the last `build` (or `orient_normals`, `dbscan`) on the mesh's device: for every face the nearest
+    usable point of the cloud -> (dist2 float32 [F], index int32 [F], weights float32 [F,3], diff float32 [F,3], info dict: usable,
+    tests, wide, max_ring).  dist2 is section 4f's float32 point-triangle function, index the lowest original index attaining the
+    minimum; weights are the barycentrics of the face's closest point r to that point, diff = p_index - r.  A face with an index
+    outside [0, V) or a non-finite vertex gets (NaN, -1, 0, 0).  The cloud is read and left as it is; hold ffi.device_lock(device)
+    across build and face_nearest."""
+    v, f = _mesh_arg(verts, faces)
+    dev = v.device.index or 0
+    n = f.shape[0]
+    d2 = torch.empty((n,), dtype=torch.float32, device=v.device)
+    idx = torch.empty((n,), dtype=torch.int32, device=v.device)
+    w = torch.empty((n, 3), dtype=torch.float32, device=v.device)
+    diff = torch.empty((n, 3), dtype=torch.float32, device=v.device)
+    rep = (ctypes.c_int64 * 4)()
+    with ffi.device_lock(dev), torch.cuda.device(v.device):
+        ffi.check(ffi.lib().r3g_cloud_faces(ffi.context(dev), _ptr(v), v.shape[0], _ptr(f), n, _ptr(d2), _ptr(idx), _ptr(w), _ptr(diff), rep,
+                                            ffi.stream_ptr()))
+    return d2, idx, w, diff, dict(zip(FACES_REPORT, (int(x) for x in rep)))
+
+
+def face_nearest_backward(grad_dist2, index, weights, diff, csr, n_verts):
+    """r3g_cloud_faces_backward: grad_dist2 [F] and face_nearest's index, weights and diff -> grad_verts float32 [V,3], summed over
+    the corner lists csr = r3g.softras.corner_csr(faces, V) without floating-point atomics"""
+    g = grad_dist2.detach().to(torch.float32).contiguous()
+    start, ids = csr
+    if ids.numel() == 0 and g.shape[0]:      # no corner in range at all: the library refuses a NULL list while there are faces
+        ids = torch.full((1,), -1, dtype=torch.int32, device=g.device)
+    dev = g.device.index or 0
+    out = torch.empty((n_verts, 3), dtype=torch.float32, device=g.device)
+    with ffi.device_lock(dev), torch.cuda.device(g.device):
+        ffi.check(ffi.lib().r3g_cloud_faces_backward(ffi.context(dev), int(n_verts), g.shape[0], _ptr(g), _ptr(index), _ptr(weights), _ptr(diff),
+                                                     _ptr(start), _ptr(ids), _ptr(out), ffi.stream_ptr()))
+    return out
+
+
+def faces_times(device=0):
+    """milliseconds of the passes of the last complete `face_nearest` (and backward) on the device's context -> dict over FACES_PASSES
+    (gather: -1 while no backward has run)"""
+    ms = (ctypes.c_double * 4)()
+    with ffi.device_lock(device):
+        ffi.check(ffi.lib().r3g_cloud_faces_times(ffi.context(device), ms))
+    return dict(zip(FACES_PASSES, (float(v) for v in ms)))
+
+
+class FaceCloudDistance(torch.autograd.Function):
+    """verts [V,3] -> dist2 [F] of `face_nearest` against the cloud on the device's context, differentiable in the vertices:
+    FaceCloudDistance.apply(verts, faces, csr) with csr = r3g.softras.corner_csr(faces, V).  The backward holds each face's nearest
+    point (index) and the barycentric weights w of its closest point constant: d dist2 / d vertex_a = -2 w_a (p - r).  Because r
+    minimises over the triangle and p_index over the cloud, the derivatives through w and through the choice of the point vanish,
+    so this is the exact gradient wherever the distance is differentiable.  The CLOUD GETS NO GRADIENT: it lives on the context as
+    a packed copy and is no input here.  Unusable faces (dist2 NaN) and non-finite incoming gradients contribute nothing.
+    Do not hold ffi.device_lock(device) around backward(): autograd runs the backward on a thread of its own, which takes the lock
+    itself (as r3g.softras's does)."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, csr):
+        d2, idx, w, diff, info = face_nearest(verts, faces)
+        ctx.save_for_backward(idx, w, diff, csr[0], csr[1])
+        ctx.n_verts, ctx.dtype = verts.shape[0], verts.dtype
+        return d2.to(verts.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_dist2):
+        idx, w, diff, start, ids = ctx.saved_tensors
+        g = face_nearest_backward(grad_dist2, idx, w, diff, (start, ids), ctx.n_verts)
+        return g.to(ctx.dtype), None, None
+
+
 # ---- the reference's evaluation (src/evaluation/run_eval.py, src/utils/metrics.py), each stated once ---------------------------
 def _both_ways(a, b):
     """unsquared NN distances a->b and b->a"""

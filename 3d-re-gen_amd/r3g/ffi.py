@@ -63,6 +63,9 @@ SYMBOLS = {
     "r3g_cloud_orient": (_I, [_P, _P, _P, ctypes.c_int64, _I, _I, _P, _P, _I64P, _P]),
     "r3g_cloud_dbscan": (_I, [_P, _P, ctypes.c_int64, _D, _I, _I, _P, _P, _I64P, _P]),
     "r3g_cloud_dbscan_times": (_I, [_P, ctypes.POINTER(_D)]),
+    "r3g_cloud_faces": (_I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _I64P, _P]),
+    "r3g_cloud_faces_backward": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "r3g_cloud_faces_times": (_I, [_P, ctypes.POINTER(_D)]),
     "r3g_plane_ransac": (_I, [_P, _P, ctypes.c_int64, _P, _I, _D, _P, _P, _I64P, ctypes.POINTER(_D), _P]),
     "r3g_plane_moments": (_I, [_P, _P, ctypes.c_int64, _P, ctypes.POINTER(_D), _I64P, _P]),
     "r3g_plane_times": (_I, [_P, ctypes.POINTER(_D)]),

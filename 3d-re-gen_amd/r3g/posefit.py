@@ -6,14 +6,15 @@ loop (pose_matching_planar.py).  The silhouette comes from r3g.softras, the 3D t
 `point_face_loss` is the point -> nearest-face half of pytorch3d's point_mesh_face_distance, computed on the STATIC base mesh: the
 target points are moved by the inverse similarity in torch, r3g_meshdist_closest gives each one's closest point q on the base mesh,
 q is held constant, and the loss is s^2 mean |T^-1 p - q|^2.  Because q minimises the distance, the derivative through q vanishes:
-this is the exact gradient wherever the distance is differentiable (away from the medial axis).  The face -> nearest-point half is
-not computed."""
+this is the exact gradient wherever the distance is differentiable (away from the medial axis).  `face_point_loss` is the other half,
+face -> nearest point, on r3g.cloud's grid over the target points; `mesh_cloud_loss` is their sum, and
+`cloud_loss(..., face_to_point=True)` puts it into a fit.  The default fit uses the point half alone, as before."""
 import math
 
 import torch
 import torch.nn.functional as F
 
-from . import meshdist, softras
+from . import cloud, meshdist, softras
 
 DEFAULTS = {"silhoutte_loss": 1.0, "loss_3d": 1.0, "loss_bbox": 1.0, "rotation_speed_mult": 20.0, "learning_rate": 0.01, "max_iterations": 100,
             "early_stop_grad_threshold": 5e-3, "early_stop_min_iterations": 100, "sigma": 5e-7, "faces_per_pixel": 20}
@@ -135,10 +136,40 @@ def camera_renderer(faces, camera, size, config=None):
     return render
 
 
-def cloud_loss(base_verts, faces, points):
-    """the GPU 3D term of a fit: builds the base grid once -> point_loss(similarity)"""
+def face_point_loss(verts, faces, csr):
+    """verts [V, 3] (world, differentiable), faces [F, 3], csr = r3g.softras.corner_csr(faces, V), against the cloud of the last
+    r3g.cloud.build on the device: the mean over the usable faces of the squared distance to the face's nearest point
+    (r3g.cloud.FaceCloudDistance).  Each face's nearest point p and the barycentric weights w of its closest point r are held
+    constant, so d loss / d vertex_a = -2 w_a (p - r) / usable; because r minimises over the triangle and p over the cloud, the
+    derivatives through both vanish: this is the exact gradient wherever the distance is differentiable.  A face with an index
+    outside [0, V) or a non-finite vertex takes no part.  The cloud gets no gradient."""
+    d2 = cloud.FaceCloudDistance.apply(verts, faces, csr)
+    ok = ~torch.isnan(d2.detach())
+    return torch.where(ok, d2, torch.zeros_like(d2)).sum() / ok.sum().clamp(min=1)
+
+
+def mesh_cloud_loss(base_mesh_grid, points, similarity, verts, faces, csr):
+    """[UPSTREAM-RECALLED] pytorch3d.loss.point_mesh_face_distance(mesh, pcl) for one mesh and one cloud, as recalled: the mean over
+    the points of the squared distance to the nearest face (`point_face_loss`) plus the mean over the faces of the squared distance
+    to the nearest point (`face_point_loss`).  verts are the base vertices moved by `similarity`; the cloud of r3g.cloud.build is
+    `points`.  There is no min_triangle_area: a face without area is served by its edges."""
+    return point_face_loss(base_mesh_grid, points, similarity) + face_point_loss(verts, faces, csr)
+
+
+def cloud_loss(base_verts, faces, points, face_to_point=False):
+    """the GPU 3D term of a fit: builds the base grid once -> point_loss(similarity).  face_to_point=True adds the face -> point half
+    (`mesh_cloud_loss`): the cloud's grid is built once as well (it lives in the device's shared context until the next
+    r3g.cloud.build, orient_normals or dbscan there), and the closure moves the base vertices by the similarity in torch."""
     grid = BaseGrid(base_verts, faces)
-    return lambda similarity: point_face_loss(grid, points, similarity)
+    if not face_to_point:
+        return lambda similarity: point_face_loss(grid, points, similarity)
+    cloud.build(points)
+    csr = softras.corner_csr(faces, base_verts.shape[0])
+
+    def both(similarity):
+        s, R, t = similarity
+        return mesh_cloud_loss(grid, points, similarity, s * (base_verts @ R.T) + t, faces, csr)
+    return both
 
 
 def fit(model, config=None, callback=None):

@@ -453,6 +453,41 @@ int r3g_softras_backward(r3g_ctx* ctx, const float* d_pos, int64_t n_verts, cons
                          int64_t* report, void* stream);
 int r3g_softras_times(r3g_ctx* ctx, double* ms);
 
+/* ---- point clouds: every triangle's nearest point ---------------------------------------------------
+ * The face -> point half of pytorch3d's point_mesh_face_distance, against the cloud on this context (the last successful
+ * r3g_cloud_build, r3g_cloud_orient or r3g_cloud_dbscan), which the calls read and leave as it is.  For a triangle t and the
+ * usable points p_i: d2(t) = min_i tri_dist2(p_i, t), section 4f's float32 function without contraction, index(t) = the lowest
+ * original index attaining it: the minimum of (d2, i) in lexicographic order.  Beside it come r, the closest point of t to
+ * p_index, as barycentric weights w[3] (r = w0 a + w1 b + w2 c up to rounding; the s, v, w that formed r), and diff = p_index - r.
+ * A triangle without area is served by its edges; there is no min_triangle_area.  The definition is the text of
+ * csrc/facecloud_core.h and tests/emu/facecloud_twin.cpp reproduces every bit on the host.  The grid only prunes: the result does
+ * not depend on the cloud's resolution.
+ *
+ * r3g_cloud_faces: d_verts float32 [n_verts][3], d_tri int32 [n_faces][3] -> d_dist2 float32 [n_faces], d_index int32 [n_faces],
+ *   d_weights float32 [n_faces][3], d_diff float32 [n_faces][3].  A face is unusable when an index lies outside [0, n_verts) or a
+ *   vertex is not finite: it gets d2 = NaN 0x7fc00000, index -1, weights 0, diff 0, and nothing is read through its indices.
+ *   report (int64 [4]): usable faces, point-triangle tests, faces walked by a wave (a cell box of more than 64 cells), the largest
+ *   ring walked.  Launches: classify, narrow, wide.  Synchronises `stream` once, for the report.  Without a cloud on this context:
+ *   R3G_ERR_STATE.  n_faces == 0: success, a zero report, nothing launched.  n_verts or n_faces negative, n_verts above 2^31 - 1,
+ *   n_faces above 2^29, report NULL, d_tri or an output NULL with n_faces > 0, d_verts NULL with n_verts > 0: R3G_ERR_INVALID before
+ *   any launch.
+ * r3g_cloud_faces_backward: d_grad_dist2 float32 [n_faces], and d_index, d_weights, d_diff as the forward wrote them ->
+ *   d_grad_verts float32 [n_verts][3].  With w and index held constant d d2 / d vertex_a = -2 w_a diff, which is the exact
+ *   gradient wherever the distance is differentiable.  A vertex sums its corners d_corner_ids[d_corner_start[v] ..
+ *   d_corner_start[v + 1]) (int32; corner 3 f + a, ascending: section 4o's lists) sequentially in float32, each corner adding
+ *   g_f * (-2 w[f][a]) * diff[f]: no floating-point atomics, the same bits on every call.  A corner adds nothing when its face is
+ *   unusable or its g_f is NaN or infinite.  Needs no cloud.  Does not synchronise.  n_verts or n_faces negative, n_verts above
+ *   2^31 - 1, n_faces above 2^29, a NULL buffer with a non-zero size (d_corner_start, d_grad_verts with n_verts > 0; the others with
+ *   n_faces > 0): R3G_ERR_INVALID before any launch.  n_verts == 0: success, nothing launched.
+ * r3g_cloud_faces_times: milliseconds between HIP events of the last complete calls on this context, ms double [4]: classify,
+ *   narrow, wide, gather; -1 for the last while no backward has run.  Without a forward that launched: R3G_ERR_STATE. */
+int r3g_cloud_faces(r3g_ctx* ctx, const float* d_verts, int64_t n_verts, const int32_t* d_tri, int64_t n_faces, float* d_dist2,
+                    int32_t* d_index, float* d_weights, float* d_diff, int64_t* report, void* stream);
+int r3g_cloud_faces_backward(r3g_ctx* ctx, int64_t n_verts, int64_t n_faces, const float* d_grad_dist2, const int32_t* d_index,
+                             const float* d_weights, const float* d_diff, const int32_t* d_corner_start, const int32_t* d_corner_ids,
+                             float* d_grad_verts, void* stream);
+int r3g_cloud_faces_times(r3g_ctx* ctx, double* ms);
+
 /* ---- point clouds: Poisson surface on a uniform lattice -----------------------------------------
  * Oriented points -> an implicit function chi whose level set is the surface (r3g/recon.py runs marching cubes on it).  The
  * lattice has n = 2^depth + 1 nodes per axis over the cube (centre, side), node (i0, i1, i2) stored [i0][i1][i2].  Every value is

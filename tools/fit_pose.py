@@ -3,10 +3,12 @@
 floor is known (r3g.posefit):
 
     python tools/fit_pose.py MESH.glb MASK.png CLOUD.ply --camera fx,fy,cx,cy [--sigma 5e-7] [--iterations 100] [--lr 0.01]
+                             [--face-to-point]
 
 The cloud and the mesh are in the camera's frame (x right, y down, z forward).  The floor comes from r3g.plane.fit_floor on the
-cloud; the mask's size is the render size.  Prints one JSON line: the plane, the fitted translation_uv, yaw (radians) and scale,
-the first and last loss and the iterations run.
+cloud; the mask's size is the render size.  --face-to-point adds the face -> nearest-point half to the 3D term (section 4p), which
+makes it pytorch3d's point_mesh_face_distance; without it the term is the point -> face half alone.  Prints one JSON line: the
+plane, the fitted translation_uv, yaw (radians) and scale, the first and last loss and the iterations run.
 """
 import argparse
 import json
@@ -27,6 +29,7 @@ def main(argv=None):
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--face-to-point", action="store_true", help="add the face -> nearest-point half to the 3D term")
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -46,9 +49,9 @@ def main(argv=None):
     cfg = {"sigma": a.sigma, "max_iterations": a.iterations, "learning_rate": a.lr}
     cam = dict(R=torch.eye(3, device="cuda"), t=torch.zeros(3, device="cuda"), fx=fx, fy=fy, cx=cx, cy=cy)
     pose = posefit.PlanarPose(verts, faces, m, posefit.camera_renderer(faces, cam, mask.shape, cfg), mask, config=cfg)
-    pose.point_loss = posefit.cloud_loss(pose.base_verts_plane, faces, pts)
+    pose.point_loss = posefit.cloud_loss(pose.base_verts_plane, faces, pts, face_to_point=a.face_to_point)
     out = posefit.fit(pose)
-    print(json.dumps({"tool": "fit_pose", "faces": int(faces.shape[0]), "points": int(pts.shape[0]), "size": list(mask.shape),
+    print(json.dumps({"tool": "fit_pose", "face_to_point": bool(a.face_to_point), "faces": int(faces.shape[0]), "points": int(pts.shape[0]), "size": list(mask.shape),
                       "plane_method": floor["method"], "normal": [float(v) for v in floor["normal"].cpu()],
                       "translation_uv": [float(v) for v in pose.translation_uv.detach().cpu().reshape(-1)],
                       "yaw": float(pose.rotation_yaw.detach()) * pose.config["rotation_speed_mult"], "scale": float(pose.scale.detach()),
